@@ -1,14 +1,19 @@
 #!/usr/bin/env python3
 """bench.py -- headline benchmark of the ORB front-end + local-BA hot path on MI355X.
 
-  python bench.py --gpus N --steps K --warmup W
+  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
   (N > 1: python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 ... bench.py --gpus N ...)
+
+A plain run sets up, warms up, times the K steps and prints the headline line (metric, value, unit, ms_per_step, ...).
+--dump-outputs DIR writes what the last timed step computed (rank 0's frames) as DIR/*.npy, see dump_outputs().
+--full adds everything else the line used to carry, after the timed steps: value_cold, the per-stage timing and the roofline,
+the CPU baseline (--no-cpu-baseline leaves it out) and the extras below (--no-extra leaves them out).
 
 A "step" = one pass of the hot path over one batch of synthetic input, inputs already resident in HBM:
   * ORB extraction of BASELINE.json configs[1]: 64 synthetic 640x480 frames, nFeatures 1000, 8 levels   -> `value`
   * inside the same timed step, on the same stream: Hamming best-2 matching of consecutive frames'
     descriptor sets is NOT included in `value` (reported under "extra").
-Local BA (configs[3], 20 KF x 3000 MP) and Hamming (configs[2]) are measured after the timed region and reported
+Local BA (configs[3], 20 KF x 3000 MP) and Hamming (configs[2]) are measured after the timed region (--full) and reported
 under "extra" -- the combined BASELINE metric has two halves; `value` is its first half (ORB kpts/s), the BA half
 is extra.ba (one window, latency at the C-ABI) and extra.ba_batch (25 windows per call, residual blocks/s).
 `python bench.py --gpus N` (N > 1) starts its own torch.distributed.run child; extra.sequence is BASELINE configs[4].
@@ -96,8 +101,12 @@ def main():
     ap.add_argument("--steps", type=int, default=100)     # (a step is 0.28 ms: the GPU's clocks need ~15 ms of work to settle --
     ap.add_argument("--warmup", type=int, default=50)     #  3 warm-up steps read 0.299 ms per step, 10 read 0.290, 50 read 0.275)
     ap.add_argument("--batch", type=int, default=64)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extra", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also measure value_cold, the per-stage timing, the roofline, the CPU baseline and the extras")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: leave out the CPU baseline")
+    ap.add_argument("--no-extra", action="store_true", help="with --full: leave out the extras (sequence, Hamming, BA, class surface, mixed load)")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write the keypoints and descriptors of the last timed step (rank 0's frames) to DIR/*.npy")
     ap.add_argument("--dry-run", action="store_true",
                     help="rehearse the N-rank launch and the collectives on the CPU (gloo, stand-in payloads, no HIP call, no timing)")
     args = ap.parse_args()
@@ -168,6 +177,27 @@ def main():
     torch.cuda.synchronize()
     barrier()
     t1 = time.perf_counter()
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, d_kps.cpu().numpy(), d_desc.cpu().numpy(), d_n.cpu().numpy())
+    # whole-job throughput: SUM of the units of all ranks / MAX of the elapsed times (RCCL all_reduce when N > 1)
+    value, kp_all_steps, elapsed = shard.aggregate_throughput(int(d_n.to(torch.int64).sum().item()) * args.steps, t1 - t0, device=dev)
+    kp_total_step = int(round(kp_all_steps / args.steps))
+    out = {
+        "metric": "ORB kpts/s (640x480, 1k feat) + local-BA residuals/s (20 KF x 3k pts)",
+        "value": round(value, 1), "unit": "kpts/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "settle_steps": SETTLE_STEPS,
+        "ms_per_step": round(elapsed / args.steps * 1e3, 4), "higher_is_better": True, "scaling": "weak",
+        "vs_baseline": None, "dtype": "u8", "data": "synthetic",
+        "config": {"workload": "ORBextractor FAST+rBRIEF, 640x480, 8-level pyramid, nFeatures 1000, batch=%d synthetic frames per GPU (BASELINE configs[1])" % B,
+                   "frames_per_step": B * world, "keypoints_per_step": kp_total_step, "parallelism": "frames sharded per GPU, no data-path collective"},
+    }
+    if not args.full:
+        if world > 1:
+            dist.barrier()
+            dist.destroy_process_group()
+        if rank == 0:
+            print(json.dumps(out))
+        return 0
+    # ---- --full from here on: everything beside the headline, outside the timed region
     # ---- `value_cold` (VERDICT r3 next #8a): the timed loop above replays the SAME 64 frames -- 19.7 MB of input and the 60 MB pyramid stay in the
     #      256 MB Infinity Cache, so none of its traffic is HBM traffic.  Here sixteen DISTINCT batches (the frames shifted by another offset each:
     #      other corners, other keypoints; 315 MB of input) rotate through the same extractor, K steps, same barriers: every step's input comes from HBM.
@@ -208,9 +238,6 @@ def main():
     torch.cuda.synchronize()
     stage_ms = ext.last_timing()
     ext.set_profiling(False)
-    # whole-job throughput: SUM of the units of all ranks / MAX of the elapsed times (RCCL all_reduce when N > 1)
-    value, kp_all_steps, elapsed = shard.aggregate_throughput(int(d_n.to(torch.int64).sum().item()) * args.steps, t1 - t0, device=dev)
-    kp_total_step = int(round(kp_all_steps / args.steps))
 
     # ---- roofline of the dominant kernel (largest average HIP-event duration over the timed steps)
     n_host = d_n.cpu().numpy()
@@ -325,15 +352,7 @@ def main():
                     cpu_baseline[k_] = fn_()
                 except Exception:  # noqa: BLE001
                     pass
-        out = {
-            "metric": "ORB kpts/s (640x480, 1k feat) + local-BA residuals/s (20 KF x 3k pts)",
-            "value": round(value, 1), "unit": "kpts/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "settle_steps": SETTLE_STEPS,
-            "ms_per_step": round(elapsed / args.steps * 1e3, 4), "higher_is_better": True, "scaling": "weak",
-            "vs_baseline": None, "dtype": "u8", "data": "synthetic",
-            "config": {"workload": "ORBextractor FAST+rBRIEF, 640x480, 8-level pyramid, nFeatures 1000, batch=%d synthetic frames per GPU (BASELINE configs[1])" % B,
-                       "frames_per_step": B * world, "keypoints_per_step": kp_total_step, "parallelism": "frames sharded per GPU, no data-path collective"},
-            "roofline": roofline, "cpu_baseline": cpu_baseline, "extra": extra,
-        }
+        out.update({"roofline": roofline, "cpu_baseline": cpu_baseline, "extra": extra})
         out.update(cold)
         print(json.dumps(out))
     if seq_out and seq_out.get("allgather_ok") is False:
@@ -511,6 +530,34 @@ def ba_roofline(extra):
     except Exception as ex:  # noqa: BLE001
         out["error"] = repr(ex)
     return out
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+KP_FIELDS = ("x", "y", "size", "angle", "response", "octave", "class_id")
+
+
+def dump_outputs(path, kps, desc, n):
+    """--dump-outputs: what the caller of the timed step receives, host copies taken right after the last timed step.  kps [B, cap, 28] /
+    desc [B, cap, 32] uint8 and n [B] int32 as the extractor left them; frame f's result is the first n[f] rows of its block.  Written:
+      keypoint_counts.npy  [B] float64
+      keypoints.npy        [N, 7] float64, the valid rows of every frame in frame order, columns KP_FIELDS (cv::KeyPoint)
+      descriptors.npy      [N, 32] float32, the descriptor bytes of the same rows
+    Should the rows exceed 64 MB (large --batch), a fixed sample of them is written instead (seed 0, ascending), with its row numbers in
+    sample_rows.npy."""
+    from eao_fusion_amd.orb import KP_DTYPE
+    os.makedirs(path, exist_ok=True)
+    rec = np.ascontiguousarray(kps).view(KP_DTYPE)[..., 0]
+    rows = np.concatenate([rec[f, :n[f]] for f in range(len(n))])
+    d = np.concatenate([desc[f, :n[f]] for f in range(len(n))])
+    per_row = 8 * len(KP_FIELDS) + 4 * d.shape[1]
+    budget = DUMP_LIMIT_BYTES - 8 * len(n) - 4096          # (the counts and the .npy headers)
+    if len(rows) * per_row > budget:
+        keep = np.sort(np.random.default_rng(0).choice(len(rows), budget // (per_row + 8), replace=False))
+        rows, d = rows[keep], d[keep]
+        np.save(os.path.join(path, "sample_rows.npy"), keep.astype(np.float64))
+    np.save(os.path.join(path, "keypoint_counts.npy"), np.asarray(n, np.float64))
+    np.save(os.path.join(path, "keypoints.npy"), np.stack([rows[k].astype(np.float64) for k in KP_FIELDS], axis=1))
+    np.save(os.path.join(path, "descriptors.npy"), d.astype(np.float32))
 
 
 def self_launch(n):

@@ -25,12 +25,20 @@ def _parse_inc(path):
 
 
 def test_fixture_equals_reference_text_when_present():
-    if not os.path.isdir("/root/reference/src"):
-        pytest.skip("the reference tree only exists in the build container")
+    """Every entry of the fixture is what tools/gen_ref_constants.py records for its SPEC row: same name, type, file:line and note, in SPEC's
+    order; a literal of the form the row's regular expression captures; the value parse() derives from it.  With a reference tree named by
+    EAO_REFERENCE_DIR, re-parsing its text gives the same entries."""
     sys.path.insert(0, os.path.join(ROOT, "tools"))
     import gen_ref_constants as G
-    now = G.parse()
-    assert [(e["name"], e["literal"], e["where"]) for e in now] == [(e["name"], e["literal"], e["where"]) for e in FIX]
+    assert [(e["name"], e["type"], e["where"], e["note"]) for e in FIX] == [(n, t, "%s:%d" % (rel, line), note) for n, t, rel, line, _rx, note in G.SPEC]
+    for e, (name, ctype, _rel, _line, rx, _note) in zip(FIX, G.SPEC):
+        group = re.search(r"(?<!\\)\(((?:\\.|[^()\\])*)\)", rx).group(1)      # the row's one capture group
+        assert re.fullmatch(group, e["literal"]), (name, group, e["literal"])
+        assert e["value"] == (int(e["literal"]) if ctype == "int" else float(e["literal"])) and type(e["value"]) is (int if ctype == "int" else float), name
+    ref = os.environ.get("EAO_REFERENCE_DIR")
+    if ref:
+        now = G.parse(ref)
+        assert [(e["name"], e["literal"], e["where"]) for e in now] == [(e["name"], e["literal"], e["where"]) for e in FIX]
 
 
 @pytest.mark.parametrize("who", ["product", "oracle"])

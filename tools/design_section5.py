@@ -1,7 +1,7 @@
 """Renders the numeric tables of DESIGN.md section 5 from the round's committed evidence files and writes them between the
    <!-- MEASURED:BEGIN --> / <!-- MEASURED:END --> markers (the prose around the markers is hand-written).
        python tools/design_section5.py [r06]
-   Inputs: profiles/<R>_bench_line.json (python bench.py, default flags), profiles/<R>_kernel_stats_bench.csv (rocprofv3 --kernel-trace --stats of
+   Inputs: profiles/<R>_bench_line.json (python bench.py --full), profiles/<R>_kernel_stats_bench.csv (rocprofv3 --kernel-trace --stats of
    the same command), profiles/<R>_pmc_traffic.json, profiles/<R>_ba_pmc_traffic.json, profiles/<R>_ba_{single,batch}_kernel_stats.csv."""
 import csv, json, os, sys
 
@@ -38,7 +38,7 @@ def main():
     rf = dict(ex.get("flat", {}), **line["roofline"])      # (round 6: the driver-visible head of the record in `roofline`, the other flat figures in extra.flat)
     out = []
     w = out.append
-    w("Source: `profiles/%s_bench_line.json` (`python bench.py`, default flags, HEAD of the round's last kernel edit).  Every row can be recomputed from the"
+    w("Source: `profiles/%s_bench_line.json` (`python bench.py --full`, HEAD of the round's last kernel edit).  Every row can be recomputed from the"
       " flat scalars of `roofline` in the driver's `BENCH_%s.json`.\n" % (R, R))
     w("| Quantity | Value | Verdict-r5 target (round 5's figure) | Where it is measured |")
     w("|---|---|---|---|")
@@ -96,7 +96,7 @@ def main():
                                                                       "%.3f / %.3f / %.3f" % (b["frame_ms"]["p50"], b["frame_ms"]["p99"], b["frame_ms"]["max"]) if b else "—", ", ".join(bg) or "—"))
     # ---- kernel table
     ks = stats(P("kernel_stats_bench.csv"))
-    w("\nPer-kernel durations, `profiles/%s_kernel_stats_bench.csv` (`rocprofv3 --kernel-trace --stats -- python3 bench.py --steps 20 --warmup 3`; the ORB rows mix the"
+    w("\nPer-kernel durations, `profiles/%s_kernel_stats_bench.csv` (`rocprofv3 --kernel-trace --stats -- python3 bench.py --steps 20 --warmup 3 --full`; the ORB rows mix the"
       " 64-frame batches with the single-frame and 256-frame calls of the extras, the stage events of the table above are the 64-frame figures):\n" % R)
     w("| Kernel | calls | avg µs | min µs | max µs | % of GPU time |")
     w("|---|---|---|---|---|---|")

@@ -44,7 +44,7 @@ a, b, h = load(R + "_sq_a"), load(R + "_sq_b"), load(R + "_sq_h")
 fe, wr = load(R + "_fetch"), load(R + "_write")
 batch = int(os.environ.get("EAO_PMC_BATCH", "64"))
 steps = a.get("k_blur7", {}).get("launches", 1)         # one blur launch per bench step (timed and profiled alike)
-sq = {"_note": "rocprofv3 --kernel-trace --pmc <8 SQ counters> -- python3 bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-extra (two passes); "
+sq = {"_note": "rocprofv3 --kernel-trace --pmc <8 SQ counters> -- python3 bench.py --steps 3 --warmup 1 --full --no-cpu-baseline --no-extra (two passes); "
                "values are PER LAUNCH (sum over the chip).  SQ_ACTIVE_INST_* / SQ_WAVE_CYCLES / SQ_WAIT_* count quad-cycles.  k_fast_cells<true, 48> "
                "is the whole-stage launch of the profiled steps (the <false, 48> rows are the shares of the overlapped schedule).",
       "batch": batch, "source_sha16": SRC, "kernels": {}, "kernels_extra": {}}
@@ -75,7 +75,7 @@ with open(os.path.join(O, R + "_pmc_sq.txt"), "w") as f:
         f.write(k[:22].ljust(22) + "".join(("%.4g" % d[c]).rjust(17) if c in d else "-".rjust(17) for c in cols) + "\n")
 print(open(os.path.join(O, R + "_pmc_sq.txt")).read())
 # traffic
-tr = {"_note": "rocprofv3 --kernel-trace --pmc FETCH_SIZE / --pmc WRITE_SIZE (two separate passes) -- python3 bench.py --steps 3 --warmup 1 --no-cpu-baseline "
+tr = {"_note": "rocprofv3 --kernel-trace --pmc FETCH_SIZE / --pmc WRITE_SIZE (two separate passes) -- python3 bench.py --steps 3 --warmup 1 --full --no-cpu-baseline "
                "--no-extra; bytes = KiB counter x 1024, RAW counters.  MI355X_MICROARCH.md (HBM): FETCH_SIZE reports half the bytes of a streaming read on gfx950 "
                "-- bench.py doubles it; self-check: k_blur7 reads 22/16 x 60.8 MB = 83.6 MB (16-row strips + 6 halo rows), 2 x FETCH_SIZE counted below.",
       "batch": batch, "source_sha16": SRC, "kernels": {}}

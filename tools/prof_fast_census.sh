@@ -5,8 +5,8 @@ cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"
 O=gpurun_out/r06_fast; mkdir -p $O
 for stop in 1 2 3 0; do
   rm -rf $O/pmc_$stop $O/tr_$stop
-  EAO_FAST_STOP_AFTER=$stop rocprofv3 --kernel-trace --pmc SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_WAVES --output-format csv -d $O/pmc_$stop -o c -- python3 bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-extra > $O/pmc_$stop.log 2>&1 || { tail -5 $O/pmc_$stop.log; exit 1; }
-  EAO_FAST_STOP_AFTER=$stop rocprofv3 --kernel-trace --stats --output-format csv -d $O/tr_$stop -o t -- python3 bench.py --steps 20 --warmup 3 --no-cpu-baseline --no-extra > $O/tr_$stop.log 2>&1 || { tail -5 $O/tr_$stop.log; exit 1; }
+  EAO_FAST_STOP_AFTER=$stop rocprofv3 --kernel-trace --pmc SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_WAVES --output-format csv -d $O/pmc_$stop -o c -- python3 bench.py --steps 3 --warmup 1 --full --no-cpu-baseline --no-extra > $O/pmc_$stop.log 2>&1 || { tail -5 $O/pmc_$stop.log; exit 1; }
+  EAO_FAST_STOP_AFTER=$stop rocprofv3 --kernel-trace --stats --output-format csv -d $O/tr_$stop -o t -- python3 bench.py --steps 20 --warmup 3 --full --no-cpu-baseline --no-extra > $O/tr_$stop.log 2>&1 || { tail -5 $O/tr_$stop.log; exit 1; }
 done
 python3 - <<'PY' | tee gpurun_out/r06_fast_census.txt
 import csv, glob, collections

@@ -8,13 +8,13 @@ cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"
 O=gpurun_out
 rm -rf $O/${R}_stats $O/${R}_sq_a $O/${R}_sq_b $O/${R}_fetch $O/${R}_write $O/${R}_sq_h $O/${R}_ba_batch $O/${R}_ba_single
 # 1. per-kernel durations of the same command the driver runs
-rocprofv3 --kernel-trace --stats --output-format csv -d $O/${R}_stats -o bench -- python3 bench.py --steps 20 --warmup 3 > $O/${R}_bench_line_under_rocprof.json 2> $O/${R}_stats.err
+rocprofv3 --kernel-trace --stats --output-format csv -d $O/${R}_stats -o bench -- python3 bench.py --steps 20 --warmup 3 --full > $O/${R}_bench_line_under_rocprof.json 2> $O/${R}_stats.err
 f=$(find $O/${R}_stats -name "*kernel_stats.csv" | head -1)
 cp "$f" $O/${R}_kernel_stats_raw.csv
-python3 tools/summarize_rocprof.py "$f" $O/${R}_kernel_stats_bench.csv "python3 bench.py --steps 20 --warmup 3" | head -30
+python3 tools/summarize_rocprof.py "$f" $O/${R}_kernel_stats_bench.csv "python3 bench.py --steps 20 --warmup 3 --full" | head -30
 echo "--- bench line under rocprofv3"; tail -c 400 $O/${R}_bench_line_under_rocprof.json; echo
 # 2. SQ counters of the ORB kernels (two passes: 8 SQ slots each)
-BENCH="python3 bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-extra"
+BENCH="python3 bench.py --steps 3 --warmup 1 --full --no-cpu-baseline --no-extra"
 rocprofv3 --kernel-trace --pmc SQ_WAVES SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_INSTS_VALU SQ_INSTS_LDS SQ_ACTIVE_INST_VALU SQ_ACTIVE_INST_LDS SQ_WAIT_INST_LDS \
     --output-format csv -d $O/${R}_sq_a -o a -- $BENCH > $O/${R}_sq_a.log 2>&1
 rocprofv3 --kernel-trace --pmc SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_INSTS_SALU SQ_INSTS_VMEM_RD SQ_INSTS_VMEM_WR \
@@ -43,7 +43,7 @@ python3 tools/summarize_rocprof.py "$f" $O/${R}_ba_single_kernel_stats.csv "pyth
 ./tools/ubench/f64_simd > $O/${R}_ubench_f64.txt 2>&1
 ./tools/ubench/lds_ops > $O/${R}_ubench_lds.txt 2>&1
 # 6. the default bench line itself
-python3 bench.py > $O/${R}_bench_line.json 2> $O/${R}_bench_line.err; tail -c 600 $O/${R}_bench_line.json; echo
+python3 bench.py --full > $O/${R}_bench_line.json 2> $O/${R}_bench_line.err; tail -c 600 $O/${R}_bench_line.json; echo
 # 7. the map-scale BundleAdjustment benchmarks: host-phase stamps, the plan line, rocprofv3 kernel summaries (fresh directories: this step removes nothing)
 G=$O/${R}_gba_$$; GB=$O/${R}_gbab_$$
 rocprofv3 --kernel-trace --stats --output-format csv -d $G -o s -- python3 tools/dbg_gba.py > $O/${R}_gba.log 2>&1
