@@ -410,3 +410,219 @@ def add_ba_planes(prob, n_planes=5, seed=7000, angle_noise_deg=0.3, dist_noise=0
     out.update(planes=np.array(init, np.float32), planes_gt=np.array(gt, np.float32), pedge_plane=np.array(pe_pl, np.int32),
                pedge_cam=np.array(pe_cam, np.int32), pedge_obs=pe_obs.astype(np.float32))
     return out
+
+
+# ---- contended scenes -------------------------------------------------------------------------------------------------
+# synth_tracking / synth_search_scene give every map point an i.i.d. descriptor and flip a few percent of its bits per
+# observation: a true match sits ~13 bits away, everything else ~128, so no two queries ever compete for a keypoint and the
+# greedy order of the guided searches (a keypoint claimed by an earlier query is skipped by every later one) decides
+# nothing.  The generators below plant the contention real input is full of -- landmarks created twice, one corner at two
+# pyramid levels, exact distance ties, chains of queries each wanting its predecessor's keypoint, rotation-histogram ties --
+# and return the same dicts as the generators above.
+
+TIE_CASES = (   # (best, second, same level): equal distances, TH_HIGH / TH_LOW and one bit either side, best == nnratio * second
+    (30, 30, False), (30, 30, True), (100, 130, False), (101, 130, False), (99, 130, False), (50, 90, False), (49, 90, True), (51, 90, True),
+    (40, 50, True), (41, 50, True), (39, 50, True), (36, 60, True), (37, 60, True), (35, 60, True), (45, 50, True), (46, 50, True))
+
+
+def _flip_exact(d, k, rng):
+    """d with exactly k distinct bits flipped."""
+    bits = np.unpackbits(d)
+    idx = rng.choice(256, size=k, replace=False)
+    bits[idx] ^= 1
+    return np.packbits(bits)
+
+
+def synth_tracking_contended(n=400, seed=7600, dup_groups=40, chains=(120,), ratio_chains=(60,), ties=2, hist=None, hist_only=False,
+                             extra_points=0, prior_frac=0.1, moved=0.03, mono_frac=0.3, occupied_frac=0.03, chain_level=1, chain_step=1.0):
+    """A tracked frame pair like synth_tracking's -- (cur, last, mps), the same keys -- whose map points compete for keypoints:
+      background  n points as synth_tracking draws them (true keypoint at a few px, ~6 % of the bits flipped) plus 10 % clutter; every background
+                  match turns by 348 +- 4 deg (histogram bin 29 of 30)
+      dup_groups  groups of 2-4 map points at one pixel (+-0.3 px, the same depth to 1 mm) with the same descriptor up to 0-3 bits, in ascending or
+                  descending order of those bits; their corner is detected twice at the same pixel, at octaves L and L-1 (or both at L), 12 and
+                  12 + {0, 1, 2, 3, 5} bits from the group's descriptor; a fraction `prior_frac` of these corners is occupied before the search
+      chains      per entry a chain of that many points 1 px apart along a row: point j is 20 bits from keypoint j-1 and 30 bits from keypoint j, so
+                  every point's outcome waits for its predecessor's (one assignment round per link)
+      ratio_chains the same with 40 / 48 bits at one level: alone, point j fails the 0.8 ratio test; with keypoint j-1 claimed it matches keypoint j
+      ties        per TIE_CASES entry this many pairs of (best, second) keypoints at exactly planted distances, queried by two map points with one
+                  descriptor (the second sees what the first left)
+      hist        {bin: count} of isolated probes (one point, one keypoint 15 bits away, nothing else near) whose rotation falls into that bin of
+                  SearchByProjection(Cur, Last)'s histogram; a third of them sit exactly half-way from the previous bin (or 1e-3 deg inside)
+      hist_only   only the probes (n, dup_groups, chains, ties ignored): the histogram's counts are then exact by construction
+      extra_points map points beyond those (random descriptors, most out of view): local maps past 4096 / 8192 points
+    The map points are in index order as listed; the keypoints are shuffled.  Deterministic in `seed`."""
+    rng = np.random.default_rng(seed)
+    scale = np.cumprod(np.concatenate([[1.0], np.full(7, 1.2)])).astype(np.float32)
+    Tc = np.eye(4)
+    Tc[:3, :3] = _rot(0.01, -0.015, 0.005)
+    Tc[:3, 3] = [0.02, -0.01, -moved]
+    Rwc, twc = Tc[:3, :3].T, -Tc[:3, :3].T @ Tc[:3, 3]
+    P = dict(u=[], v=[], z=[], lvl=[], desc=[], ang=[], vc=[])      # map points (in pixels of the current frame)
+    K = dict(x=[], y=[], oct=[], desc=[], ang=[], mono=[], occ=[])
+    if hist_only:
+        n, dup_groups, chains, ratio_chains, ties = 0, 0, (), (), 0
+
+    def point(u, v, z, lvl, d, a, vc=0.9995):
+        P["u"].append(u); P["v"].append(v); P["z"].append(z); P["lvl"].append(lvl); P["desc"].append(d); P["ang"].append(a); P["vc"].append(vc)
+
+    def kp(x, y, o, d, a, occ=0, mono=None):
+        K["x"].append(x); K["y"].append(y); K["oct"].append(o); K["desc"].append(d); K["ang"].append(a % 360.0)
+        K["mono"].append(rng.random() < mono_frac if mono is None else mono); K["occ"].append(occ)
+
+    def spot(margin=40.0):
+        return rng.uniform(margin, 640 - margin), rng.uniform(margin, 480 - margin)
+
+    def rot_bg():
+        return 348.0 + rng.uniform(-4.0, 4.0)
+
+    for i in range(n):
+        u, v = spot(10.0)
+        z, lvl, d, a = rng.uniform(2.0, 6.0), int(rng.integers(0, 8)), rng.integers(0, 256, 32, dtype=np.uint8), rng.uniform(0, 360)
+        point(u, v, z, lvl, d, a, 0.9995 if rng.random() < 0.5 else 0.97)
+        kp(u + rng.normal(0, 1.0) * scale[lvl], v + rng.normal(0, 1.0) * scale[lvl], int(np.clip(lvl - rng.integers(0, 2), 0, 7)),
+           _flip_exact(d, int(rng.integers(5, 25)), rng), a - rot_bg(), occ=int(rng.random() < occupied_frac))
+    for i in range(n // 10):
+        x, y = spot(0.0)
+        kp(x, y, int(rng.integers(0, 8)), rng.integers(0, 256, 32, dtype=np.uint8), rng.uniform(0, 360))
+    for g in range(dup_groups):
+        u, v = spot()
+        z, L, d0, a = rng.uniform(2.0, 6.0), int(rng.integers(1, 7)), rng.integers(0, 256, 32, dtype=np.uint8), rng.uniform(0, 360)
+        size = int(rng.integers(2, 5))
+        flips = np.sort(rng.integers(0, 4, size))
+        if g % 2:
+            flips = flips[::-1]
+        for f in flips:
+            point(u + rng.uniform(-0.3, 0.3), v + rng.uniform(-0.3, 0.3), z * (1 + rng.uniform(-2e-4, 2e-4)), L, _flip_exact(d0, int(f), rng), a)
+        x, y, r = u + rng.uniform(-0.5, 0.5), v + rng.uniform(-0.5, 0.5), rot_bg()
+        mono = bool(rng.random() < mono_frac)
+        kp(x, y, L, _flip_exact(d0, 12, rng), a - r, occ=int(rng.random() < prior_frac), mono=mono)
+        kp(x, y, L - 1 if g % 3 else L, _flip_exact(d0, 12 + int(rng.choice([0, 1, 2, 3, 5])), rng), a - r, mono=mono)
+    for length, (near, far) in [(c, (20, 30)) for c in chains] + [(c, (40, 48)) for c in ratio_chains]:
+        z, a = rng.uniform(2.5, 5.0), rng.uniform(0, 360)
+        u0, v0 = rng.uniform(20, max(21.0, 620 - length * chain_step)), rng.uniform(30, 450)
+        d = rng.integers(0, 256, 32, dtype=np.uint8)
+        prev = None
+        for j in range(length):
+            if prev is not None:
+                d = _flip_exact(prev, near, rng)
+            u = u0 + j * chain_step
+            point(u, v0, z, chain_level, d, a)
+            prev = _flip_exact(d, far, rng)
+            kp(u + 0.2, v0 + 0.1, chain_level, prev, a - rot_bg(), mono=True)
+    for d1, d2, same in TIE_CASES * ties:
+        u, v = spot()
+        z, L, d, a = rng.uniform(2.0, 6.0), int(rng.integers(1, 7)), rng.integers(0, 256, 32, dtype=np.uint8), rng.uniform(0, 360)
+        point(u, v, z, L, d, a)
+        point(u + 0.2, v - 0.2, z, L, d, a)
+        r = rot_bg()
+        for dd, o in ((d1, L), (d2, L if same else L - 1)):
+            kp(u + rng.uniform(-0.4, 0.4), v + rng.uniform(-0.4, 0.4), o, _flip_exact(d, dd, rng), a - r, mono=True)
+    for b, cnt in sorted((hist or {}).items()):
+        for c in range(cnt):
+            u, v = spot(10.0)
+            L, d, a = int(rng.integers(0, 4)), rng.integers(0, 256, 32, dtype=np.uint8), float(rng.integers(100, 200))
+            if c % 3 == 0:       # half-way between bins b - 1 and b (integer angles: exact in float32; the product with the factor rounds away from zero to b)
+                r = (b - 0.5) * 12.0 + (0.0, 1e-3)[(c // 3) % 2]
+            else:
+                r = b * 12.0 + rng.uniform(-4.0, 4.0)
+            point(u, v, rng.uniform(2.0, 6.0), L, d, a)
+            kp(u + rng.uniform(-0.5, 0.5), v + rng.uniform(-0.5, 0.5), L, _flip_exact(d, 15, rng), float(np.float32(a)) - (r % 360.0), mono=True)
+    M, N = len(P["u"]), len(K["x"])
+    u, v, z = np.array(P["u"]), np.array(P["v"]), np.array(P["z"])
+    Xc = np.stack([(u - CX) * z / FX, (v - CY) * z / FY, z], 1)
+    Xw = Xc @ Rwc.T + twc
+    lvl = np.array(P["lvl"], np.int32)
+    desc = np.array(P["desc"], np.uint8).reshape(M, 32)
+    ang = np.array(P["ang"], np.float32)
+    vc = np.array(P["vc"], np.float32)
+    if extra_points:
+        Xe = rng.uniform([-8, -6, -2], [8, 6, 10], (extra_points, 3))
+        Xw = np.concatenate([Xw, Xe])
+        lvl = np.concatenate([lvl, rng.integers(0, 8, extra_points).astype(np.int32)])
+        desc = np.concatenate([desc, rng.integers(0, 256, (extra_points, 32), dtype=np.uint8)])
+        ang = np.concatenate([ang, rng.uniform(0, 360, extra_points).astype(np.float32)])
+        vc = np.concatenate([vc, np.full(extra_points, 0.97, np.float32)])
+        M += extra_points
+    Xc = Xw @ Tc[:3, :3].T + Tc[:3, 3]
+    pu = FX * Xc[:, 0] / Xc[:, 2] + CX
+    pv = FY * Xc[:, 1] / Xc[:, 2] + CY
+    perm = rng.permutation(N)
+    kx, ky = np.array(K["x"]), np.array(K["y"])
+    kdesc = np.array(K["desc"], np.uint8).reshape(N, 32)
+    # stereo: the right coordinate of the landmark's depth where a keypoint has one (the depth of the nearest planted point), none where mono
+    zk = np.full(N, 4.0)
+    if M:
+        near = np.argmin((kx[:, None] - pu[None, :]) ** 2 + (ky[:, None] - pv[None, :]) ** 2, axis=1)
+        zk = np.maximum(Xc[near, 2], 0.5)
+    ur = np.where(np.array(K["mono"], bool), -1.0, np.maximum(kx - BF / zk, 0.5))
+    cur = dict(kp_x=kx[perm].astype(np.float32), kp_y=ky[perm].astype(np.float32), kp_octave=np.array(K["oct"], np.int32)[perm],
+               kp_angle=np.array(K["ang"], np.float32)[perm], u_right=ur[perm].astype(np.float32), descriptors=np.ascontiguousarray(kdesc[perm]),
+               occupied=np.array(K["occ"], np.uint8)[perm], min_x=np.float32(0), min_y=np.float32(0), max_x=np.float32(640), max_y=np.float32(480),
+               scale_factors=scale, Tcw=Tc.astype(np.float32), fx=np.float32(FX), fy=np.float32(FY), cx=np.float32(CX), cy=np.float32(CY),
+               mbf=np.float32(BF), mb=np.float32(BF / FX))
+    last = dict(Tcw=np.eye(4, dtype=np.float32), valid=np.ones(M, np.uint8), Xw=Xw.astype(np.float32), descriptors=np.ascontiguousarray(desc), octave=lvl,
+                angle=ang)
+    mps = dict(proj_x=pu.astype(np.float32), proj_y=pv.astype(np.float32), proj_xr=(pu - BF / Xc[:, 2]).astype(np.float32), view_cos=vc, level=lvl,
+               descriptors=np.ascontiguousarray(desc), skip=np.zeros(M, np.uint8))
+    return cur, last, mps
+
+
+def synth_search_scene_contended(n=800, seed=8500, dup_points=0.2, dup_keypoints=0.25, **kw):
+    """synth_search_scene (same arguments, same dict) with the contention of real keyframes planted on top:
+      - a fraction `dup_points` of the map points is created again 1-3 times (the landmark before Fuse merges it): the same position to 1 mm,
+        the same descriptor up to 0-3 bits, appended behind the originals -- the searches that walk map points (Fuse, the Sim3 / keyframe
+        projections) see two or more queries for one keypoint
+      - in each keyframe a fraction `dup_keypoints` of the keypoints that observe a point is detected once more at the same pixel one octave up,
+        with the descriptor 0, 1, 2, 3 or 5 bits away (0: an exact tie), in the same vocabulary node; it observes a duplicate of the point where
+        there is one, nothing otherwise -- the searches that walk keypoints (SearchByBoW, triangulation, initialisation) see two candidates at
+        (nearly) one distance and two queries for one candidate."""
+    sc = synth_search_scene(n=n, seed=seed, **kw)
+    rng = np.random.default_rng(seed + 77)
+    P = sc["points"]
+    src = rng.choice(n, int(dup_points * n), replace=False)
+    copies = {}
+    rows = []
+    for s in src:
+        for _ in range(int(rng.integers(1, 4))):
+            copies.setdefault(int(s), []).append(n + len(rows))
+            rows.append(int(s))
+    rows = np.array(rows, np.int64)
+    newP = {}
+    for k, v in P.items():
+        add = v[rows].copy()
+        if k == "Xw":
+            add = (add * (1 + rng.uniform(-2e-4, 2e-4, add.shape))).astype(v.dtype)
+        elif k == "descriptors":
+            add = np.stack([_flip_exact(d, int(rng.integers(0, 4)), rng) for d in add]) if len(add) else add
+        elif k == "active":
+            add = np.ones_like(add)
+        newP[k] = np.ascontiguousarray(np.concatenate([v, add]))
+    sc["points"] = newP
+    for side in ("1", "2"):
+        K, mp, fv = sc["K" + side], sc["mp" + side], sc["fv" + side]
+        N = len(K["kp_x"])
+        node = np.empty(N, np.int64)
+        for j, nid in enumerate(fv["node_id"]):
+            node[fv["index"][fv["node_start"][j]:fv["node_start"][j + 1]]] = nid
+        cand = np.nonzero(mp >= 0)[0]
+        pick = np.sort(rng.choice(cand, int(dup_keypoints * len(cand)), replace=False))
+        nlev = len(K["scale_factors"])
+        K2 = dict(K)
+        K2["kp_x"] = np.concatenate([K["kp_x"], K["kp_x"][pick]])
+        K2["kp_y"] = np.concatenate([K["kp_y"], K["kp_y"][pick]])
+        K2["kp_octave"] = np.concatenate([K["kp_octave"], np.minimum(K["kp_octave"][pick] + 1, nlev - 1)]).astype(np.int32)
+        K2["kp_angle"] = np.concatenate([K["kp_angle"], K["kp_angle"][pick]])
+        K2["u_right"] = np.concatenate([K["u_right"], K["u_right"][pick]])
+        dd = np.stack([_flip_exact(K["descriptors"][k], int(rng.choice([0, 1, 2, 3, 5])), rng) for k in pick])
+        K2["descriptors"] = np.ascontiguousarray(np.concatenate([K["descriptors"], dd]))
+        mpn = np.array([copies[int(mp[k])][0] if int(mp[k]) in copies else -1 for k in pick], np.int32)
+        sc["mp" + side] = np.concatenate([mp, mpn]).astype(np.int32)
+        node = np.concatenate([node, node[pick]])
+        ids = np.unique(node)
+        start, index = [0], []
+        for nid in ids:
+            index.extend(np.nonzero(node == nid)[0].tolist())
+            start.append(len(index))
+        sc["fv" + side] = dict(node_id=ids.astype(np.uint32), node_start=np.asarray(start, np.int32), index=np.asarray(index, np.uint32))
+        sc["K" + side] = K2
+    return sc

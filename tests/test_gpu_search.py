@@ -18,9 +18,13 @@ def both(request, oracle):
     return (search.product() if request.param == "host arrays" else search.product_handles()), oracle.search_binding()
 
 
-@pytest.fixture(scope="module", params=[dict(), dict(n=1200, seed=8001, flip=0.09, mono_frac=0.6), dict(n=300, seed=8002, clutter=0.5, n_nodes=12)])
+@pytest.fixture(scope="module", params=[dict(), dict(n=1200, seed=8001, flip=0.09, mono_frac=0.6), dict(n=300, seed=8002, clutter=0.5, n_nodes=12),
+                                        dict(contended=True, n=800, seed=8500), dict(contended=True, n=600, seed=8501, n_nodes=9, dup_points=0.4, dup_keypoints=0.4)])
 def scene(request):
-    return synth.synth_search_scene(**request.param)
+    """The last two: landmarks created twice and corners detected at two octaves (synth.synth_search_scene_contended) -- earlier claims decide later matches;
+    nine vocabulary nodes put ~80 features in a node (the per-lane taken mask beyond its first word)."""
+    kw = dict(request.param)
+    return (synth.synth_search_scene_contended if kw.pop("contended", False) else synth.synth_search_scene)(**kw)
 
 
 def _same(a, b):

@@ -110,7 +110,8 @@ def _chain(calls, cur, kps, desc, depth, pts, prior, th, nnratio, prior_Xw=None,
     projected = active.copy()
     if prior is not None:
         projected[kp_mp[(kp_mp >= 0) & (occupied == 1)]] = False
-    res = dict(n_matches=nm, kp_map_point=kp_mp, u_right=ur, depth=dz, n_edges=len(ks), in_view=fo["in_view"].astype(bool) & active, projected=projected)
+    res = dict(n_matches=nm, kp_map_point=kp_mp, u_right=ur, depth=dz, n_edges=len(ks), in_view=fo["in_view"].astype(bool) & active, projected=projected,
+               search_args=(frame, mps))
     Xe = np.zeros((len(ks), 3), np.float32)
     inmap = kp_mp[ks] >= 0
     Xe[inmap] = pts["Xw"][kp_mp[ks][inmap]]
@@ -463,10 +464,10 @@ def test_motion_model_stage_rejects_bad_input():
     assert E.load().eao_abi_version() == 6
 
 
-def _bow_case(seed, n, n_nodes, flip=0.05, clutter=0.15, mono=False):
-    """A reference keyframe (K1 of synth_search_scene: map points, descriptors, angles, feature vector) and a current frame (K2 as the extractor would leave
-    it + a depth image that gives every keypoint the depth of the point it observes, 0 where the scene says monocular)."""
-    sc = synth.synth_search_scene(n=n, seed=seed, flip=flip, clutter=clutter, n_nodes=n_nodes)
+def _bow_case(seed, n, n_nodes, flip=0.05, clutter=0.15, mono=False, gen=None):
+    """A reference keyframe (K1 of synth_search_scene, or of `gen` with its arguments: map points, descriptors, angles, feature vector) and a current frame (K2 as the
+    extractor would leave it + a depth image that gives every keypoint the depth of the point it observes, 0 where the scene says monocular)."""
+    sc = (gen or synth.synth_search_scene)(n=n, seed=seed, flip=flip, clutter=clutter, n_nodes=n_nodes)
     K1, K2 = sc["K1"], sc["K2"]
     N = len(K2["kp_x"])
     kps = np.zeros(N, KP)

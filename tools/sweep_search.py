@@ -1,7 +1,8 @@
 """Randomised bit-exactness sweep of the guided searches (SearchByProjection sim3 / keyframe / frame-to-frame / points, SearchByBoW,
 SearchForTriangulation, SearchForInitialization, Fuse, SearchBySim3) against the CPU oracle over scene sizes, descriptor noise,
 clutter, monocular fractions, vocabulary sizes, radii and ratio thresholds.  Not part of the test suite: run by hand on a GPU box.
-    python tools/sweep_search.py [seed] [scenes] [handles]      (handles: the same calls through keyframe handles, eao_kf_*, round 5)"""
+    python tools/sweep_search.py [seed] [scenes] [handles|arrays] [contended]      (handles: the same calls through keyframe handles, eao_kf_*, round 5;
+    contended: the scenes from synth.synth_search_scene_contended -- landmarks created twice, corners detected at two octaves)"""
 import sys; sys.path.insert(0, '.'); sys.path.insert(0, 'tests')
 import numpy as np, torch  # noqa: F401
 import eao_fusion_amd as E
@@ -24,7 +25,7 @@ for it in range(N):
               flip=float(rng.choice([0.0, 0.03, 0.08, 0.15])), clutter=float(rng.choice([0.0, 0.15, 0.5])), mono_frac=float(rng.choice([0.0, 0.3, 1.0])),
               n_nodes=int(rng.choice([1, 12, 60, 400])))
     try:
-        sc = synth.synth_search_scene(**kw)
+        sc = (synth.synth_search_scene_contended if len(sys.argv) > 4 and sys.argv[4] == "contended" else synth.synth_search_scene)(**kw)
         P = sc["points"]
         kf = dict(sc["K2"]); kf["occupied"] = (rng.random(len(kf["kp_x"])) < rng.choice([0.0, 0.1, 0.5])).astype(np.uint8)
         th = int(rng.choice([3, 4, 10, 15]))

@@ -3,7 +3,9 @@
 points, search radii, ratio thresholds, prior matches (on active, bad and foreign points), monocular fractions, and (round 5) a third of the frames through a camera
 with random lens distortion (Frame::UndistortKeyPoints on the chain).  Integer tables bit for
 bit, the pose within 1e-4 of the update.  Not part of the test suite: run by hand on a GPU box.
-    python tools/sweep_track.py [seed] [cases]"""
+    python tools/sweep_track.py [seed] [cases] [contended]
+(contended: the frames come from synth.synth_tracking_contended -- duplicated landmarks, exact ties, chains of dependent points, prior matches on
+contested keypoints -- with random sizes of each.)"""
 import sys; sys.path.insert(0, '.'); sys.path.insert(0, 'tests')
 import numpy as np, torch
 import eao_fusion_amd as E
@@ -11,12 +13,21 @@ from oracle import oracle as O
 import test_gpu_track as T
 rng = np.random.default_rng(int(sys.argv[1]) if len(sys.argv) > 1 else 1)
 N = int(sys.argv[2]) if len(sys.argv) > 2 else 40
+CONTENDED = len(sys.argv) > 3 and sys.argv[3] == "contended"
 bad = 0
 for it in range(N):
     kw = dict(seed=int(rng.integers(0, 1 << 30)), n=int(rng.choice([rng.integers(60, 300), rng.integers(300, 1100), rng.integers(1100, 1800)])),
               prior_frac=float(rng.choice([0.0, 0.0, 0.1, 0.4])), mono_frac=float(rng.choice([0.0, 0.25, 1.0])))
     th, nnratio = float(rng.choice([1.0, 3.0, 5.0, 8.0])), float(rng.choice([0.6, 0.8, 0.9]))
-    cur, kps, desc, depth, pts, prior = T._scene(**kw)
+    if CONTENDED:
+        import test_gpu_contended as TC
+        gk = dict(seed=kw["seed"], n=int(rng.integers(0, 800)), dup_groups=int(rng.integers(0, 80)), chains=tuple(int(c) for c in rng.integers(10, 220, rng.integers(0, 3))),
+                  ratio_chains=tuple(int(c) for c in rng.integers(10, 150, rng.integers(0, 3))), ties=int(rng.integers(0, 3)), prior_frac=float(rng.choice([0.0, 0.1, 0.4])),
+                  mono_frac=kw["mono_frac"])
+        kw = gk
+        cur, _, kps, desc, depth, pts, prior = TC._scene(gk, bool(rng.random() < 0.7))
+    else:
+        cur, kps, desc, depth, pts, prior = T._scene(**kw)
     M = len(pts["Xw"])
     extra = int(rng.choice([0, 0, 3000, 9000, 15000]))
     extra = min(extra, 16384 - M)
