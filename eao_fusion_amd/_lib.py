@@ -71,6 +71,19 @@ class BAResult(C.Structure):
                 ("iters", C.c_int32 * 2), ("aborted", C.c_int32), ("chi2", C.c_double * 2)]
 
 
+class Sim3Problem(C.Structure):   # eao_sim3_problem
+    _fields_ = [("n", C.c_int32), ("T1w", C.c_void_p), ("T2w", C.c_void_p), ("Xw1", C.c_void_p), ("Xw2", C.c_void_p),
+                ("obs1", C.c_void_p), ("obs2", C.c_void_p), ("inv_sigma2_1", C.c_void_p), ("inv_sigma2_2", C.c_void_p),
+                ("fx1", C.c_float), ("fy1", C.c_float), ("cx1", C.c_float), ("cy1", C.c_float),
+                ("fx2", C.c_float), ("fy2", C.c_float), ("cx2", C.c_float), ("cy2", C.c_float),
+                ("q", C.c_double * 4), ("t", C.c_double * 3), ("s", C.c_double), ("th2", C.c_float), ("fix_scale", C.c_int32)]
+
+
+class Sim3Result(C.Structure):   # eao_sim3_result
+    _fields_ = [("q", C.c_double * 4), ("t", C.c_double * 3), ("s", C.c_double), ("removed", C.c_void_p),
+                ("n_inliers", C.c_int32), ("lm_iterations", C.c_int32 * 2), ("early_exit", C.c_int32)]
+
+
 # every symbol include/eao_fusion.h declares: (restype, argtypes)
 _P = C.c_void_p
 _I = C.c_int32
@@ -128,6 +141,8 @@ SYMBOLS = {
     "eao_bundle_adjustment_planes": (_I, [C.POINTER(BAProblem), C.POINTER(BAPlanes), _I, _P, C.POINTER(BAResult), _P]),
     "eao_last_lm_trace": (_I, [_P, _P, _P, _I, C.POINTER(_I)]),
     "eao_last_lm_timing": (_I, [C.POINTER(C.c_float), C.POINTER(_I)]),
+    "eao_optimize_sim3": (_I, [C.POINTER(Sim3Problem), C.POINTER(Sim3Result)]),
+    "eao_optimize_sim3_batch": (_I, [C.POINTER(Sim3Problem), _I, C.POINTER(Sim3Result)]),
     "eao_bundle_adjustment_plan": (_I, [_I, _I, _P, _P, _I, _P, _P, _P, _I, _P, _I, _P, _I, _P, _I, _P, _I, _P, _I]),
 }
 

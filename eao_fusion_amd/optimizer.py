@@ -181,3 +181,66 @@ class Optimizer:
         (fixed[i] = 1 for the keyframe with mnId == 0); optional planes (m,4) f32 + pedge_plane / pedge_cam (Ep,) i32 + pedge_obs
         (Ep,4) f32: the MapPlane vertices and EdgePlane edges of :203-252 (eao_bundle_adjustment_planes)."""
         return Optimizer.LocalBundleAdjustment(prob, stop, (int(nIterations), 0), gba=bool(bRobust))
+
+
+# ---------------------------------------------------------------------- Optimizer::OptimizeSim3 (src/Optimizer.cc:1437-1632)
+def _pack_sim3(prob):
+    """eao_sim3_problem of one problem dict (the arrays it points into come back with it, to keep them alive).
+    prob: T1w / T2w (4,4) f32, Xw1 / Xw2 (n,3) f32, obs1 / obs2 (n,2) f32, inv_sigma2_1 / inv_sigma2_2 (n,) f32,
+    K1 / K2 (fx, fy, cx, cy), q (x, y, z, w) / t (3,) / s of the initial S12 in float64, th2, fix_scale."""
+    keep = dict(T1w=np.ascontiguousarray(prob["T1w"], np.float32), T2w=np.ascontiguousarray(prob["T2w"], np.float32),
+                Xw1=np.ascontiguousarray(prob["Xw1"], np.float32).reshape(-1, 3), Xw2=np.ascontiguousarray(prob["Xw2"], np.float32).reshape(-1, 3),
+                obs1=np.ascontiguousarray(prob["obs1"], np.float32).reshape(-1, 2), obs2=np.ascontiguousarray(prob["obs2"], np.float32).reshape(-1, 2),
+                i1=np.ascontiguousarray(prob["inv_sigma2_1"], np.float32), i2=np.ascontiguousarray(prob["inv_sigma2_2"], np.float32))
+    n = len(keep["Xw1"])
+    assert len(keep["Xw2"]) == n and len(keep["obs1"]) == n and len(keep["obs2"]) == n and len(keep["i1"]) == n and len(keep["i2"]) == n
+    keep["removed"] = np.zeros(max(n, 1), np.uint8)
+    K1, K2 = [float(v) for v in prob["K1"]], [float(v) for v in prob["K2"]]
+    P = _lib.Sim3Problem(n, _lib.ptr(keep["T1w"]), _lib.ptr(keep["T2w"]), _lib.ptr(keep["Xw1"]), _lib.ptr(keep["Xw2"]),
+                         _lib.ptr(keep["obs1"]), _lib.ptr(keep["obs2"]), _lib.ptr(keep["i1"]), _lib.ptr(keep["i2"]), *K1, *K2,
+                         (C.c_double * 4)(*[float(v) for v in prob["q"]]), (C.c_double * 3)(*[float(v) for v in prob["t"]]), float(prob["s"]),
+                         float(prob["th2"]), 1 if prob["fix_scale"] else 0)
+    return P, keep, n
+
+
+def _sim3_out(R, keep, n):
+    return dict(q=np.array(R.q[:], np.float64), t=np.array(R.t[:], np.float64), s=float(R.s), removed=keep["removed"][:n].copy(),
+                n_inliers=int(R.n_inliers), iters=np.array(R.lm_iterations[:], np.int32), early_exit=bool(R.early_exit))
+
+
+def optimize_sim3(prob):
+    """Optimizer::OptimizeSim3 of one flattened problem (eao_optimize_sim3).  Returns dict(q, t, s, removed, n_inliers, iters,
+    early_exit, timing): q / t / s as the vertex holds them (the initial S12 on early exit), removed[i] = 1 where vpMatches1 is nulled."""
+    P, keep, n = _pack_sim3(prob)
+    R = _lib.Sim3Result()
+    R.removed = _lib.ptr(keep["removed"])
+    _lib.check(_lib.load().eao_optimize_sim3(C.byref(P), C.byref(R)))
+    out = _sim3_out(R, keep, n)
+    out["timing"] = _timing()
+    return out
+
+
+def pack_sim3_batch(probs):
+    """The argument arrays of eao_optimize_sim3_batch (kept alive by the returned object)."""
+    nb = len(probs)
+    Ps, Rs = (_lib.Sim3Problem * max(nb, 1))(), (_lib.Sim3Result * max(nb, 1))()
+    keeps = []
+    for b, prob in enumerate(probs):
+        P, keep, n = _pack_sim3(prob)
+        Ps[b] = P
+        Rs[b].removed = _lib.ptr(keep["removed"])
+        keeps.append((keep, n))
+    return dict(P=Ps, R=Rs, n=nb, keeps=keeps)
+
+
+def optimize_sim3_batch(probs, packed=None):
+    """OptimizeSim3 for a list of problems in one launch (eao_optimize_sim3_batch); each entry as optimize_sim3 returns it."""
+    pk = packed or pack_sim3_batch(probs)
+    _lib.check(_lib.load().eao_optimize_sim3_batch(pk["P"], pk["n"], pk["R"]))
+    tm = _timing()
+    outs = []
+    for b, (keep, n) in enumerate(pk["keeps"]):
+        o = _sim3_out(pk["R"][b], keep, n)
+        o["timing"] = tm
+        outs.append(o)
+    return outs

@@ -692,6 +692,48 @@ eao_status eao_tracker_track_reference_keyframe(eao_tracker* h, const eao_keypoi
                                                 const eao_feature_vector* fv_kf, const eao_feature_vector* fv_cur, float nnratio, int32_t check_orientation,
                                                 int32_t discard_outliers, eao_track_result* out, void* stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * Optimizer::OptimizeSim3(pKF1, pKF2, vpMatches1, g2oS12, th2, bFixScale) -- reference include/Optimizer.h,
+ * src/Optimizer.cc:1437-1632 (g2o: types/types_seven_dof_expmap.h:48-170, types/sim3.h:70-141, core/base_binary_edge.hpp:147-196,
+ * core/optimization_algorithm_levenberg.cpp:61-189, solvers/linear_solver_dense.h:104-112)
+ * ------------------------------------------------------------------------------------------------ */
+typedef struct {
+    int32_t n;                  /* correspondences that got an edge pair (src/Optimizer.cc:1502-1561: vpMatches1[i] != NULL, pMP1 = GetMapPointMatches()[i]
+                                 * != NULL, neither isBad(), pMP2->GetIndexInKeyFrame(pKF2) >= 0), in index order */
+    const float* T1w;           /* 16 floats, row-major 4x4: pKF1 pose (GetRotation() = upper-left 3x3, GetTranslation() = last column) */
+    const float* T2w;           /* 16 floats: pKF2 */
+    const float* Xw1;           /* n*3: pMP1->GetWorldPos() */
+    const float* Xw2;           /* n*3: pMP2->GetWorldPos() */
+    const float* obs1;          /* n*2: pKF1->mvKeysUn[i].pt.x, .pt.y */
+    const float* obs2;          /* n*2: pKF2->mvKeysUn[i2].pt.x, .pt.y */
+    const float* inv_sigma2_1;  /* n: pKF1->mvInvLevelSigma2[mvKeysUn[i].octave] */
+    const float* inv_sigma2_2;  /* n: pKF2->mvInvLevelSigma2[mvKeysUn[i2].octave] */
+    float fx1, fy1, cx1, cy1;   /* pKF1->mK */
+    float fx2, fy2, cx2, cy2;   /* pKF2->mK */
+    double q[4];                /* the initial g2oS12: rotation coefficients in Eigen's order x, y, z, w */
+    double t[3];                /*   translation */
+    double s;                   /*   scale */
+    float th2;                  /* chi2 gate of both inlier passes; the Huber width is sqrtf(th2) (src/Optimizer.cc:1495) */
+    int32_t fix_scale;          /* bFixScale: VertexSim3Expmap::_fix_scale (the update's 7th component is zeroed) */
+} eao_sim3_problem;
+
+typedef struct {
+    double q[4], t[3], s;       /* the optimised g2oS12 as the vertex holds it (x, y, z, w; t; s); the initial one on early exit */
+    uint8_t* removed;           /* n flags (caller-allocated): 1 where the reference sets vpMatches1[i] = NULL, in either inlier pass */
+    int32_t n_inliers;          /* return value of OptimizeSim3 (0 on early exit) */
+    int32_t lm_iterations[2];   /* outer LM iterations of the two optimize() calls (the second is 0 on early exit) */
+    int32_t early_exit;         /* 1: nCorrespondences - nBad < 10 after the first pass (src/Optimizer.cc:1591-1592), g2oS12 not written back */
+} eao_sim3_result;
+
+/* Camera-frame points R1w * Xw1 + t1w (src/Optimizer.cc:1525-1526, float cv::Mat): the product accumulates in double and rounds
+ * once to float, the translation is added in float, then the result is promoted to double.  One workgroup runs both optimize()
+ * calls, the inlier pass between them and the final one. */
+eao_status eao_optimize_sim3(const eao_sim3_problem* p, eao_sim3_result* r);
+
+/* `n` independent OptimizeSim3 problems in one launch (one workgroup per problem): offline replays, several maps or
+ * candidates at once.  results[i] is bit-identical to what eao_optimize_sim3(&problems[i], &results[i]) returns. */
+eao_status eao_optimize_sim3_batch(const eao_sim3_problem* problems, int32_t n, eao_sim3_result* results);
+
 /* The value of EAO_ABI_VERSION the library was built with.  Bumped whenever an entry point's parameter list or a struct's layout changes (round 3
  * changed eao_tracker_track_local_map and eao_track_result in place); a caller compiled against another version must not call into the library.
  * Result structs are zero-initialised by the caller (`eao_track_result R = {0};`) before their array pointers are set: a pointer member the
