@@ -812,8 +812,6 @@ void plan_for(const PlanGraph& G, const std::vector<int>& prA, const std::vector
     std::vector<int> gorder;
     for (int step = 1; step <= (int)cut.size(); step *= 2)
         for (int gq = step; gq <= (int)cut.size(); gq += 2 * step) gorder.push_back(gq);
-    static const bool envSepChain = getenv("EAO_BA_ND_SEP_CHAIN") != nullptr;      // (A/B: the separators in the order of their cuts)
-    if (envSepChain) { gorder.clear(); for (int gq = 1; gq <= (int)cut.size(); gq++) gorder.push_back(gq); }
     for (int gq : gorder) {
         row = up64(row);
         for (int p = 0; p < nFa; p++) { const int v = line[p]; if (sep[v] == gq) { pl.rowOf[v] = row; row += 6; } }

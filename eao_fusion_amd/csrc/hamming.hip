@@ -525,7 +525,7 @@ eao_status eao_hamming_matrix_device(const uint8_t* d_A, int32_t na, const uint8
     if ((nb & 7) == 0 && ((uintptr_t)d_D & 15) == 0 && envMfma && (blocks >= 64 || envMfma > 1)) {
         hipLaunchKernelGGL(k_hamming_matrix_mfma, dim3(eao::cdiv(nb, kMB), eao::cdiv(na, kMB), pairs), dim3(256), 0, (hipStream_t)stream, (const uint4*)d_A, na,
                            (const uint4*)d_B, nb, d_D);
-    } else if ((nb & 7) == 0 && ((uintptr_t)d_D & 15) == 0 && !getenv("EAO_HAMMING_NARROW")) {
+    } else if ((nb & 7) == 0 && ((uintptr_t)d_D & 15) == 0) {
         dim3 grid8(eao::cdiv(nb, 1024), eao::cdiv(na, kRowsPerBlock8), pairs);
         hipLaunchKernelGGL(k_hamming_matrix8, grid8, dim3(128), 0, (hipStream_t)stream, (const uint4*)d_A, na, (const uint4*)d_B, nb, d_D);
     } else {
@@ -547,7 +547,7 @@ eao_status eao_hamming_best2_device(const uint8_t* d_A, int32_t na, const uint8_
     if (!d_mask && envMfma && ((long long)eao::cdiv(na, kMB) * pairs >= 64 || envMfma > 1)) {      // matrix cores: enough row blocks to spread over the chip
         Best2Src S{(const uint4*)d_A, (const uint4*)d_B, na, nb, nullptr, nullptr, 0, 0};
         hipLaunchKernelGGL(k_hamming_best2_mfma<false>, dim3(eao::cdiv(na, kMB), pairs), dim3(256), 0, (hipStream_t)stream, S, d_out);
-    } else if (!d_mask && na >= 256 && !getenv("EAO_HAMMING_NARROW"))     // (few rows: one row per wave fills the chip better)
+    } else if (!d_mask && na >= 256)     // (few rows: one row per wave fills the chip better)
         hipLaunchKernelGGL(k_hamming_best2_rows, dim3(eao::cdiv(na, 4 * kB2Rows), pairs), dim3(256), 0, (hipStream_t)stream, (const uint4*)d_A, na,
                            (const uint4*)d_B, nb, d_out);
     else

@@ -238,7 +238,7 @@ struct FinishArgs {
     int* nm;         // mapped host: nProb
     // the call's LAST finish launch publishes a done word the host polls (as the tracker's chain does, csrc/lm.hip pose_publish): every workgroup fences its
     // stores to host memory at system scope, reads one of its own words back over PCIe (a read pushes posted writes) and takes a ticket; the last one stores
-    // the word.  done == nullptr: the host synchronises the stream instead.
+    // the word.
     int* ticket; int ticketLast; int* done; int doneSeq;
     const float* ang2[kMaxProb];
 };
@@ -325,14 +325,12 @@ __global__ __launch_bounds__(256) void k_kf_finish(FinishArgs A) {
     if ((t & 63) == 0 && kept) atomicAdd(&s_nm, kept);
     __syncthreads();
     if (t == 0) A.nm[pb] = s_nm;
-    if (A.done) {
-        __threadfence_system();
-        __syncthreads();
-        if (t == 0) {
-            const int back = __hip_atomic_load(&A.nm[pb], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);      // (cannot pass this workgroup's posted writes)
-            const int tk = atomicAdd(A.ticket, 1);
-            if (tk == A.ticketLast && back == s_nm) __hip_atomic_store(A.done, A.doneSeq, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-        }
+    __threadfence_system();
+    __syncthreads();
+    if (t == 0) {
+        const int back = __hip_atomic_load(&A.nm[pb], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);      // (cannot pass this workgroup's posted writes)
+        const int tk = atomicAdd(A.ticket, 1);
+        if (tk == A.ticketLast && back == s_nm) __hip_atomic_store(A.done, A.doneSeq, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
     }
 }
 
@@ -658,7 +656,6 @@ eao_status run_nodes(int mode, const eao_keyframe* k1, int nProb, const eao_keyf
         c.ticketNext = 0;
         if ((st = c.doneWord.reserve(64))) return st;
     }
-    static const int envPoll = getenv("EAO_KF_POLL") ? atoi(getenv("EAO_KF_POLL")) : 1;      // 0: hipStreamSynchronize (A/B switch)
     if (c.ticketNext > 0x70000000) { EAO_HIP(hipMemsetAsync(c.ticket.p, 0, sizeof(int), c.stream)); c.ticketNext = 0; }
     const int seq = ++c.seq;
     volatile int* doneHost = reinterpret_cast<volatile int*>(c.doneWord.p);
@@ -687,9 +684,9 @@ eao_status run_nodes(int mode, const eao_keyframe* k1, int nProb, const eao_keyf
         B.ang1 = k1->D.ang; B.nProb = np; B.n1 = n1; B.gen = c.gen; B.checkOrientation = checkOrientation; B.match = A.match;
         B.out = (int*)(c.out.d + oTab) + (size_t)p0 * n1; B.nm = (int*)c.out.d + p0;
         const bool lastChunk = p0 + np >= nProb;
-        B.ticket = c.ticket.p; B.done = nullptr; B.doneSeq = seq; B.ticketLast = -1;
-        if (envPoll && lastChunk) { B.done = (int*)c.doneWord.d; B.ticketLast = c.ticketNext + nProb - 1; }      // the last workgroup of the call's LAST launch: every earlier one has taken its ticket
-        else if (envPoll) { B.done = (int*)c.doneWord.d; B.doneSeq = 0; }                                            // (earlier chunks take tickets and confirm their stores; they never see ticketLast)
+        B.ticket = c.ticket.p; B.done = (int*)c.doneWord.d; B.doneSeq = seq; B.ticketLast = -1;
+        if (lastChunk) B.ticketLast = c.ticketNext + nProb - 1;      // the last workgroup of the call's LAST launch: every earlier one has taken its ticket
+        else B.doneSeq = 0;                                          // (earlier chunks take tickets and confirm their stores; they never see ticketLast)
         for (int q = 0; q < np; q++) {
             A.P[q].k2 = (const KfDev*)k2s[p0 + q]->dev;
             if (F12s) { std::memcpy(A.P[q].F, F12s + 9 * (size_t)(p0 + q), 36); A.P[q].ex = exs[p0 + q]; A.P[q].ey = eys[p0 + q]; }
@@ -714,16 +711,14 @@ eao_status run_nodes(int mode, const eao_keyframe* k1, int nProb, const eao_keyf
         eao::set_error("keyframe search launch failed: %s", hipGetErrorString(launchErr));
         return EAO_ERR_NO_DEVICE;
     }
-    if (envPoll) {
-        c.ticketNext += nProb;
-        const auto t0 = std::chrono::steady_clock::now();
-        for (unsigned spins = 0; !(seen = *doneHost == seq); spins++)
-            if ((spins & 1023) == 1023 && std::chrono::steady_clock::now() - t0 > std::chrono::milliseconds(50)) break;
-        std::atomic_thread_fence(std::memory_order_acquire);
-    }
+    c.ticketNext += nProb;
+    const auto t0 = std::chrono::steady_clock::now();
+    for (unsigned spins = 0; !(seen = *doneHost == seq); spins++)
+        if ((spins & 1023) == 1023 && std::chrono::steady_clock::now() - t0 > std::chrono::milliseconds(50)) break;
+    std::atomic_thread_fence(std::memory_order_acquire);
     if (!seen) {
         EAO_HIP(eao::wait_latency(c.stream));
-        if (envPoll) { EAO_HIP(hipMemsetAsync(c.ticket.p, 0, sizeof(int), c.stream)); EAO_HIP(eao::wait_latency(c.stream)); c.ticketNext = 0; }
+        EAO_HIP(hipMemsetAsync(c.ticket.p, 0, sizeof(int), c.stream)); EAO_HIP(eao::wait_latency(c.stream)); c.ticketNext = 0;
     }
     EAO_HIP(hipGetLastError());
     if (c.dbg) {

@@ -846,11 +846,9 @@ __global__ __launch_bounds__(NT, 1024 / NT) void k_ba_schur_pairs_b(const BADev*
 constexpr int kPairG = 7;                       // landmarks per fetch
 constexpr int kPairSlot = 160;                  // LDS bytes per staged block: 144 data + a zero slot for the padding lanes
 constexpr int kPairWaveLds = 3 * kPairG * kPairSlot;      // A blocks, B blocks, u entries (24 bytes each, at the blocks' pitch: one immediate offset per landmark)
+constexpr int kPairOcc = 6;                     // minimum workgroups per CU of the four-wave (batch) variant
 template <int NW>      // waves per pair: 4 in a batch (5 250 workgroups: throughput), 16 for a single window (210 workgroups: latency of the longest pair)
-#ifndef EAO_PAIR_OCC
-#define EAO_PAIR_OCC 6
-#endif
-__global__ __launch_bounds__(64 * NW, NW == 4 ? EAO_PAIR_OCC : 1) void k_ba_schur_pairs_mfma(const BADev* __restrict__ W, int wpar, int first) {
+__global__ __launch_bounds__(64 * NW, NW == 4 ? kPairOcc : 1) void k_ba_schur_pairs_mfma(const BADev* __restrict__ W, int wpar, int first) {
     BA_WIN(P);
     if ((int)bx >= P.nFree * (P.nFree + 1) / 2) return;
     __shared__ double part[NW][64];
@@ -1469,17 +1467,14 @@ eao_status BALaunch::attributes() const {
 }
 int BALaunch::linBlocks() const { return eao::cdiv(std::max(d.nL, 1) * 8, kLinThreads); }
 // the pre-scaled-block linearisation: 1024-thread workgroups in a batch (48.9 us per 25 windows against 51.8 with 512), 512 / 256 for one window -- its 24 landmark
-// workgroups of 1024 leave nine tenths of the chip idle (EAO_BA_LIN_THREADS for A/B runs; profiles/r04_ba_pair_ablation.txt)
+// workgroups of 1024 leave nine tenths of the chip idle (profiles/r04_ba_pair_ablation.txt)
 template <int NT> void BALaunch::lin_launch(int par, int first, int diagOnly) const {
     const int lb = eao::cdiv(std::max(d.nL, 1) * 8, NT);
     hipLaunchKernelGGL((k_ba_linearize<false, NT, true>), dim3(lb + d.nF, 1, gz()), dim3(NT), 0, s, W, wp(par), lb, first, diagOnly);
 }
 void BALaunch::lin_w(int par, int first, int diagOnly) const {
-    static const int envLinT = getenv("EAO_BA_LIN_THREADS") ? atoi(getenv("EAO_BA_LIN_THREADS")) : 0;
-    const int nt = envLinT ? envLinT : (nz > 1 ? 1024 : 512);
-    if (nt == 256) lin_launch<256>(par, first, diagOnly);
-    else if (nt == 512) lin_launch<512>(par, first, diagOnly);
-    else lin_launch<kLinThreads>(par, first, diagOnly);
+    if (nz > 1) lin_launch<kLinThreads>(par, first, diagOnly);
+    else lin_launch<512>(par, first, diagOnly);
 }
 void BALaunch::setup() const {      // device-side part of the set-up (once per window)
     hipLaunchKernelGGL(k_ba_prepare, dim3(eao::cdiv(std::max(std::max(std::max(std::max(std::max(d.bigPath ? 0 : d.nL * d.nF, d.nL * 8), d.nP * 3), d.nC), d.E), d.nPl * 4), 256), 1, gz()), dim3(256), 0, s, W, wp(0));

@@ -397,10 +397,7 @@ __global__ __launch_bounds__(64) void k_fast_cells(const Geom* __restrict__ g, c
     // heavy ones) than the saved re-fetches return.  What does pay is FRAME affinity (below): frame f is served by XCD f % 8
     // only, every XCD walks its frames' cells in table order, so a cache line is fetched into one L2 and the load stays
     // balanced by construction -- 256-frame batch: FAST alone 0.540 -> 0.532 ms, the scheduled step 1.338 -> 1.301 ms (the
-    // resize running beside FAST gets the fabric).  Speed only, never results.  EAO_FAST_AFFINITY=0 switches it off.
-    // (bits 8.. of the last argument: the phase after which a CENSUS run leaves the kernel -- EAO_FAST_STOP_AFTER, tools/prof_fast_census.sh; 0 in every other run)
-    const int stopAfter = frameAffinity >> 8;
-    frameAffinity &= 1;
+    // resize running beside FAST gets the fabric).  Speed only, never results.
     int cell = blockIdx.x, fy = blockIdx.y;
     if constexpr (kFastXcdRun > 0) {
         const int xcd = blockIdx.x & 7, bslot = blockIdx.x >> 3;
@@ -466,7 +463,6 @@ __global__ __launch_bounds__(64) void k_fast_cells(const Geom* __restrict__ g, c
             tile[y * kTileStride + x + ph] = src[(long long)(c.y0 + y) * pitch + c.x0 + x];
         }
     }
-    if (stopAfter == 1) { if (lane == 0) cellcnt[slot] = 0; return; }      // census: launch + staging (an empty cell for the kernels behind)
     const int rw = tw + 2;
     const int scWords = (rw * (th_ + 2) + 3) >> 2;
     // (the geometry fields the loops need, read ONCE: the compiler re-loads g->x after every store it cannot tell apart)
@@ -568,7 +564,6 @@ __global__ __launch_bounds__(64) void k_fast_cells(const Geom* __restrict__ g, c
             }
         }
         __syncthreads();
-        if (stopAfter == 2) { if (lane == 0) cellcnt[slot] = 0; return; }  // census: ... + candidate test
         // ---- 2. arc value of the survivors in one polarity; corners go to the score map.  A survivor whose candidate test allows
         // both polarities and that is no dark corner is APPENDED to the work list with kSecond set and meets the bright
         // evaluation in a later lane of the same loop -- normally one of the lanes the last 64-entry round leaves idle (a
@@ -605,7 +600,6 @@ __global__ __launch_bounds__(64) void k_fast_cells(const Geom* __restrict__ g, c
             k0 = min(k0 + 64, nlist);      // (entries appended by a partial round start right behind it)
         }
         __syncthreads();
-        if (stopAfter == 3) { if (lane == 0) cellcnt[slot] = 0; return; }  // census: ... + arc values
         // ---- 3. NMS + ordered emission (a corner of score 0 is never kept: 0 > max(...) cannot hold, upstream the same)
         int total = 0;
         for (int k0 = 0; k0 < nwork; k0 += 64) {
@@ -1138,9 +1132,14 @@ __global__ __launch_bounds__(256) void k_stereo_match(const Geom* __restrict__ g
 namespace eao {
 namespace orb {
 
-// enqueue the whole pipeline for `batch` frames; level 0 is read from `src` (device memory)
-eao_status enqueue_direct(eao_orb* h, const uint8_t* d_img, int pitch0, long long fs0, int batch, eao_keypoint* d_kps,
-                          uint8_t* d_desc, int cap, int* d_n, hipStream_t st, int lanes) {
+// Enqueue the whole pipeline for `batch` frames on the caller's stream `st`; level 0 is read from `d_img` (device memory).
+// The main chain runs on `st` itself -- no hand-over to a private stream and back, which put two cross-stream event hops (~25 us on
+// PyTorch's bundled HIP 7.0 runtime) between consecutive calls -- and the handle's side stream takes the work that runs beside it.
+// (Measured on MI355X, 64-frame batch: the launch sequence captured into a hipGraph and replayed 0.736 ms against 0.742 ms of direct
+// launches, the batch cut into 2 / 4 concurrent pipelines on stream pairs 0.75 / 0.94 ms -- the kernels are throughput-bound, not
+// latency-bound, so a call is one pipeline of direct launches.)
+eao_status enqueue(eao_orb* h, const uint8_t* d_img, int pitch0, long long fs0, int batch, eao_keypoint* d_kps,
+                   uint8_t* d_desc, int cap, int* d_n, hipStream_t st) {
     const Geom& g = h->geom;
     eao::Range rAll("eao_orb_extract: enqueue");
     ImgSrc s;
@@ -1158,9 +1157,6 @@ eao_status enqueue_direct(eao_orb* h, const uint8_t* d_img, int pitch0, long lon
         h->evUsed += kProfEvents;
         EAO_HIP(hipEventRecord(ev[0], st));
     }
-    // split the batch into up to kLanes contiguous slices; slice i runs pyramid -> {FAST -> quad-tree | blur} ->
-    // orientation + description on its own stream pair.  Profiling events bracket the stages of slice 0.
-    lanes = std::max(1, std::min(std::min(eao_orb::kLanes, batch), lanes));
     // the handle's pyramid / candidate scratch is shared by its calls: a call enqueued on another stream than the previous
     // one waits for it (same stream: already ordered, the wait costs nothing)
     // (no event is recorded at the end of a call for this: an event record between two kernels of a stream costs ~5 us on this
@@ -1168,109 +1164,93 @@ eao_status enqueue_direct(eao_orb* h, const uint8_t* d_img, int pitch0, long lon
     //  change of stream waits for the previous one on the host instead)
     //  (the previous stream may have been DESTROYED by its owner in the meantime -- a garbage-collected
     //  torch.cuda.Stream -- so its handle is never touched again: the rare change of stream drains the device instead)
-    if (h->evLastValid && !h->capturing && h->lastStream != st) {
-        eao_status so = order_behind_last_call(h, st);
-        if (so) return so;
+    eao_status so;
+    if (h->evLastValid && h->lastStream != st) {
+        if ((so = order_behind_last_call(h, st))) return so;
     }
-    if (!h->capturing) h->lastStream = st;
+    h->lastStream = st;
     EAO_HIP(hipEventRecord(h->evStart, st));
-    for (int i = 0; i < lanes; i++) {
-        const int f0 = (int)((long long)batch * i / lanes), f1 = (int)((long long)batch * (i + 1) / lanes), nb = f1 - f0;
-        // One lane (the default): the main chain runs on the CALLER's stream itself -- no hand-over to a private stream and
-        // back, which put two cross-stream event hops (~25 us on PyTorch's bundled HIP 7.0 runtime) between consecutive calls.
-        const bool onCaller = lanes == 1;
-        hipStream_t ms = onCaller ? st : h->laneMain[i], ss = h->laneSide[i];
-
-        const bool pe = prof && i == 0;
-        if (!onCaller) EAO_HIP(hipStreamWaitEvent(ms, h->evStart, 0));
-        // Level 0 IS the input image: its FAST cells (a third of all cells) do not wait for the pyramid.  Outside profiling
-        // runs they start on the side stream at once and overlap the seven resize launches; the side stream then goes on
-        // with the blur as before.  (Profiling runs keep the stages sequential so that each is timed alone.)
-        const int cells0 = g.L[0].nCells;
-        const bool early0 = !prof && g.nlevels > 1 && g.L[0].cellBase == 0 && cells0 < g.totalCells;
-        // frame -> XCD placement of the resize chain and of the blur (round 5; EAO_RESIZE_AFFINITY=0 / EAO_BLUR_AFFINITY=0: plain order)
-        static const int envRAff = getenv("EAO_RESIZE_AFFINITY") ? atoi(getenv("EAO_RESIZE_AFFINITY")) : 1;
-        static const int envBAff = getenv("EAO_BLUR_AFFINITY") ? atoi(getenv("EAO_BLUR_AFFINITY")) : 1;
-        const int resizeAff = envRAff && (nb & 7) == 0 ? 1 : 0, blurAff = envBAff && (nb & 7) == 0 ? 1 : 0;
-        auto fast = [&](hipStream_t str, int first, int end) {
-            eao::Range rg("orb: FAST cells");
-            static const int envAff = getenv("EAO_FAST_AFFINITY") ? atoi(getenv("EAO_FAST_AFFINITY")) : 1;
-            static const int envStop = getenv("EAO_FAST_STOP_AFTER") ? atoi(getenv("EAO_FAST_STOP_AFTER")) : 0;      // (census runs only: results are garbage)
-            const int aff = (envAff && (nb & 7) == 0 ? 1 : 0) | envStop << 8;
-            const bool whole = first == 0 && end == g.totalCells, narrow = g.fastStride == 48;
-            auto* kern = whole ? (narrow ? k_fast_cells<true, 48> : k_fast_cells<true, kTileStrideWide>)
-                               : (narrow ? k_fast_cells<false, 48> : k_fast_cells<false, kTileStrideWide>);
-            hipLaunchKernelGGL(kern, dim3(128 * ((end - first + 127) / 128), nb), dim3(64), g.fastLdsBytes, str, h->d_geom.p, h->d_cells.p, s,
-                               h->d_cellcand.p, h->d_cellcnt.p, f0, first, end, aff);
+    const hipStream_t ss = h->side;
+    // Level 0 IS the input image: its FAST cells (a third of all cells) do not wait for the pyramid.  Outside profiling
+    // runs they start on the side stream at once and overlap the seven resize launches; the side stream then goes on
+    // with the blur as before.  (Profiling runs keep the stages sequential so that each is timed alone.)
+    const int cells0 = g.L[0].nCells;
+    const bool early0 = !prof && g.nlevels > 1 && g.L[0].cellBase == 0 && cells0 < g.totalCells;
+    // frame -> XCD placement of the resize chain, of FAST and of the blur (round 5, see k_fast_cells): batches that are a multiple of 8
+    const int aff = (batch & 7) == 0 ? 1 : 0;
+    auto fast = [&](hipStream_t str, int first, int end) {
+        eao::Range rg("orb: FAST cells");
+        const bool whole = first == 0 && end == g.totalCells, narrow = g.fastStride == 48;
+        auto* kern = whole ? (narrow ? k_fast_cells<true, 48> : k_fast_cells<true, kTileStrideWide>)
+                           : (narrow ? k_fast_cells<false, 48> : k_fast_cells<false, kTileStrideWide>);
+        hipLaunchKernelGGL(kern, dim3(128 * ((end - first + 127) / 128), batch), dim3(64), g.fastLdsBytes, str, h->d_geom.p, h->d_cells.p, s,
+                           h->d_cellcand.p, h->d_cellcnt.p, 0, first, end, aff);
+    };
+    // Schedule of a (non-profiled) batch -- FAST and the blur are both VALU-bound, the quad-tree leaves the machine
+    // almost idle, so the blur runs beside the quad-tree, not beside FAST:
+    //   main:  resize 1..n-1 -> FAST(levels >= mid) -> quad-tree -> orientation + description
+    //   side:  FAST(level 0) -> FAST(levels 1..mid-1) once they exist -> (all FAST done) blur
+    // mid = 3: FAST of levels 1 and 2 joins level 0 on the side stream as soon as they exist, beside the rest of the pyramid
+    // chain, whose small launches leave the machine idle (measured, ms per step, mid 0 / 3: batch 32 0.296 / 0.296, 64
+    // 0.420 / 0.417, 128 0.717 / 0.706, 256 1.339 / 1.314; mid 4 = 1.314, mid 5 = 1.352).
+    // A single frame pays for the extra launch and event instead: 0.220 vs 0.211 ms per call -- small batches keep mid = 0.
+    const int mid = early0 && batch >= 48 && g.nlevels > 3 ? 3 : 0;
+    // ... and, up to 96 frames, their quad-trees right behind, beside the main stream's FAST of the upper levels instead of beside
+    // the blur afterwards: a quad-tree launch lasts as long as its level-0 workgroup (~60 us), and at these batches that is the long
+    // pole of the last-but-one segment (64 frames: 0.403 -> 0.390 ms per step).  At 256 frames it is slower (1.258 vs 1.226 ms: 768
+    // workgroups with 42 KB of LDS each take the occupancy FAST needs), so large batches keep all eight levels after FAST.
+    const bool qtEarly = mid > 0 && batch <= 96;
+    // word loads need a 4-byte aligned source whose rows can be read up to the next multiple of 4
+    const int src0Aligned = ((((uintptr_t)s.img0 | (uintptr_t)s.pitch0 | (uintptr_t)(batch > 1 ? s.fs0 : 0)) & 3) == 0) ? 1 : 0;
+    auto quadtree = [&](hipStream_t str, int lFirst, int nLev) {
+        eao::Range rg("orb: quad-tree");
+        launch_quadtree(h, str, batch, 0, lFirst, nLev);
+    };
+    // the blur on the side stream, behind evFork (which the schedule records on the main stream); evJoin marks its end
+    auto blur = [&]() -> eao_status {
+        EAO_HIP(hipStreamWaitEvent(ss, h->evFork, 0));
+        if (prof) EAO_HIP(hipEventRecord(ev[6], ss));
+        { eao::Range rg("orb: blur"); hipLaunchKernelGGL(k_blur7, dim3(g.totalTiles, batch), dim3(256), 0, ss, h->d_geom.p, s, h->d_blur.p, 0, src0Aligned, aff); }
+        if (prof) EAO_HIP(hipEventRecord(ev[7], ss));
+        EAO_HIP(hipEventRecord(h->evJoin, ss));
+        return EAO_OK;
+    };
+    // Measured (device-resident step, ms): batch 1: 0.117 fused vs 0.142 chain, 8: 0.136 / 0.160, 32: 0.231 / 0.235, 64: 0.353 /
+    // 0.309 -- small batches are bound by the chain of dependent launches, large ones by the VALU, where the fused kernel's
+    // recomputed fringes (+35 % pixels) and its seven barrier-separated levels per workgroup lose.
+    if (h->pyrFused && batch <= 32) {
+        // ---- the pyramid is ONE launch (k_pyramid_fused): no chain to hide things behind, so the schedule is simply
+        //   main:  pyramid -> FAST(levels >= 1) -> quad-trees(levels >= 1) ----------------------> orientation + description
+        //   side:  FAST(level 0) -> quad-tree(level 0, the longest) -> (pyramid done) blur --^
+        // (profiled calls: every stage alone, one after the other)
+        auto pyramid = [&] {
+            eao::Range rg("orb: pyramid");
+            hipLaunchKernelGGL(k_pyramid_fused, dim3(h->pyr.tilesX * h->pyr.tilesY, 1, batch), dim3(kPyrThreads), h->pyrLds, st, h->pyr, s, 0);
         };
-        // Schedule of a (non-profiled) batch -- FAST and the blur are both VALU-bound, the quad-tree leaves the machine
-        // almost idle, so the blur runs beside the quad-tree, not beside FAST:
-        //   main:  resize 1..n-1 -> FAST(levels >= mid) -> quad-tree -> orientation + description
-        //   side:  FAST(level 0) -> FAST(levels 1..mid-1) once they exist -> (all FAST done) blur
-        // mid = 3: FAST of levels 1 and 2 joins level 0 on the side stream as soon as they exist, beside the rest of the pyramid
-        // chain, whose small launches leave the machine idle (measured, ms per step, mid 0 / 3: batch 32 0.296 / 0.296, 64
-        // 0.420 / 0.417, 128 0.717 / 0.706, 256 1.339 / 1.314; mid 4 = 1.314, mid 5 = 1.352).  EAO_ORB_MID=0 switches it off.
-        // A single frame pays for the extra launch and event instead: 0.220 vs 0.211 ms per call -- small batches keep mid = 0.
-        static const int envMid = getenv("EAO_ORB_MID") ? atoi(getenv("EAO_ORB_MID")) : -1;
-        const int wantMid = envMid >= 0 ? envMid : (nb >= 48 ? 3 : 0);
-        const int mid = early0 && wantMid >= 2 && wantMid < g.nlevels ? wantMid : 0;
-        static const int envQtEarly = getenv("EAO_ORB_QT_EARLY") ? atoi(getenv("EAO_ORB_QT_EARLY")) : -1;
-        const bool qtEarly = mid > 0 && (envQtEarly >= 0 ? envQtEarly != 0 : nb <= 96);
-        // word loads need a 4-byte aligned source whose rows can be read up to the next multiple of 4
-        const int src0Aligned = ((((uintptr_t)s.img0 | (uintptr_t)s.pitch0 | (uintptr_t)(batch > 1 ? s.fs0 : 0)) & 3) == 0) ? 1 : 0;
-        auto quadtree = [&](hipStream_t str, int lFirst, int nLev) {
-            eao::Range rg("orb: quad-tree");
-            launch_quadtree(h, str, nb, f0, lFirst, nLev);
-        };
-        // Measured (device-resident step, ms): batch 1: 0.117 fused vs 0.142 chain, 8: 0.136 / 0.160, 32: 0.231 / 0.235, 64: 0.353 /
-        // 0.309 -- small batches are bound by the chain of dependent launches, large ones by the VALU, where the fused kernel's
-        // recomputed fringes (+35 % pixels) and its seven barrier-separated levels per workgroup lose.  EAO_ORB_PYRAMID=fused
-        // forces it for any batch, =chain disables it.
-        static const bool envFused = getenv("EAO_ORB_PYRAMID") && !strcmp(getenv("EAO_ORB_PYRAMID"), "fused");
-        if (h->pyrFused && (envFused || nb <= 32)) {
-            // ---- the pyramid is ONE launch (k_pyramid_fused): no chain to hide things behind, so the schedule is simply
-            //   main:  pyramid -> FAST(levels >= 1) -> quad-trees(levels >= 1) ----------------------> orientation + description
-            //   side:  FAST(level 0) -> quad-tree(level 0, the longest) -> (pyramid done) blur --^
-            // (profiled calls: every stage alone, one after the other)
-            const dim3 pgrid(h->pyr.tilesX * h->pyr.tilesY, 1, nb);
-            if (prof) {
-                { eao::Range rg("orb: pyramid"); hipLaunchKernelGGL(k_pyramid_fused, pgrid, dim3(kPyrThreads), h->pyrLds, ms, h->pyr, s, f0); }
-                if (pe) EAO_HIP(hipEventRecord(ev[1], ms));
-                EAO_HIP(hipEventRecord(h->evFork[i], ms));
-                EAO_HIP(hipStreamWaitEvent(ss, h->evFork[i], 0));
-                if (pe) EAO_HIP(hipEventRecord(ev[6], ss));
-                { eao::Range rg("orb: blur"); hipLaunchKernelGGL(k_blur7, dim3(g.totalTiles, nb), dim3(256), 0, ss, h->d_geom.p, s, h->d_blur.p, f0, src0Aligned, blurAff); }
-                if (pe) EAO_HIP(hipEventRecord(ev[7], ss));
-                EAO_HIP(hipEventRecord(h->evJoin[i], ss));
-                EAO_HIP(hipStreamWaitEvent(ms, h->evJoin[i], 0));
-                if (pe) EAO_HIP(hipEventRecord(ev[9], ms));
-                fast(ms, 0, g.totalCells);
-                if (pe) EAO_HIP(hipEventRecord(ev[2], ms));
-                quadtree(ms, 0, g.nlevels);
-                if (pe) EAO_HIP(hipEventRecord(ev[3], ms));
-                if (pe) EAO_HIP(hipEventRecord(ev[4], ms));
-            } else {
-                EAO_HIP(hipStreamWaitEvent(ss, h->evStart, 0));
-                fast(ss, 0, cells0);
-                quadtree(ss, 0, 1);
-                { eao::Range rg("orb: pyramid"); hipLaunchKernelGGL(k_pyramid_fused, pgrid, dim3(kPyrThreads), h->pyrLds, ms, h->pyr, s, f0); }
-                EAO_HIP(hipEventRecord(h->evFork[i], ms));
-                EAO_HIP(hipStreamWaitEvent(ss, h->evFork[i], 0));
-                { eao::Range rg("orb: blur"); hipLaunchKernelGGL(k_blur7, dim3(g.totalTiles, nb), dim3(256), 0, ss, h->d_geom.p, s, h->d_blur.p, f0, src0Aligned, blurAff); }
-                EAO_HIP(hipEventRecord(h->evJoin[i], ss));
-                fast(ms, cells0, g.totalCells);
-                quadtree(ms, 1, g.nlevels - 1);
-                EAO_HIP(hipStreamWaitEvent(ms, h->evJoin[i], 0));
-            }
-            { eao::Range rg("orb: orientation + description"); hipLaunchKernelGGL(k_orient_describe, dim3(eao::cdiv(std::min(cap, g.totalKpCap), 4), nb), dim3(256), 0, ms, h->d_geom.p, s,
-                               h->d_blur.p, h->d_levelkps.p, h->d_levelcnt.p, d_kps, d_desc, d_n, cap, f0, g.nlevels, 0, g.nlevels, 1); }
-            if (pe) EAO_HIP(hipEventRecord(ev[5], ms));
-            if (!onCaller) {
-                EAO_HIP(hipEventRecord(h->evDone[i], ms));
-                EAO_HIP(hipStreamWaitEvent(st, h->evDone[i], 0));
-            }
-            continue;
+        if (prof) {
+            pyramid();
+            EAO_HIP(hipEventRecord(ev[1], st));
+            EAO_HIP(hipEventRecord(h->evFork, st));
+            if ((so = blur())) return so;
+            EAO_HIP(hipStreamWaitEvent(st, h->evJoin, 0));
+            EAO_HIP(hipEventRecord(ev[9], st));
+            fast(st, 0, g.totalCells);
+            EAO_HIP(hipEventRecord(ev[2], st));
+            quadtree(st, 0, g.nlevels);
+            EAO_HIP(hipEventRecord(ev[3], st));
+            EAO_HIP(hipEventRecord(ev[4], st));
+        } else {
+            EAO_HIP(hipStreamWaitEvent(ss, h->evStart, 0));
+            fast(ss, 0, cells0);
+            quadtree(ss, 0, 1);
+            pyramid();
+            EAO_HIP(hipEventRecord(h->evFork, st));
+            if ((so = blur())) return so;
+            fast(st, cells0, g.totalCells);
+            quadtree(st, 1, g.nlevels - 1);
+            EAO_HIP(hipStreamWaitEvent(st, h->evJoin, 0));
         }
+    } else {
         if (early0) {
             EAO_HIP(hipStreamWaitEvent(ss, h->evStart, 0));
             fast(ss, 0, cells0);
@@ -1278,128 +1258,62 @@ eao_status enqueue_direct(eao_orb* h, const uint8_t* d_img, int pitch0, long lon
         // (Round 3 measured four more schedule variants and a multi-keypoint description kernel here -- the upper levels' FAST split over a third
         //  stream, the blur on its own stream with a split description, the top of the pyramid as one launch, several keypoints per wave -- none
         //  faster than this schedule; they were removed in round 4, DESIGN.md section 5 keeps the measurements and the commits that hold the code.)
-        auto orient = [&](hipStream_t str, int lFirst, int lEnd, int writeN) {
-            eao::Range rg("orb: orientation + description");
-            const int rangeCap = (lEnd < g.nlevels ? g.L[lEnd].kpBase : g.totalKpCap) - g.L[lFirst].kpBase;
-            hipLaunchKernelGGL(k_orient_describe, dim3(eao::cdiv(std::min(cap, rangeCap), 4), nb), dim3(256), 0, str, h->d_geom.p, s, h->d_blur.p, h->d_levelkps.p,
-                               h->d_levelcnt.p, d_kps, d_desc, d_n, cap, f0, g.nlevels, lFirst, lEnd, writeN);
-        };
         for (int l = 1; l < g.nlevels; l++) {
             const int G4 = eao::cdiv(g.L[l].w, 4);
             // ONE-WAVE workgroups: the chain's small launches run beside FAST launches that fill every CU with one-wave workgroups;
             // a 256-thread workgroup needs four wave slots free on ONE CU at the same moment and kept losing them to the next FAST
             // wave -- levels 2 and 4 took 32 / 37 us instead of 9, and the pyramid was the critical path of the step up to 121 us
-            // (64 frames: 0.296 -> 0.279 ms per step; EAO_RESIZE_WAVES=4 restores the 256-thread workgroups)
-            static const int envRW = getenv("EAO_RESIZE_WAVES") ? atoi(getenv("EAO_RESIZE_WAVES")) : 1;
-            const int rw = envRW == 2 || envRW == 4 ? envRW : 1;
-            dim3 grid(eao::cdiv(G4 * eao::cdiv(g.L[l].h, kResizeRows), 64 * rw), 1, nb), block(64, rw);
+            // (64 frames: 0.296 -> 0.279 ms per step)
             ResizeArgs ra;
             ra.G = G4; ra.invG = 1.0f / (float)G4;
             ra.D = {g.L[l].w, g.L[l].h, g.L[l].pitch, g.L[l].off};
             ra.S = {g.L[l - 1].w, g.L[l - 1].h, g.L[l - 1].pitch, g.L[l - 1].off};
             ra.invX = 1. / ((double)g.L[l].w / g.L[l - 1].w); ra.invY = 1. / ((double)g.L[l].h / g.L[l - 1].h);
             ra.srcIsInput = l == 1; ra.pyrFrameBytes = g.pyrFrameBytes;
-            ra.frameAffinity = resizeAff;
-            { eao::Range rg("orb: pyramid"); hipLaunchKernelGGL(k_resize, grid, block, 0, ms, ra, s, f0); }
+            ra.frameAffinity = aff;
+            { eao::Range rg("orb: pyramid"); hipLaunchKernelGGL(k_resize, dim3(eao::cdiv(G4 * eao::cdiv(g.L[l].h, kResizeRows), 64), 1, batch), dim3(64), 0, st, ra, s, 0); }
             if (l == mid - 1) {
-                EAO_HIP(hipEventRecord(h->evMid[i], ms));
-                EAO_HIP(hipStreamWaitEvent(ss, h->evMid[i], 0));
+                EAO_HIP(hipEventRecord(h->evMid, st));
+                EAO_HIP(hipStreamWaitEvent(ss, h->evMid, 0));
                 fast(ss, cells0, g.L[mid].cellBase);
-                // ... and, up to 96 frames, their quad-trees right behind, beside the main stream's FAST of the upper levels
-                // instead of beside the blur afterwards: a quad-tree launch lasts as long as its level-0 workgroup (~60 us), and
-                // at these batches that is the long pole of the last-but-one segment (64 frames: 0.403 -> 0.390 ms per step).
-                // At 256 frames it is slower (1.258 vs 1.226 ms: 768 workgroups with 42 KB of LDS each take the occupancy FAST
-                // needs), so large batches keep all eight levels after FAST.  EAO_ORB_QT_EARLY=0 / 1 overrides.
                 if (qtEarly) quadtree(ss, 0, mid);
             }
         }
-        if (early0) EAO_HIP(hipEventRecord(h->evFast0[i], ss));   // the side stream's share of FAST (and of the quad-trees)
-        if (pe) EAO_HIP(hipEventRecord(ev[1], ms));
+        if (early0) EAO_HIP(hipEventRecord(h->evFast0, ss));   // the side stream's share of FAST (and of the quad-trees)
         if (prof) {   // profiled calls: every stage alone -- blur, then FAST
-            EAO_HIP(hipEventRecord(h->evFork[i], ms));
-            EAO_HIP(hipStreamWaitEvent(ss, h->evFork[i], 0));
-            if (pe) EAO_HIP(hipEventRecord(ev[6], ss));
-            { eao::Range rg("orb: blur"); hipLaunchKernelGGL(k_blur7, dim3(g.totalTiles, nb), dim3(256), 0, ss, h->d_geom.p, s, h->d_blur.p, f0, src0Aligned, blurAff); }
-            if (pe) EAO_HIP(hipEventRecord(ev[7], ss));
-            EAO_HIP(hipEventRecord(h->evJoin[i], ss));
-            EAO_HIP(hipStreamWaitEvent(ms, h->evJoin[i], 0));
-            if (pe) EAO_HIP(hipEventRecord(ev[9], ms));
-            static const int envSplitProf = getenv("EAO_FAST_SPLIT_PROF") ? atoi(getenv("EAO_FAST_SPLIT_PROF")) : 0;      // (diagnostic: the three launches of the chain schedule, each alone)
-            if (envSplitProf && g.nlevels > 3) { fast(ms, 0, cells0); fast(ms, cells0, g.L[3].cellBase); fast(ms, g.L[3].cellBase, g.totalCells); }
-            else fast(ms, 0, g.totalCells);
+            EAO_HIP(hipEventRecord(ev[1], st));
+            EAO_HIP(hipEventRecord(h->evFork, st));
+            if ((so = blur())) return so;
+            EAO_HIP(hipStreamWaitEvent(st, h->evJoin, 0));
+            EAO_HIP(hipEventRecord(ev[9], st));
+            fast(st, 0, g.totalCells);
+            EAO_HIP(hipEventRecord(ev[2], st));
         } else {
             // The blur's fork point is the END OF THE PYRAMID, not the end of the main stream's FAST: on the side stream the blur
             // follows the quad-trees of the lower levels in stream order, which end when the main stream's FAST does, so the
             // blur still runs beside the upper levels' quad-trees -- but without a cross-stream hand-over (~10 us) in front of
             // it (64 frames: 0.2784 -> 0.2762 ms, 256 frames: 1.092 -> 1.071; measured the other way round before the resize
-            // launches became one-wave workgroups, when the pyramid ended 20 us later).  EAO_ORB_BLUR_EARLY=0 restores the old point.
-            static const int envBlurEarly = getenv("EAO_ORB_BLUR_EARLY") ? atoi(getenv("EAO_ORB_BLUR_EARLY")) : 1;
-            if (envBlurEarly) EAO_HIP(hipEventRecord(h->evFork[i], ms));
-            fast(ms, early0 ? (mid ? g.L[mid].cellBase : cells0) : 0, g.totalCells);
-            if (!envBlurEarly) EAO_HIP(hipEventRecord(h->evFork[i], ms));
-            EAO_HIP(hipStreamWaitEvent(ss, h->evFork[i], 0));
-            { eao::Range rg("orb: blur"); hipLaunchKernelGGL(k_blur7, dim3(g.totalTiles, nb), dim3(256), 0, ss, h->d_geom.p, s, h->d_blur.p, f0, src0Aligned, blurAff); }
-            EAO_HIP(hipEventRecord(h->evJoin[i], ss));
-            if (early0 && !qtEarly) EAO_HIP(hipStreamWaitEvent(ms, h->evFast0[i], 0));
+            // launches became one-wave workgroups, when the pyramid ended 20 us later).
+            EAO_HIP(hipEventRecord(h->evFork, st));
+            fast(st, early0 ? (mid ? g.L[mid].cellBase : cells0) : 0, g.totalCells);
+            if ((so = blur())) return so;
+            if (early0 && !qtEarly) EAO_HIP(hipStreamWaitEvent(st, h->evFast0, 0));
         }
-        if (pe) EAO_HIP(hipEventRecord(ev[2], ms));
-        quadtree(ms, qtEarly ? mid : 0, g.nlevels - (qtEarly ? mid : 0));
+        quadtree(st, qtEarly ? mid : 0, g.nlevels - (qtEarly ? mid : 0));
         // (the lower levels' quad-trees ran on the side stream, ahead of the blur: the wait for evJoin below covers them)
-        if (pe) EAO_HIP(hipEventRecord(ev[3], ms));
-        EAO_HIP(hipStreamWaitEvent(ms, h->evJoin[i], 0));
-        if (pe) EAO_HIP(hipEventRecord(ev[4], ms));
-        orient(ms, 0, g.nlevels, 1);
-        if (pe) EAO_HIP(hipEventRecord(ev[5], ms));
-        if (!onCaller) {
-            EAO_HIP(hipEventRecord(h->evDone[i], ms));
-            EAO_HIP(hipStreamWaitEvent(st, h->evDone[i], 0));
-        }
+        if (prof) EAO_HIP(hipEventRecord(ev[3], st));
+        EAO_HIP(hipStreamWaitEvent(st, h->evJoin, 0));
+        if (prof) EAO_HIP(hipEventRecord(ev[4], st));
     }
-    if (prof) EAO_HIP(hipEventRecord(ev[8], st));
-    if (!h->capturing) {
-        h->evLastValid = true;
-        if (h->everyCallEvent) { EAO_HIP(hipEventRecord(h->evLast, st)); h->evLastRecorded = true; }
+    { eao::Range rg("orb: orientation + description"); hipLaunchKernelGGL(k_orient_describe, dim3(eao::cdiv(std::min(cap, g.totalKpCap), 4), batch), dim3(256), 0, st,
+                       h->d_geom.p, s, h->d_blur.p, h->d_levelkps.p, h->d_levelcnt.p, d_kps, d_desc, d_n, cap, 0, g.nlevels, 0, g.nlevels, 1); }
+    if (prof) {
+        EAO_HIP(hipEventRecord(ev[5], st));
+        EAO_HIP(hipEventRecord(ev[8], st));
     }
-    EAO_HIP(hipGetLastError());
-    return EAO_OK;
-}
-
-
-// Optional (EAO_ORB_GRAPH=1): capture the launch sequence of one batch into a hipGraph per argument set and replay it.
-// Measured on MI355X (tools/dbg_lanes.py): replay 0.736 ms vs direct launches 0.742 ms per 64-frame batch, and cutting
-// the batch into 2 / 4 concurrent lanes (EAO_ORB_LANES) is SLOWER (0.75 / 0.94 ms): the kernels are throughput-bound,
-// not latency-bound, so the defaults are one lane and direct launches.  (Graph replay also crashes inside the HIP 7.0
-// runtime bundled with PyTorch 2.10; it works with the ROCm 7.2 runtime.)  Profiled calls always bypass the graph.
-eao_status enqueue(eao_orb* h, const uint8_t* d_img, int pitch0, long long fs0, int batch, eao_keypoint* d_kps,
-                   uint8_t* d_desc, int cap, int* d_n, hipStream_t st) {
-    static const int envLanes = getenv("EAO_ORB_LANES") ? atoi(getenv("EAO_ORB_LANES")) : 1;
-    static const bool envGraph = getenv("EAO_ORB_GRAPH") && atoi(getenv("EAO_ORB_GRAPH")) != 0;
-    if (h->profiling || !envGraph) return enqueue_direct(h, d_img, pitch0, fs0, batch, d_kps, d_desc, cap, d_n, st, envLanes);
-    const GraphKey key = {d_img, pitch0, fs0, batch, d_kps, d_desc, cap, d_n, envLanes};
-    if (!h->graphExec || !(h->graphKey == key)) {
-        if (h->graphExec) { (void)hipGraphExecDestroy(h->graphExec); h->graphExec = nullptr; }
-        hipGraph_t graph = nullptr;
-        EAO_HIP(hipStreamBeginCapture(h->stream, hipStreamCaptureModeThreadLocal));
-        h->capturing = true;
-        const eao_status st2 = enqueue_direct(h, d_img, pitch0, fs0, batch, d_kps, d_desc, cap, d_n, h->stream, envLanes);
-        h->capturing = false;
-        const hipError_t e = hipStreamEndCapture(h->stream, &graph);
-        if (st2) { if (graph) (void)hipGraphDestroy(graph); return st2; }
-        if (e != hipSuccess) { eao::set_error("hipStreamEndCapture: %s", hipGetErrorString(e)); return EAO_ERR_NO_DEVICE; }
-        EAO_HIP(hipGraphInstantiate(&h->graphExec, graph, nullptr, nullptr, 0));
-        (void)hipGraphDestroy(graph);
-        h->graphKey = key;
-    }
-    h->lastBatch = batch; h->lastComplete = false; h->pyrFrame = -1;
-    // the same ordering rule as the direct path: the replayed launches use the handle's scratch
-    if (h->evLastValid && h->lastStream != st) {
-        eao_status so = order_behind_last_call(h, st);
-        if (so) return so;
-    }
-    h->lastStream = st;
     h->evLastValid = true;
-    EAO_HIP(hipGraphLaunch(h->graphExec, st));
     if (h->everyCallEvent) { EAO_HIP(hipEventRecord(h->evLast, st)); h->evLastRecorded = true; }
+    EAO_HIP(hipGetLastError());
     return EAO_OK;
 }
 
@@ -1493,18 +1407,17 @@ eao_status eao_orb_stream_submit(eao_orb* h, int32_t slot, int32_t batch) {
     eao_status st = ensure(h, h->sW, h->sH, h->sB);
     if (st) return st;
     const size_t B = batch;
-    static const int envSkip = getenv("EAO_STREAM_SKIP") ? atoi(getenv("EAO_STREAM_SKIP")) : 0;      // diagnostic: 1 upload, 2 extraction, 4 download left out
-    if (!(envSkip & 1)) EAO_HIP(hipMemcpyAsync(sl.dIn, sl.pinIn, B * (size_t)h->sPitch * h->sH, hipMemcpyHostToDevice, h->sUp));
+    EAO_HIP(hipMemcpyAsync(sl.dIn, sl.pinIn, B * (size_t)h->sPitch * h->sH, hipMemcpyHostToDevice, h->sUp));
     EAO_HIP(hipEventRecord(sl.evIn, h->sUp));
     EAO_HIP(hipStreamWaitEvent(h->sRun, sl.evIn, 0));
-    if (!(envSkip & 2)) st = enqueue(h, sl.dIn, h->sPitch, (long long)h->sPitch * h->sH, batch, (eao_keypoint*)(sl.dOut + h->sOffK), sl.dOut + h->sOffD, h->sCap, (int*)sl.dOut, h->sRun);
+    st = enqueue(h, sl.dIn, h->sPitch, (long long)h->sPitch * h->sH, batch, (eao_keypoint*)(sl.dOut + h->sOffK), sl.dOut + h->sOffD, h->sCap, (int*)sl.dOut, h->sRun);
     if (st) return st;
     // the download is a KERNEL (see k_stream_download) on a stream of its own behind the extraction's event: a few workgroups that
     // store over PCIe beside the next slot's extraction; counts, keypoints and descriptors of the frames submitted lie in three ranges
     EAO_HIP(hipEventRecord(sl.evDone, h->sRun));
     EAO_HIP(hipStreamWaitEvent(h->sDown, sl.evDone, 0));
     const size_t parts[3][2] = {{0, (B * sizeof(int) + 15) & ~(size_t)15}, {h->sOffK, B * (size_t)h->sCap * sizeof(eao_keypoint)}, {h->sOffD, B * (size_t)h->sCap * 32}};
-    for (int q = 0; q < 3 && !(envSkip & 4); q++) {
+    for (int q = 0; q < 3; q++) {
         const size_t n16 = (parts[q][1] + 15) / 16;
         const unsigned grid = (unsigned)std::min<size_t>((n16 + 255) / 256, 64);
         hipLaunchKernelGGL(k_stream_download, dim3(grid), dim3(256), 0, h->sDown, reinterpret_cast<const uint4*>(sl.dOut + parts[q][0]),

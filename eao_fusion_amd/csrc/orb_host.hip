@@ -90,8 +90,7 @@ eao_status build_geometry(eao_orb* h, int W, int H) {
         PyrArgs& P = h->pyr;
         std::memset(&P, 0, sizeof(P));
         h->pyrFused = false;
-        static const bool envChain = getenv("EAO_ORB_PYRAMID") && !strcmp(getenv("EAO_ORB_PYRAMID"), "chain");
-        if (c.nlevels > 1 && !envChain) {
+        if (c.nlevels > 1) {
             P.nlevels = c.nlevels; P.pyrFrameBytes = g.pyrFrameBytes;
             for (int l = 0; l < c.nlevels; l++) {
                 P.L[l].w = g.L[l].w; P.L[l].h = g.L[l].h; P.L[l].pitch = g.L[l].pitch; P.L[l].off = g.L[l].off;
@@ -195,8 +194,7 @@ eao_status build_geometry(eao_orb* h, int W, int H) {
     // for 1000 features; a level that holds more falls back to the global arrays).  With the level-major dispatch the
     // smaller footprint pays: three workgroups per CU instead of two -- k_quadtree alone 210 -> 169 us at batch 256 (8192 ->
     // 4096 candidates; 3200: 143 us, but then the blur beside it is the longer of the two).
-    static const size_t kQtLdsCandEnv = getenv("EAO_QT_LDS_CAND") ? (size_t)atoi(getenv("EAO_QT_LDS_CAND")) : 0;
-    const size_t kQtLdsCand = kQtLdsCandEnv ? kQtLdsCandEnv : std::min<size_t>(8192, std::max<size_t>(2048, ((size_t)h->cfg.nfeatures * 4 + 63) & ~(size_t)63));
+    const size_t kQtLdsCand = std::min<size_t>(8192, std::max<size_t>(2048, ((size_t)h->cfg.nfeatures * 4 + 63) & ~(size_t)63));
     g.qtLdsCand = (int)std::min<size_t>(kQtLdsCand, h->quadLds < 76 * 1024 ? (76 * 1024 - h->quadLds) / 6 : 0) & ~7;
     h->quadLds += (size_t)g.qtLdsCand * 6;
     if (g.qtNodesGlobal) { g.qtLdsCand = 0; h->quadLds = 0; }     // (everything in the global workspace)
@@ -216,20 +214,7 @@ eao_status build_geometry(eao_orb* h, int W, int H) {
     { eao_status sq = quadtree_reserve_lds(h->quadLds); if (sq) return sq; }
     h->geomValid = true;
     h->batchCap = 0;
-    if (h->graphExec) { (void)hipGraphExecDestroy(h->graphExec); h->graphExec = nullptr; }
     return EAO_OK;
-}
-
-// EAO_ORB_LAST_EVENT: 0 = never (drain on a change of stream), 1 = adaptive (default), 2 = always
-int orb_last_event_mode() {
-    static const int mode = [] {
-        const char* e = getenv("EAO_ORB_LAST_EVENT");
-        if (!e) return 1;
-        if (!strcmp(e, "always")) return 2;
-        if (!strcmp(e, "never")) return 0;
-        return 1;
-    }();
-    return mode;
 }
 
 eao_status ensure(eao_orb* h, int W, int H, int batch, hipStream_t caller) {
@@ -249,22 +234,12 @@ eao_status ensure(eao_orb* h, int W, int H, int batch, hipStream_t caller) {
         EAO_HIP(make(&h->stream));
         EAO_HIP(hipEventCreateWithFlags(&h->evStart, hipEventDisableTiming));
         EAO_HIP(hipEventCreateWithFlags(&h->evLast, hipEventDisableTiming));
-        h->everyCallEvent = orb_last_event_mode() == 2;
-        // (HIP maps its streams onto a handful of hardware queues, and streams that share one execute in submission order: only the
-        //  lanes the schedule can use get streams -- lane 0 unless EAO_ORB_LANES asks for more -- so that the streaming API's upload
-        //  stream does not end up behind the extraction's side stream)
-        const int lanesWanted = std::max(1, std::min(eao_orb::kLanes, getenv("EAO_ORB_LANES") ? atoi(getenv("EAO_ORB_LANES")) : 1));
-        for (int i = 0; i < eao_orb::kLanes; i++) {
-            if (i < lanesWanted) {
-                EAO_HIP(make(&h->laneMain[i]));
-                EAO_HIP(make(&h->laneSide[i]));
-            }
-            EAO_HIP(hipEventCreateWithFlags(&h->evFork[i], hipEventDisableTiming));
-            EAO_HIP(hipEventCreateWithFlags(&h->evFast0[i], hipEventDisableTiming));
-            EAO_HIP(hipEventCreateWithFlags(&h->evMid[i], hipEventDisableTiming));
-            EAO_HIP(hipEventCreateWithFlags(&h->evJoin[i], hipEventDisableTiming));
-            EAO_HIP(hipEventCreateWithFlags(&h->evDone[i], hipEventDisableTiming));
-        }
+        // (HIP deals its streams round-robin onto a handful of hardware queues, and streams that share one execute in submission order.  The
+        //  idle spacer stream keeps the queue of every later stream where it was measured best: without it the mixed-load frame p99 beside a
+        //  LocalBundleAdjustment rose from 0.81-0.84 to 1.11-1.14 ms.)
+        EAO_HIP(make(&h->spacer));
+        EAO_HIP(make(&h->side));
+        for (hipEvent_t* e : {&h->evFork, &h->evFast0, &h->evMid, &h->evJoin}) EAO_HIP(hipEventCreateWithFlags(e, hipEventDisableTiming));
     }
     if (!h->d_dbg && getenv("EAO_DEBUG_STAMPS")) {
         EAO_HIP(hipMalloc(&h->d_dbg, 16 * kMaxLevels * sizeof(long long)));
@@ -290,7 +265,6 @@ eao_status ensure(eao_orb* h, int W, int H, int batch, hipStream_t caller) {
         RES(d_candcnt, B * g.nlevels);
 #undef RES
         h->batchCap = batch;
-        if (h->graphExec) { (void)hipGraphExecDestroy(h->graphExec); h->graphExec = nullptr; }   // buffers moved
     }
     return EAO_OK;
 }
@@ -301,7 +275,7 @@ eao_status ensure(eao_orb* h, int W, int H, int batch, hipStream_t caller) {
 eao_status order_behind_last_call(eao_orb* h, hipStream_t st) {
     if (h->evLastRecorded) EAO_HIP(hipStreamWaitEvent(st, h->evLast, 0));
     else EAO_HIP(hipDeviceSynchronize());
-    if (orb_last_event_mode() != 0) h->everyCallEvent = true;
+    h->everyCallEvent = true;
     return EAO_OK;
 }
 
@@ -324,14 +298,14 @@ void stream_release(eao_orb* h) {
 // Readers of the last extraction's products (pyramid levels, candidate taps, the stereo matcher).  After a host-API call (eao_orb_extract / _batch: what the
 // class-surface adapter makes) the products are final when the call returns -- nothing to wait for, and in particular no device-wide synchronise that would
 // make the Tracking thread wait for the LocalMapping thread's bundle adjustment.  Only after a DEVICE-API call on a caller's stream, which
-// the library must not touch again (its owner may have destroyed it, see enqueue_direct) and on which recording an event per call was measured at ~5 us, does
+// the library must not touch again (its owner may have destroyed it, see enqueue) and on which recording an event per call was measured at ~5 us, does
 // the reader drain the device.
 eao_status wait_last_extraction(eao_orb* h) {
     if (!h->lastComplete) {
         if (h->evLastRecorded) EAO_HIP(hipEventSynchronize(h->evLast));      // (round 6: the call left its event)
         else {
             EAO_HIP(hipDeviceSynchronize());
-            if (orb_last_event_mode() != 0) h->everyCallEvent = true;           // this handle has readers behind device-API calls: later calls leave an event
+            h->everyCallEvent = true;           // this handle has readers behind device-API calls: later calls leave an event
         }
         h->lastComplete = true;
     }
@@ -341,14 +315,13 @@ eao_status wait_last_extraction(eao_orb* h) {
 // The caller's frames (pageable memory) to h->d_in in the device pitch.  Small uploads -- the per-frame calls -- go through a pinned staging buffer of the handle: the
 // runtime's own path for pageable memory registers the caller's pages with the driver for the duration of the copy, and a registered range that the kernel touches
 // meanwhile (another thread's munmap, page migration) has the driver take every queue of the process off the GPU for a millisecond or more -- one tracked frame in a
-// thousand took 6 - 12 ms beside a looping LocalBundleAdjustment.  The staging copy costs ~15 us per 640 x 480 frame.  EAO_ORB_PINNED_IN=0: the runtime's path (A/B runs).
+// thousand took 6 - 12 ms beside a looping LocalBundleAdjustment.  The staging copy costs ~15 us per 640 x 480 frame.  Larger uploads take the runtime's path.
 constexpr size_t kPinnedInMax = 8u << 20;
 eao_status upload_frames(eao_orb* h, const uint8_t* img, int width, int height, int stride, long long frame_stride, int batch) {
     const Geom& g = h->geom;
     const long long fs0 = (long long)g.L[0].pitch * height;
     const size_t bytes = (size_t)batch * (size_t)fs0;
-    static const bool envNoPinned = getenv("EAO_ORB_PINNED_IN") && !atoi(getenv("EAO_ORB_PINNED_IN"));
-    if (bytes <= kPinnedInMax && !envNoPinned) {
+    if (bytes <= kPinnedInMax) {
         if (h->pinUpCap < bytes) {
             if (h->pinUp) (void)hipHostFree(h->pinUp);
             h->pinUp = nullptr; h->pinUpCap = 0;
@@ -428,22 +401,14 @@ void eao_orb_destroy(eao_orb* h) {
     if (!h) return;
     for (hipEvent_t e : h->evs) if (e) (void)hipEventDestroy(e);
     if (h->stream) { (void)hipStreamSynchronize(h->stream); (void)hipStreamDestroy(h->stream); }
-    for (int i = 0; i < eao_orb::kLanes; i++) {
-        if (h->laneMain[i]) { (void)hipStreamSynchronize(h->laneMain[i]); (void)hipStreamDestroy(h->laneMain[i]); }
-        if (h->laneSide[i]) { (void)hipStreamSynchronize(h->laneSide[i]); (void)hipStreamDestroy(h->laneSide[i]); }
-        if (h->evFork[i]) (void)hipEventDestroy(h->evFork[i]);
-        if (h->evFast0[i]) (void)hipEventDestroy(h->evFast0[i]);
-        if (h->evMid[i]) (void)hipEventDestroy(h->evMid[i]);
-        if (h->evJoin[i]) (void)hipEventDestroy(h->evJoin[i]);
-        if (h->evDone[i]) (void)hipEventDestroy(h->evDone[i]);
-    }
+    for (hipStream_t q : {h->spacer, h->side}) if (q) { (void)hipStreamSynchronize(q); (void)hipStreamDestroy(q); }
+    for (hipEvent_t e : {h->evFork, h->evFast0, h->evMid, h->evJoin}) if (e) (void)hipEventDestroy(e);
     if (h->pinOut) (void)hipHostFree(h->pinOut);
     if (h->pinUp) (void)hipHostFree(h->pinUp);
     if (h->pinPyr) (void)hipHostFree(h->pinPyr);
     stream_release(h);
     if (h->evStart) (void)hipEventDestroy(h->evStart);
     if (h->evLast) (void)hipEventDestroy(h->evLast);
-    if (h->graphExec) (void)hipGraphExecDestroy(h->graphExec);
     delete h;
 }
 
@@ -509,8 +474,7 @@ eao_status eao_orb_extract_batch(eao_orb* h, const uint8_t* img, int32_t width, 
     // pinned host memory -- ~70 KB per frame over PCIe -- and the rows that exist are copied to the caller's (pageable) arrays
     // after the one synchronisation: three pageable device-to-host copies (~15 us each) gone.  Large batches keep the DMA path.
     const size_t outBytes = B * sizeof(int) + 64 + B * (size_t)cap * (sizeof(eao_keypoint) + 32);
-    static const bool envNoPinned = getenv("EAO_ORB_PINNED_OUT") && !atoi(getenv("EAO_ORB_PINNED_OUT"));      // (A/B switch)
-    if (outBytes <= kPinnedOutMax && !envNoPinned) {
+    if (outBytes <= kPinnedOutMax) {
         if (h->pinOutCap < outBytes) {
             if (h->pinOut) (void)hipHostFree(h->pinOut);
             h->pinOut = nullptr; h->pinOutCap = 0;
@@ -569,8 +533,8 @@ eao_status eao_orb_stream_create(eao_orb* h, int32_t width, int32_t height, int3
     h->sOutBytes = (h->sOffD + B * cap * 32 + 15) & ~(size_t)15;
     // Three plain streams.  HIP maps streams onto a few hardware queues and streams that share one run in submission order: with the
     // handle's eight unused lane streams in the way the upload stream shared a queue with the extraction's side stream and the next
-    // slot's upload started ~100 us into the current extraction (0.50 ms per 64 frames instead of 0.42; the lane streams are now
-    // created on demand).  Stream PRIORITIES make it worse on this runtime (upload high: 0.44; download or extraction low: 0.83-0.88).
+    // slot's upload started ~100 us into the current extraction (0.50 ms per 64 frames instead of 0.42; the handle no longer creates
+    // them).  Stream PRIORITIES make it worse on this runtime (upload high: 0.44; download or extraction low: 0.83-0.88).
     EAO_HIP(eao::create_stream(&h->sUp, eao::StreamClass::Latency));
     EAO_HIP(eao::create_stream(&h->sRun, eao::StreamClass::Latency));
     EAO_HIP(eao::create_stream(&h->sDown, eao::StreamClass::Latency));
@@ -682,7 +646,7 @@ eao_status eao_orb_extract_ref(eao_orb* h, const uint8_t* img, int32_t width, in
     return EAO_OK;
 }
 
-int32_t eao_orb_lanes(int32_t batch) { return batch < eao_orb::kLanes ? (batch > 0 ? batch : 1) : eao_orb::kLanes; }
+int32_t eao_orb_lanes(int32_t) { return 1; }
 
 eao_status eao_orb_set_profiling(eao_orb* h, int32_t on) {
     EAO_REQUIRE(h, "null handle");
@@ -699,7 +663,6 @@ eao_status eao_orb_last_timing(eao_orb* h, float ms[6]) {
     for (size_t c = 0; c < calls; c++) {
         hipEvent_t* ev = &h->evs[c * kProfEvents];
         float t;
-        // stage intervals of slice 0 (one of the concurrently running sub-batches)
         EAO_HIP(hipEventElapsedTime(&t, ev[0], ev[1])); acc[0] += t;   // pyramid
         EAO_HIP(hipEventElapsedTime(&t, ev[9], ev[2])); acc[1] += t;   // FAST (after the blur of a profiled call)
         EAO_HIP(hipEventElapsedTime(&t, ev[2], ev[3])); acc[2] += t;   // quad-tree

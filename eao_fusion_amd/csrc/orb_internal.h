@@ -98,12 +98,6 @@ constexpr int kQTSmall = 1024, kQTLarge = 256;
 constexpr int kQtNodeInts = 2 + 2 + 2 + 4 + 4 + 5;   // per list entry next to its two boxes: cnt, crk, mid (x2 each), childcnt, childpos (x4), five work arrays
 
 constexpr size_t kProfEvents = 10;
-struct GraphKey {
-    const void* img; int pitch0; long long fs0; int batch; void* kps; void* desc; int cap; void* n; int lanes;
-    bool operator==(const GraphKey& o) const {
-        return img == o.img && pitch0 == o.pitch0 && fs0 == o.fs0 && batch == o.batch && kps == o.kps && desc == o.desc && cap == o.cap && n == o.n && lanes == o.lanes;
-    }
-};
 
 
 // the same on the host (k_pyramid_fused reads tables built with it): lrintf rounds to nearest even like v_cvt_i32_f32
@@ -145,7 +139,7 @@ inline int cv_round(double v) { return (int)std::lrint(v); }
 }  // namespace eao
 
 struct eao_orb {
-    using Geom = eao::orb::Geom; using CellDesc = eao::orb::CellDesc; using PyrArgs = eao::orb::PyrArgs; using ImgSrc = eao::orb::ImgSrc; using GraphKey = eao::orb::GraphKey;
+    using Geom = eao::orb::Geom; using CellDesc = eao::orb::CellDesc; using PyrArgs = eao::orb::PyrArgs; using ImgSrc = eao::orb::ImgSrc;
     eao_orb_cfg cfg;
     std::vector<float> scale, invScale, sigma2, invSigma2;
     std::vector<int> quota;
@@ -163,26 +157,24 @@ struct eao_orb {
     bool pyrFused = false;
     // device state
     hipStream_t stream = nullptr;
-    // up to kLanes sub-batches can run as independent pipelines, each on its own (main, side) stream pair
-    // (EAO_ORB_LANES, default 1: see the measurement note at enqueue())
-    static constexpr int kLanes = 4;
-    hipStream_t laneMain[kLanes] = {}, laneSide[kLanes] = {};
+    hipStream_t side = nullptr;    // the side stream of every call (FAST of the lower levels, their quad-trees, the blur); the main chain runs on the call's stream
+    hipStream_t spacer = nullptr;  // never used: keeps the hardware queues of the streams created after it where they were (see ensure())
     // Round 6: the handle's private streams (its own main stream, the side stream of every call) take the priority of the stream the handle's FIRST call arrives on:
     // a host-API call (ORBextractor::operator(), what the Tracking thread makes) arrives on no stream -> Latency class; a device-API call arrives on the caller's stream
     // (PyTorch's default stream in bench.py) -> that stream's priority.  Measured (gpurun_out/r06g .. r06i, 64-frame step on PyTorch's default-priority stream): side
     // stream at the same (default) priority 0.2553 ms; a Latency-class side stream beside it 0.2665 ms (FAST level 0 and the blur overtake the main chain's seven dependent
     // resize launches); and a default-priority side stream created NEXT TO idle Latency-class streams of the same handle 0.43-0.64 ms, every stage twice as long -- one
     // handle's streams are all of one priority.
-    bool evLastValid = false, capturing = false;   // evLastValid: a call has been enqueued on lastStream
+    bool evLastValid = false;              // a call has been enqueued on lastStream
     hipStream_t lastStream = nullptr;      // the stream of the previous call: compared, never dereferenced (its owner may have destroyed it)
     // Round 6: ordering between calls that come in on DIFFERENT streams without draining the device (under the reference's concurrency a drain makes the
     // Tracking thread wait for LocalMapping's whole bundle adjustment).  evLast is recorded behind a call's last kernel, a call on another stream waits for
     // it ON THE DEVICE (hipStreamWaitEvent).  An event record between two calls costs the stream a few microseconds, so a handle that only ever sees one
     // stream (the common case: the bench loop, one tracker) records nothing; the FIRST change of stream in a handle's life finds no event and drains once,
-    // from then on every call leaves its event.  EAO_ORB_LAST_EVENT=always records from the first call on (no drain ever), =never is the rounds 1-5 drain.
+    // from then on every call leaves its event.
     hipEvent_t evLast = nullptr;
     bool everyCallEvent = false, evLastRecorded = false;
-    hipEvent_t evStart = nullptr, evFork[kLanes] = {}, evJoin[kLanes] = {}, evDone[kLanes] = {}, evFast0[kLanes] = {}, evMid[kLanes] = {};
+    hipEvent_t evStart = nullptr, evFork = nullptr, evJoin = nullptr, evFast0 = nullptr, evMid = nullptr;
     eao::DevBuf<Geom> d_geom;
     eao::DevBuf<CellDesc> d_cells;
     eao::DevBuf<uint8_t> d_pyr, d_blur, d_in;
@@ -209,8 +201,6 @@ struct eao_orb {
     int lastBatch = 0;
     bool profiling = false;
     long long* d_dbg = nullptr;   // EAO_DEBUG_STAMPS: per-level phase cycles of k_quadtree (diagnostic runs only)
-    hipGraphExec_t graphExec = nullptr;
-    GraphKey graphKey = {};
     std::vector<hipEvent_t> evs;   // kProfEvents events per profiled call, averaged by eao_orb_last_timing
     size_t evUsed = 0;
     // streaming host API (eao_orb_stream_*): a ring of pinned input / output slots, three streams (upload, extraction, download)
@@ -232,7 +222,6 @@ namespace eao {
 namespace orb {
 // orb_host.hip
 constexpr uintptr_t kNoCallerStream = ~(uintptr_t)0;      // a host-API call: the handle's streams are of the Latency class
-int orb_last_event_mode();
 eao_status ensure(eao_orb* h, int W, int H, int batch, hipStream_t caller = (hipStream_t)kNoCallerStream);
 eao_status order_behind_last_call(eao_orb* h, hipStream_t st);
 void stream_release(eao_orb* h);

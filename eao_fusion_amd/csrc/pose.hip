@@ -691,7 +691,7 @@ __global__ __launch_bounds__(MAXT) void k_pose_optimization_batch(const PoseDev*
 }
 // Launch geometry of the register kernels.  A lone wave issues an fp64 instruction every 5.45 cycles, the SIMD's fp64 pipe takes one every
 // 4.3 (tools/ubench/f64_simd.hip, profiles/r03_ubench_f64.txt): one wave per SIMD (four per workgroup) is within 20 % of what the CU's
-// fp64 pipes can do, and the per-wave stamps of the evaluation say the same (tools/dbg_pose_waves.py, 1000 correspondences, 23 heavy
+// fp64 pipes can do, and the per-wave stamps of the evaluation say the same (EAO_DEBUG_STAMPS, 1000 correspondences, 23 heavy
 // passes: four waves x 4 edges 114 k ticks; eight waves x 2 edges: waves 0-3 59 k, waves 4-7 -- the younger wave of every SIMD, served
 // when the older one has nothing to issue -- 108 k).  Every further wave adds its own reduction tree.  Hence FOUR waves with up to four
 // edges per thread for frames of up to 1024 correspondences (edge i lives in thread i mod 256, slot i / 256), eight waves x four edges beyond.
@@ -700,14 +700,6 @@ inline int pose_threads(int n) { return n <= 4 * kPoseWaves4 ? std::min(kPoseWav
 inline int pose_ept(int n) { return n <= kPoseWaves4 ? 1 : (n <= 2 * kPoseWaves4 ? 2 : 4); }
 inline int pose_class(int n) { return n <= kPoseWaves4 ? 0 : n <= 2 * kPoseWaves4 ? 1 : n <= 4 * kPoseWaves4 ? 2 : 3; }
 inline void launch_pose_registers(const PoseDev& P, int n, bool planes, hipStream_t s) {
-    static const bool env8 = getenv("EAO_POSE_WAVES") && atoi(getenv("EAO_POSE_WAVES")) == 8;      // A/B switch: eight waves, fewer edges per thread
-    if (env8 && !planes && n <= 4 * kPoseThreads) {
-        const dim3 b8(kPoseThreads);
-        if (n <= kPoseThreads) hipLaunchKernelGGL((k_pose_optimization<1, false, kPoseThreads>), dim3(1), b8, 0, s, P);
-        else if (n <= 2 * kPoseThreads) hipLaunchKernelGGL((k_pose_optimization<2, false, kPoseThreads>), dim3(1), b8, 0, s, P);
-        else hipLaunchKernelGGL((k_pose_optimization<4, false, kPoseThreads>), dim3(1), b8, 0, s, P);
-        return;
-    }
     const dim3 b(planes && n <= 4 * kPoseWaves4 ? std::max(pose_threads(n), std::min(kPoseWaves4, (13 * P.nPlanes + 63) / 64 * 64)) : pose_threads(n));
     switch (pose_class(n) + (planes ? 4 : 0)) {
         case 0: hipLaunchKernelGGL((k_pose_optimization<1, false, kPoseWaves4>), dim3(1), b, 0, s, P); break;
@@ -1056,8 +1048,7 @@ eao_status eao_pose_optimization(const eao_pose_problem* p, eao_pose_result* r) 
     // The register variants read every input exactly once: they take it straight from the pinned mirror over PCIe (~60 KB) --
     // an upload in front of the kernel is a copy-engine job plus a hand-over to the compute queue (~10 us).  The memory
     // variant walks the edges in every LM pass and gets its copy.
-    static const bool envUpload = getenv("EAO_POSE_UPLOAD") && atoi(getenv("EAO_POSE_UPLOAD")) != 0;      // (A/B switch)
-    const bool zeroCopy = n <= 4 * kPoseThreads && M == 0 && !envUpload;      // (plane coefficients are re-read in every pass: uploaded)
+    const bool zeroCopy = n <= 4 * kPoseThreads && M == 0;      // (plane coefficients are re-read in every pass: uploaded)
     if (!zeroCopy) EAO_HIP(hipMemcpyAsync(a.base + off0, c.pin + off0, off1 - off0, hipMemcpyHostToDevice, c.stream));
     PoseDev P;
     P.nDev = nullptr; P.scatterIdx = nullptr; P.scatterOut = nullptr; P.done = nullptr; P.doneSeq = 0;

@@ -17,7 +17,7 @@ CHI2_REL_FAR_OFF = 1e-4      # the far-off-start families (25 degrees, 0.8 m off
 LAMBDA_REL = 5e-4            # round 2 (2e-3 in round 1): observed 5.1e-5; the oracle's own one-ulp band is 8e-3 (profiles/r02_lm_trace_sensitivity.txt)
 LAMBDA_REL_FAR_OFF = 4e-3    # round 4 (2e-3 before), the tile-solver path: the pair assembly works on Cholesky-scaled blocks W = Hpl C^-T (csrc/lm.hip, ba_chol3) where the
                              # oracle multiplies by an explicit 3 x 3 inverse as upstream does -- different rounding from the first iteration on.  Seed 3037, iteration 14:
-                             # 3.07e-3 off (1.45e-3 with EAO_BA_WMODE=0) while chi2 agrees to 9e-8 and the points to 8e-6 of the update (profiles/r04_lm_seed3037.txt)
+                             # 3.07e-3 off (1.45e-3 with the explicit inverse of round 3) while chi2 agrees to 9e-8 and the points to 8e-6 of the update (profiles/r04_lm_seed3037.txt)
 LAMBDA_REL_FAR_OFF_MAP_SCALE = 2e-3      # the same windows on the map-scale path (explicit inverse there): round 1's figure, never moved
 
 # ---- far-off seeds 3030..3059 on which the ORACLE ITSELF moves by more than UPDATE_REL -- or changes its LM schedule -- when its inputs are perturbed by ONE float32
