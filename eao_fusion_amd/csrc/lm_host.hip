@@ -109,7 +109,7 @@ struct BAJob {
         EAO_REQUIRE(nFreeIn <= kBigMaxFree, "at most %d free keyframes in this build (got %d)", kBigMaxFree, nFreeIn);
         // more free keyframes than the single-workgroup solvers take (or EAO_BA_SOLVER=big, the harness's A/B switch): the
         // map-scale path, dense system in HBM factorised by the whole chip (k_bal_*)
-        static const char* solverEnv0 = getenv("EAO_BA_SOLVER");
+        const char* const solverEnv0 = getenv("EAO_BA_SOLVER");      // (read per call, like the switches below: a test sets it after the process's first call)
         // (measured, LocalBundleAdjustment wall time, tools/dbg_ba_sizes.py: the LDS / global-scratch single-workgroup solver with
         //  the slab assembly takes 5.8 ms at 31 free keyframes and 29 ms at 64, the map-scale path 3.6 and 6.9 ms -- so everything
         //  beyond the register-tile solver goes there; that older path was removed in round 5)
@@ -162,7 +162,8 @@ struct BAJob {
                     int prev = cbp[q] > 0 ? ept[cbp[q] - 1] : -1;
                     for (int e = cbp[q]; e < e1;) {
                         const int lmk = ept[e];
-                        if (lmk <= prev || lmk >= nPo_) { bad[2 * q] = -2; return; }
+                        // (unsigned: `prev` of a chunk q > 0 is the caller's own, unvalidated entry in front of the chunk -- a negative landmark behind a more negative one ascends too)
+                        if ((unsigned)lmk >= (unsigned)nPo_ || lmk <= prev) { bad[2 * q] = -2; return; }
                         int m = 0, run = 0;
                         for (; e < e1 && ept[e] == lmk; e++, run++) {
                             const int ec = ecam[e];

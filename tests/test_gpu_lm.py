@@ -118,13 +118,34 @@ def test_local_ba_rejected_trials(gpu, oracle, seed):
     assert np.array_equal(r["edge_outlier"], o["edge_outlier"])
 
 
+def _bits_differ(a, b):
+    """two results of one problem that did NOT come out of the same arithmetic: some bit of the poses, the points or the lambda / chi2 trace differs"""
+    return not (np.array_equal(a["poses"].view(np.uint32), b["poses"].view(np.uint32)) and np.array_equal(a["points"].view(np.uint32), b["points"].view(np.uint32)) and
+                np.array_equal(a["trace"]["lam"], b["trace"]["lam"]) and np.array_equal(a["trace"]["chi2"], b["trace"]["chi2"]))
+
+
+def _force_map_scale_path(gpu, monkeypatch):
+    """EAO_BA_SOLVER=big for the rest of the test -- after showing that the switch is live in THIS process.  The library read it once per process until the window became
+    a grid dimension; every test that set it later in a pytest run compared the tile solver with the oracle a second time and passed.  The observable: the tile solver and
+    the map-scale kernels round differently from the first iteration on (tests/lm_tolerances.py, LAMBDA_REL_FAR_OFF), so on a far-off window (seed 3034) the forced
+    and the default run differ in some bit of the lambda trace or of the poses.  A forced run that IS the default run fails here, not silently."""
+    p = synth.synth_ba(n_free=5, n_fixed=2, n_points=200, seed=3034, rot_noise_deg=25, trans_noise=0.8, point_noise=1.0, mono_frac=0.7)
+    monkeypatch.delenv("EAO_BA_SOLVER", raising=False)
+    default = gpu.Optimizer.LocalBundleAdjustment(p)
+    monkeypatch.setenv("EAO_BA_SOLVER", "big")
+    forced = gpu.Optimizer.LocalBundleAdjustment(p)
+    assert _bits_differ(forced, default), "EAO_BA_SOLVER=big did not change a bit of the result: the forced run is the default (tile solver) run"
+
+
 @pytest.mark.parametrize("seed", [3030, 3034, 3043, 3051])
 def test_rejected_trials_on_the_map_scale_path(gpu, oracle, seed, monkeypatch):
     """The same far-off windows through the map-scale kernels (EAO_BA_SOLVER=big): rejected trials freeze the stream, the
     host replays them one by one with the dense factorisation, a failed / empty second pass is reported like g2o's."""
-    monkeypatch.setenv("EAO_BA_SOLVER", "big")
     p = synth.synth_ba(n_free=5, n_fixed=2, n_points=200, seed=seed, rot_noise_deg=25, trans_noise=0.8, point_noise=1.0, mono_frac=0.7)
+    default = gpu.Optimizer.LocalBundleAdjustment(p)
+    _force_map_scale_path(gpu, monkeypatch)
     r = gpu.Optimizer.LocalBundleAdjustment(p)
+    assert _bits_differ(r, default), "the forced run is the default run"
     o = oracle.local_ba(p)
     assert list(r["iters"]) == list(o["iters"])
     _check_trace(r, o, rel=CHI2_REL_FAR_OFF, lam_rel=LAMBDA_REL_FAR_OFF_MAP_SCALE)
@@ -272,9 +293,11 @@ def test_map_scale_path_on_small_windows(gpu, oracle, kw, monkeypatch):
     """EAO_BA_SOLVER=big forces the map-scale kernels onto windows the single-workgroup solvers would take (n = 66, 18 and
     204 unknowns: identity padding up to the 32-column panels, a single panel, odd tile counts): same results as the oracle,
     for BundleAdjustment and for both passes of LocalBundleAdjustment."""
-    monkeypatch.setenv("EAO_BA_SOLVER", "big")
     p = synth.synth_ba(**kw)
+    default = gpu.Optimizer.BundleAdjustment(p, 10, bRobust=True)
+    _force_map_scale_path(gpu, monkeypatch)
     r = gpu.Optimizer.BundleAdjustment(p, 10, bRobust=True)
+    assert _bits_differ(r, default) == (kw["n_free"] <= 30)          # (34 free keyframes take the map-scale path by themselves: forced or not, the same call)
     o = oracle.bundle_adjustment(p, 10, True)
     assert list(r["iters"]) == [int(o["iters"][0]), 0]
     _check_trace(r, o)
@@ -577,6 +600,12 @@ def test_map_scale_set_up_refuses_bad_edge_lists_the_same_way_on_any_crew(gpu, t
         dup[k] = np.ascontiguousarray(np.insert(p[k], e + 1, p[k][e], axis=0))
     with pytest.raises(Exception, match="two edges join camera %d and point %d" % (p["edge_cam"][e], p["edge_point"][e])):
         gpu.Optimizer.BundleAdjustment(dup, 3, bRobust=False)
+    # two NEGATIVE landmark indices, ascending, on either side of a chunk boundary of the crew's validation pass (48 chunks; with the two entries unequal chunk 17 starts
+    # exactly at e): the chunk takes the entry in front of it as the landmark it continues from, and must refuse what follows by its range, not by that comparison
+    e = len(p["edge_point"]) * 17 // 48
+    bad = dict(p); ep = p["edge_point"].copy(); ep[e - 1], ep[e] = -1000000, -999999; bad["edge_point"] = ep
+    with pytest.raises(Exception, match="edge %d out of range" % (e - 1)):
+        gpu.Optimizer.BundleAdjustment(bad, 3, bRobust=False)
     q, _ = _shuffle_edges(p, 5750)
     a, b = gpu.Optimizer.BundleAdjustment(p, 4, bRobust=False), gpu.Optimizer.BundleAdjustment(q, 4, bRobust=False)
     assert list(a["iters"]) == list(b["iters"]) and list(a["trace"]["trials"]) == list(b["trace"]["trials"])

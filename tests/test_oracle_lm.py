@@ -89,13 +89,10 @@ def test_fixed_cameras_do_not_move_and_abort(oracle):
     assert np.abs(r2["points"] - p["points"]).max() == 0
 
 
-def test_schur_step_equals_full_dense_step(oracle):
-    """One LM step of the oracle (Schur) vs a numpy full (poses+points) dense solve built from the oracle's
-    own per-edge residuals/Jacobians: checks the reduction/back-substitution algebra."""
-    L = oracle.lib()
-    p = synth.synth_ba(n_free=3, n_fixed=1, n_points=40, outlier_frac=0.0)
-    r = oracle.local_ba(p, its=(1, 0))
-    # rebuild the normal equations in numpy at the initial state
+def dense_lm_step(L, p):
+    """One damped Gauss-Newton step of the whole problem `p` (poses AND points, no Schur complement) as a numpy dense solve built from the oracle's own per-edge residuals
+    and Jacobians at the initial state: stereo and monocular edges (2 rows, Huber width sqrt(5.991)), Huber weights wherever an edge is beyond its width, a landmark nobody
+    free observes, landmarks and cameras without any edge (a zero block + lambda: they do not move).  Returns (points after the step, {free camera: cam7 after the step})."""
     nc, npnt = len(p["poses"]), len(p["points"])
     cam7 = np.zeros((nc, 7))
     for c in range(nc):
@@ -104,11 +101,14 @@ def test_schur_step_equals_full_dense_step(oracle):
     cidx = {c: i for i, c in enumerate(free)}
     n = 6 * len(free) + 3 * npnt
     H = np.zeros((n, n)); b = np.zeros(n)
-    d = float(np.float32(np.sqrt(7.815)))
+    d3, d2 = float(np.float32(np.sqrt(7.815))), float(np.float32(np.sqrt(5.991)))
     pts = p["points"].astype(np.float64)
     for k in range(len(p["edge_cam"])):
         c, q = int(p["edge_cam"][k]), int(p["edge_point"][k])
-        err, A, B = _edge_eval(L, cam7[c], pts[q], p["obs"][k].astype(np.float64), True)
+        stereo = not (p["obs"][k, 2] < 0)
+        D, d = (3, d3) if stereo else (2, d2)
+        err, A, B = _edge_eval(L, cam7[c], pts[q], p["obs"][k].astype(np.float64), stereo)
+        err, A, B = err[:D], A[:D], B[:D]
         info = float(p["inv_sigma2"][k])
         chi = info * err @ err
         w = 1.0 if chi <= d * d else d / np.sqrt(chi)
@@ -125,12 +125,27 @@ def test_schur_step_equals_full_dense_step(oracle):
     lam = 1e-5 * np.abs(np.diag(H)).max()
     x = np.linalg.solve(H + lam * np.eye(n), b)
     new_pts = pts + x[6 * len(free):].reshape(-1, 3)
-    assert r["trace"]["trials"][0] == 1
-    assert np.allclose(r["points_d"], new_pts, rtol=0, atol=1e-9)
+    new_cams = {}
     for c in free:
         out = np.zeros(7)
         L.orc_se3_oplus(cam7[c].ctypes.data, x[6 * cidx[c]:6 * cidx[c] + 6].copy().ctypes.data, out.ctypes.data)
-        assert np.allclose(r["cams_d"][c], out, rtol=0, atol=1e-10)
+        new_cams[c] = out
+    return new_pts, new_cams
+
+
+def check_schur_step_against_dense_step(oracle, p):
+    r = oracle.local_ba(p, its=(1, 0))
+    new_pts, new_cams = dense_lm_step(oracle.lib(), p)
+    assert r["trace"]["trials"][0] == 1
+    assert np.allclose(r["points_d"], new_pts, rtol=0, atol=1e-9)
+    for c, out in new_cams.items():
+        assert np.allclose(r["cams_d"][c], out, rtol=0, atol=1e-10), "camera %d" % c
+
+
+def test_schur_step_equals_full_dense_step(oracle):
+    """One LM step of the oracle (Schur) vs a numpy full (poses+points) dense solve built from the oracle's
+    own per-edge residuals/Jacobians: checks the reduction/back-substitution algebra."""
+    check_schur_step_against_dense_step(oracle, synth.synth_ba(n_free=3, n_fixed=1, n_points=40, outlier_frac=0.0))
 
 
 def test_pose_outlier_classification_consistent(oracle):
