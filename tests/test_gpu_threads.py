@@ -65,6 +65,62 @@ def test_concurrent_entry_points():
     assert not errors, errors
 
 
+def test_concurrent_sim3_threads_beside_pose_optimization():
+    """eao_optimize_sim3 keeps its stream, events and device / host staging buffers per host thread (thread_local in csrc/sim3.hip).  Four threads
+    each run their own slice of sim3_scenes.IRREGULAR twenty times -- sizes from 9 to 20000, so every thread's buffers grow and are reused --
+    while a fifth runs PoseOptimization; every result equals the serial one bit for bit.  One process holds the GPU throughout."""
+    import torch  # noqa: F401
+    import eao_fusion_amd as E
+    from eao_fusion_amd.optimizer import optimize_sim3
+    import sim3_scenes as SC
+    from sim3_child import result_bytes
+    assert E.load().eao_device_check() == 0
+    probs = [SC.irregular_scene(kw, edit) for _, kw, edit in SC.IRREGULAR]
+    slices = [list(range(i, len(probs), 4)) for i in range(4)]
+    pose = synth.synth_pose(n=500, seed=4100, n_planes=3)
+
+    def job_pose():
+        r = E.Optimizer.PoseOptimization(pose)
+        return r["Tcw"].tobytes() + r["outlier"].tobytes() + r["plane_outlier"].tobytes()
+
+    expect = [result_bytes(optimize_sim3(p)) for p in probs]
+    expect_pose = job_pose()
+    errors, running = [], [4]
+    lock = threading.Lock()
+
+    def sim3_worker(i):
+        try:
+            for rep in range(20):
+                order = slices[i] if rep % 2 == 0 else slices[i][::-1]
+                for k in order:
+                    if result_bytes(optimize_sim3(probs[k])) != expect[k]:
+                        errors.append("thread %d: IRREGULAR[%d] differs on repetition %d" % (i, k, rep))
+        except Exception as ex:  # noqa: BLE001
+            errors.append("thread %d: %r" % (i, ex))
+        finally:
+            with lock:
+                running[0] -= 1
+
+    pose_calls = [0]
+
+    def pose_worker():
+        try:
+            while running[0] > 0 or pose_calls[0] < 20:
+                if job_pose() != expect_pose:
+                    errors.append("PoseOptimization differs on call %d" % pose_calls[0])
+                pose_calls[0] += 1
+        except Exception as ex:  # noqa: BLE001
+            errors.append("pose thread: %r" % (ex,))
+
+    ths = [threading.Thread(target=sim3_worker, args=(i,)) for i in range(4)] + [threading.Thread(target=pose_worker)]
+    for t in ths:
+        t.start()
+    for t in ths:
+        t.join()
+    assert not errors, errors[:10]
+    assert pose_calls[0] >= 20
+
+
 def test_concurrent_map_scale_batch_and_handle_calls(monkeypatch):
     """Round 5's host-side machinery under concurrency: two threads run map-scale BundleAdjustment (their covisibility set-up is split over the ONE process-wide host
     crew, forced onto these test-size maps), one runs eao_local_ba_batch (which owns the same crew for its set-up workers and group leaders), one runs the keyframe-handle

@@ -19,9 +19,10 @@ def test_the_table_is_what_was_frozen_in_round_5():
 
 
 def test_gpu_lm_tests_carry_no_tolerance_of_their_own():
-    for fname in ("test_gpu_lm.py", "test_gpu_ba_shapes.py"):
+    for fname in ("test_gpu_lm.py", "test_gpu_ba_shapes.py", "test_gpu_sim3.py"):
         src = open(os.path.join(ROOT, "tests", fname)).read()
         code = "\n".join(ln.split("#")[0] for ln in src.splitlines() if not ln.lstrip().startswith(('"', "'")))
         assert not re.search(r"\b(rel|lam_rel|rtol)\s*=\s*[0-9]", code), "a literal tolerance in tests/%s: it belongs in tests/lm_tolerances.py" % fname
-    for name in ("profiles/r02_lm_trace_sensitivity.txt", "profiles/r02_lm_chaotic_seeds.txt", "profiles/r04_lm_seed3037.txt", "profiles/r05_sweeps.txt"):
+    for name in ("profiles/r02_lm_trace_sensitivity.txt", "profiles/r02_lm_chaotic_seeds.txt", "profiles/r04_lm_seed3037.txt", "profiles/r05_sweeps.txt",
+                 "profiles/sim3_irregular_bands.txt"):
         assert os.path.exists(os.path.join(ROOT, name)), "evidence file %s named by tests/lm_tolerances.py is missing" % name

@@ -203,9 +203,36 @@ def test_families_cover_the_cases():
     assert {kw["fix_scale"] for name, kw, o in outs if not o["early_exit"]} == {True, False}
 
 
-def test_iteration_unstable_table_matches_the_one_ulp_probe():
+def _update_norm(p, a):
+    return max(np.abs(a["q"] - p["q"]).max(), np.abs(a["t"] - p["t"]).max(), abs(a["s"] - p["s"]))
+
+
+def _displacement(a, b):
+    return max(np.abs(a["q"] - b["q"]).max(), np.abs(a["t"] - b["t"]).max(), abs(a["s"] - b["s"]))
+
+
+@pytest.fixture(scope="module")
+def irregular():
+    """Every IRREGULAR family through the yardstick, as generated and under ulp_perturbed seeds 0..3 (what tools/sim3_chaotic_seeds.py
+    --irregular logs): {id: (name, kw, problem, result, [results of the four one-ulp copies])}."""
+    out = {}
+    for (name, kw, edit), fid in zip(SC.IRREGULAR, SC.irregular_ids()):
+        p = SC.irregular_scene(kw, edit)
+        out[fid] = (name, kw, p, R.optimize_sim3(p), [R.optimize_sim3(SC.ulp_perturbed(p, s)) for s in range(4)])
+    assert len(out) == len(SC.IRREGULAR), "IRREGULAR ids are not unique"
+    return out
+
+
+def _only(irregular, name):
+    hits = [v for v in irregular.values() if v[0] == name]
+    assert len(hits) == 1, name
+    return hits[0][2], hits[0][3]
+
+
+def test_iteration_unstable_table_matches_the_one_ulp_probe(irregular):
     """sim3_scenes.ITERS_UNSTABLE lists exactly the families whose reference iteration counts move under a one-ulp change of the
-    observations, and on those only the counts move (the GPU test still compares everything else)."""
+    observations, and on those only the counts move (the GPU test still compares everything else).  Likewise IRREGULAR_ITERS_UNSTABLE and
+    IRREGULAR_BANDED over IRREGULAR and ulp_perturbed seeds 0..3 (profiles/sim3_irregular_bands.txt), within their caps."""
     found = set()
     for name, kw in SC.FAMILIES:
         p = SC.scene(**kw)
@@ -217,6 +244,119 @@ def test_iteration_unstable_table_matches_the_one_ulp_probe():
             disp = max(np.abs(a["q"] - b["q"]).max(), np.abs(a["t"] - b["t"]).max(), abs(a["s"] - b["s"]))
             assert disp <= 2e-5 * upd, (name, kw, disp / upd)
     assert found == SC.ITERS_UNSTABLE
+    from lm_tolerances import UPDATE_REL
+    unstable, banded = set(), set()
+    for fid, (name, kw, p, a, bs) in irregular.items():
+        if any(list(a["iters"]) != list(b["iters"]) for b in bs):
+            unstable.add(SC.family_key(name, kw))
+        upd = _update_norm(p, a)
+        if upd and max(_displacement(a, b) for b in bs) > UPDATE_REL * upd:
+            banded.add(SC.family_key(name, kw))
+    assert unstable == SC.IRREGULAR_ITERS_UNSTABLE and banded == SC.IRREGULAR_BANDED
+    assert len(banded) <= SC.IRREGULAR_BANDED_MAX == 1
+    early = {SC.family_key(name, kw) for name, kw, p, a, bs in irregular.values() if a["early_exit"]}
+    assert len(unstable - early) <= SC.IRREGULAR_ITERS_UNSTABLE_MAX == 3
+    assert all(_displacement(a, b) <= UPDATE_REL / 2 * _update_norm(p, a) for name, kw, p, a, bs in irregular.values() for b in bs
+               if name in ("scale_small", "scale_large"))      # the extreme-scale pair that is held to UPDATE_REL
+
+
+def test_irregular_schedules_hold_under_one_ulp(irregular):
+    """No IRREGULAR family's removed / n_inliers / early_exit moves when every observation moves by one ulp (seeds 0..3)."""
+    for fid, (name, kw, p, a, bs) in irregular.items():
+        for b in bs:
+            assert np.array_equal(a["removed"], b["removed"]) and a["n_inliers"] == b["n_inliers"] and a["early_exit"] == b["early_exit"], fid
+
+
+@pytest.mark.parametrize("which", [1, 2])
+def test_irregular_behind_camera_rows_are_behind_and_removed(irregular, which):
+    """The mirrored map points have z < 0 in their own camera frame as the library forms it, the edge that maps them divides by a negative
+    z at the start, and every one of them ends in removed."""
+    p, o = _only(irregular, "behind_cam%d" % which)
+    rows = p["planted_rows"]["behind%d" % which]
+    assert len(rows) >= 10
+    Xc = R.camera_points(p["T%dw" % which], p["Xw%d" % which])
+    assert (Xc[rows, 2] < 0).all() and (np.delete(Xc[:, 2], rows) > 0).all()
+    S0 = R.Sim3(p["q"], p["t"], p["s"])
+    mapped = S0.map(Xc) if which == 2 else S0.inverse().map(Xc)      # camera-2 points go through S12 (the direct edge), camera-1 points through S21
+    assert (mapped[rows, 2] < 0).all()
+    assert not o["early_exit"] and o["removed"][rows].all()
+    assert {kw["fix_scale"] for name, kw, *_ in irregular.values() if name.startswith("behind_cam")} == {True, False}
+
+
+def test_irregular_ten_and_nine_survivors(irregular):
+    """The nCorr - nBad < 10 gate from both sides: exactly 10 survivors go on, exactly 9 return early; with and without removals."""
+    for name, survivors, early in (("ten_survive", 10, False), ("nine_survive", 9, True), ("ten_clean", 10, False), ("nine_clean", 9, True)):
+        p, o = _only(irregular, name)
+        n = len(p["Xw1"])
+        assert n - int(o["removed"].sum()) == survivors and bool(o["early_exit"]) == early, name
+        planted = p.get("planted_rows", {}).get("gross", np.zeros(0, np.int64))
+        assert np.array_equal(np.nonzero(o["removed"])[0], planted), name
+        assert o["n_inliers"] == (0 if early else 10) and o["budget"] == ((5, 0) if early else (5, 10) if len(planted) else (5, 5)), name
+
+
+def test_irregular_strided_removes_exactly_the_planted_rows(irregular):
+    p, o = _only(irregular, "strided")
+    rows = p["planted_rows"]["gross"]
+    m = np.arange(len(p["Xw1"]))
+    assert np.array_equal(rows, m[(m % 256 == 7) | ((m >= 64) & (m < 128))]) and len(rows) == 70     # one thread's stride and one whole wave
+    assert np.array_equal(np.nonzero(o["removed"])[0], rows) and not o["early_exit"]
+
+
+def test_irregular_zero_information_rows_are_never_removed(irregular):
+    p, o = _only(irregular, "zero_info")
+    rows = p["planted_rows"]["zero_info"]
+    assert len(rows) >= 10 and not p["inv_sigma2_1"][rows].any() and not p["inv_sigma2_2"][rows].any()
+    assert (p["inv_sigma2_1"] == 0).sum() >= 40 and (p["inv_sigma2_2"] == 0).sum() >= 40
+    assert not o["removed"][rows].any() and o["removed"].sum() > 0
+    # ... although some of them are gross: with the smallest information any pyramid level carries, the gate would have removed them
+    E = R.Edges(p)
+    hit = np.intersect1d(rows, p["planted_rows"]["gross"])
+    e12, _ = R.errors(E, R.Sim3(o["q"], o["t"], o["s"]), hit)
+    assert len(hit) >= 3 and (R.chi2(e12, np.full(len(hit), 1.0 / 1.2 ** 14)) > E.th2).all()
+
+
+def test_irregular_families_are_what_they_are_named_for(irregular):
+    by_name = {}
+    for name, kw, p, o, bs in irregular.values():
+        by_name.setdefault(name, []).append((kw, p, o))
+    # near-zero depth: the collapse returns early, the milder one does not; both really moved the points
+    for name, z, early in (("depth_collapse", 1e-4, True), ("depth_near", 0.1, False)):
+        (kw, p, o), = by_name[name]
+        rows = p["planted_rows"]["depth1"]
+        assert np.abs(R.camera_points(p["T1w"], p["Xw1"])[rows, 2] - z).max() < 1e-5 and len(rows) == 4 and bool(o["early_exit"]) == early, name
+    # the second optimize() of a pass that removed nothing gets 5 iterations, uses all of them, and would go on with 10
+    (kw, p, o), = by_name["budget_five"]
+    assert o["budget"] == (5, 5) and list(o["iters"]) == [5, 5] and not o["removed"].any()
+    E, idx = R.Edges(p), np.arange(len(p["Xw1"]))
+    S, _, _ = R.lm_optimize(E, R.Sim3(p["q"], p["t"], p["s"]), idx, 5, [])
+    assert R.lm_optimize(E, S, idx, 10, [])[1] > 5
+    # extreme scales, planted and kept
+    for name, s in (("scale_small", 0.05), ("scale_large", 20.0), ("scale_large_banded", 20.0)):
+        (kw, p, o), = by_name[name]
+        assert p["planted"]["s"] == s and not p["fix_scale"] and abs(o["s"] / s - 1) < 0.02, name
+    for name in ("all_outliers", "far_start_lost"):
+        for kw, p, o in by_name[name]:
+            assert o["early_exit"] and o["removed"].sum() >= len(p["Xw1"]) - 9, name
+    assert {kw["fix_scale"] for kw, p, o in by_name["far_start_lost"]} == {True, False}
+    # a far start that survives, through rejected trials
+    (kw, p, o), = by_name["far_start"]
+    assert not o["early_exit"] and max(t[2] for t in o["trace"]) >= 3
+    # Huber widths whose float square root does not square back to th2
+    for name, th2 in (("th2_narrow", 2.0), ("th2_wide", 40.0)):
+        (kw, p, o), = by_name[name]
+        E = R.Edges(p)
+        assert E.th2 == th2 and E.delta * E.delta != th2 and not o["early_exit"], name
+    (kw, p, o), = by_name["non_unit_q"]
+    assert abs(np.linalg.norm(p["q"]) - 1.003) < 1e-12 and not o["early_exit"]
+    (kw, p, o), = by_name["duplicates"]
+    rows = p["planted_rows"]["duplicates"]
+    assert len(rows) == 50 and all((p[k][rows] == p[k][7]).all() for k in ("Xw1", "Xw2", "obs1", "obs2", "inv_sigma2_1", "inv_sigma2_2"))
+    assert len(set(o["removed"][rows])) == 1
+    # wave and workgroup edges, and far above one stride
+    assert [kw["n"] for kw, p, o in by_name["edge_n"]] == [63, 64, 65, 255, 256, 257, 513, 1025]
+    assert all(not o["early_exit"] and o["removed"].any() for kw, p, o in by_name["edge_n"])
+    (kw, p, o), = by_name["large"]
+    assert len(p["Xw1"]) == 20000 and not o["early_exit"]
 
 
 # ---------------------------------------------------------------------- the class surface's walk

@@ -1,7 +1,7 @@
 """Writes tests/golden/sim3/sim3_*.npz (a directory of its own: tests/test_golden.py owns the top level of tests/golden): hand-sized OptimizeSim3 problems solved by the numpy restatement tests/sim3_reference.py --
 inputs, the LM trace of both optimize() calls (lambda, robust chi2, trials per iteration) and the outputs.
 
-    python tools/gen_golden_sim3.py
+    python tools/gen_golden_sim3.py [name ...]          (all of them, or only the named ones)
 """
 import os
 import sys
@@ -19,11 +19,23 @@ CASES = {
     "sim3_mono_60": dict(n=60, seed=1202, fix_scale=False, outlier_frac=0.1),
     "sim3_early_exit_12": dict(n=12, seed=1203, fix_scale=True, outlier_frac=0.6),
 }
+# ... and three of sim3_scenes.IRREGULAR, by family name: map points behind camera 2, exactly ten survivors of the first inlier pass,
+# edges with zero information
+IRREGULAR_CASES = {"sim3_behind_camera_200": "behind_cam2", "sim3_ten_survive_15": "ten_survive", "sim3_zero_info_200": "zero_info"}
+
+
+def problems(only):
+    for name, kw in CASES.items():
+        if not only or name in only:
+            yield name, SC.scene(**kw)
+    for name, family in IRREGULAR_CASES.items():
+        if not only or name in only:
+            (kw, edit), = [(kw, edit) for f, kw, edit in SC.IRREGULAR if f == family]
+            yield name, SC.irregular_scene(kw, edit)
 
 
 def main():
-    for name, kw in CASES.items():
-        p = SC.scene(**kw)
+    for name, p in problems(sys.argv[1:]):
         o = R.optimize_sim3(p)
         tr = np.array(o["trace"], np.float64).reshape(-1, 3)
         np.savez_compressed(os.path.join(ROOT, "tests", "golden", "sim3", name + ".npz"),
