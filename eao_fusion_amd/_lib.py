@@ -84,6 +84,16 @@ class Sim3Result(C.Structure):   # eao_sim3_result
                 ("n_inliers", C.c_int32), ("lm_iterations", C.c_int32 * 2), ("early_exit", C.c_int32)]
 
 
+class EssentialGraphProblem(C.Structure):   # eao_essential_graph_problem
+    _fields_ = [("n", C.c_int32), ("fixed", C.c_int32), ("fix_scale", C.c_int32), ("Scw", C.c_void_p), ("has_nc", C.c_void_p), ("Snc", C.c_void_p),
+                ("n_edges", C.c_int32), ("edges", C.c_void_p), ("n_points", C.c_int32), ("Xw", C.c_void_p), ("ref", C.c_void_p)]
+
+
+class EssentialGraphResult(C.Structure):   # eao_essential_graph_result
+    _fields_ = [("Scw", C.c_void_p), ("Tiw", C.c_void_p), ("Xw_corrected", C.c_void_p), ("lm_iterations", C.c_int32), ("trials", C.c_int32 * 20),
+                ("lambda_", C.c_double * 20), ("chi2", C.c_double * 20), ("chi2_initial", C.c_double), ("n_active", C.c_int32)]
+
+
 # every symbol include/eao_fusion.h declares: (restype, argtypes)
 _P = C.c_void_p
 _I = C.c_int32
@@ -143,6 +153,8 @@ SYMBOLS = {
     "eao_last_lm_timing": (_I, [C.POINTER(C.c_float), C.POINTER(_I)]),
     "eao_optimize_sim3": (_I, [C.POINTER(Sim3Problem), C.POINTER(Sim3Result)]),
     "eao_optimize_sim3_batch": (_I, [C.POINTER(Sim3Problem), _I, C.POINTER(Sim3Result)]),
+    "eao_optimize_essential_graph": (_I, [C.POINTER(EssentialGraphProblem), C.POINTER(EssentialGraphResult)]),
+    "eao_essential_graph_plan": (_I, [C.POINTER(EssentialGraphProblem), _P, _P, _P, _I]),
     "eao_bundle_adjustment_plan": (_I, [_I, _I, _P, _P, _I, _P, _P, _P, _I, _P, _I, _P, _I, _P, _I, _P, _I, _P, _I]),
 }
 

@@ -25,14 +25,6 @@ namespace {
 //                          it on the spot (32 steps, one barrier each), off the critical path of the other tiles.
 //   solve    k_bal_backsolve: L^T x = z bottom-up in super-blocks of 256 columns, one launch each (see there), then exp(dx) * T.
 // A zero or non-finite pivot fails the trial like SimplicialLDLT (`bigFail`).
-// (every tile live -- a map in which every keyframe sees every other one: the slots are the row-major numbering of the lower triangle, no table look-up)
-__device__ __forceinline__ int big_slot(const BADev& P, int ti, int tj) { return P.bigDense ? ti * (ti + 1) / 2 + tj : P.bigTile[ti * P.bigT + tj]; }
-__device__ __forceinline__ double* big_tile(double* pool, int slot) { return pool + ((size_t)slot << 12); }
-// element (r, c), c <= r, of a pool; the caller knows the tile exists
-__device__ __forceinline__ double* big_elem(const BADev& P, double* pool, int r, int c) {
-    return big_tile(pool, big_slot(P, r >> 6, c >> 6)) + ((r & 63) << 6) + (c & 63);
-}
-
 // Round 5: ONE WAVEFRONT per pair, FOUR for the long ones (rounds 3-4 ran 512 threads per pair: 192 VGPRs each, so ONE workgroup per CU, and a block-wide reduction
 // of 42 values per pair -- 90 us for the 1 593 pairs of the 200-keyframe benchmark map, six rounds of workgroups).  A pair's entries are a latency chain -- landmark
 // index -> edge flags -> three blocks -- of ~4 us per 64 of them: a covisible pair shares tens to a few hundred landmarks, a DIAGONAL pair carries every landmark its
@@ -699,11 +691,12 @@ struct PlanGraph {      // what every candidate order of one pattern shares
     Csr g;
     std::vector<int> line, pos, lo, hi;
 };
-void plan_for(const PlanGraph& G, const std::vector<int>& prA, const std::vector<int>& prB, int wantP, GbaPlan& pl);
+void plan_for(const PlanGraph& G, const std::vector<int>& prA, const std::vector<int>& prB, int wantP, GbaPlan& pl, int bw);
 }  // namespace
 
 // forceP: 0 = choose, 1 = natural order, p > 1 = that many segments (the callers read EAO_BA_ND for it)
-void gba_build_plan(int nFa, const std::vector<int>& prA, const std::vector<int>& prB, int forceP, GbaPlan& pl) {
+// bw: unknowns per vertex block (6: the SE3 keyframes of the bundle adjustment; 7: the Sim3 vertices of the essential graph)
+void gba_build_plan(int nFa, const std::vector<int>& prA, const std::vector<int>& prB, int forceP, GbaPlan& pl, int bw) {
     // ---- the lines the keyframes can be laid out on: their natural order, and reverse Cuthill-McKee when that narrows the band.  A loop that closes on itself (the
     //      last keyframes see the first) is the case where the wider line wins: on the natural line only the first few keyframes reach across every cut (they join the
     //      separators once), while RCM folds the ring and doubles the band at every cut -- so both lines are tried and the plans decide.
@@ -731,33 +724,33 @@ void gba_build_plan(int nFa, const std::vector<int>& prA, const std::vector<int>
         G[1].bandwidth = plan_bandwidth(nFa, G[1].g, G[1].pos);
         if (G[1].bandwidth * 5 < G[0].bandwidth * 4) { reach(G[1]); nLines = 2; }
     }
-    plan_for(G[0], prA, prB, 1, pl);
+    plan_for(G[0], prA, prB, 1, pl, bw);
     const int natural = (int)pl.launches.size();
     auto cost = [](const GbaPlan& q) { return (long long)(q.launches.size() + q.sbLaunches.size()) * 100000 + (long long)(q.work.size() / 2); };
     GbaPlan cand;
     if (forceP > 1) {
         const int P = std::min(forceP, std::max(1, nFa / 2));
-        plan_for(G[0], prA, prB, P, pl);
-        if (nLines == 2) { plan_for(G[1], prA, prB, P, cand); if (cost(cand) < cost(pl)) std::swap(pl, cand); }
+        plan_for(G[0], prA, prB, P, pl, bw);
+        if (nLines == 2) { plan_for(G[1], prA, prB, P, cand, bw); if (cost(cand) < cost(pl)) std::swap(pl, cand); }
     } else if (forceP == 0 && nFa >= 96) {
         // the schedule itself is the estimate: a plan costs a fraction of a millisecond (0.23 ms at 1000 keyframes), so a handful of segment counts are built and
         // the one with the fewest dependent launches -- factorisation + back substitution -- is kept (ties: fewer work records)
         for (int li = 0; li < nLines; li++)
             for (int P : {4, 6, 8, 12, 16, 24, 32, 48}) {
                 if (nFa / P < 8) break;
-                plan_for(G[li], prA, prB, P, cand);
+                plan_for(G[li], prA, prB, P, cand, bw);
                 if (cost(cand) < cost(pl)) std::swap(pl, cand);
             }
-        if (pl.P > 1 && (pl.launches.size() + pl.sbLaunches.size()) * 10 > (size_t)(natural + (pl.N + kBigSB - 1) / kBigSB) * 7) plan_for(G[0], prA, prB, 1, pl);      // (less than 30 % shorter: not worth the padding and the fill)
+        if (pl.P > 1 && (pl.launches.size() + pl.sbLaunches.size()) * 10 > (size_t)(natural + (pl.N + kBigSB - 1) / kBigSB) * 7) plan_for(G[0], prA, prB, 1, pl, bw);      // (less than 30 % shorter: not worth the padding and the fill)
     } else if (nLines == 2) {      // natural order asked for, or a small map: the narrower line as before
-        plan_for(G[1], prA, prB, 1, cand);
+        plan_for(G[1], prA, prB, 1, cand, bw);
         if (forceP != 1 && cost(cand) < cost(pl)) std::swap(pl, cand);
     }
     pl.chainNatural = natural;
 }
 
 namespace {
-void plan_for(const PlanGraph& G, const std::vector<int>& prA, const std::vector<int>& prB, int wantP, GbaPlan& pl) {
+void plan_for(const PlanGraph& G, const std::vector<int>& prA, const std::vector<int>& prB, int wantP, GbaPlan& pl, int bw) {
     pl = GbaPlan();
     const int nFa = G.nFa;
     pl.nFa = nFa; pl.rcm = G.rcm; pl.bandwidth = G.bandwidth;
@@ -801,7 +794,7 @@ void plan_for(const PlanGraph& G, const std::vector<int>& prA, const std::vector
             const int v = line[p];
             if (sep[v]) continue;
             if (!open) { row = up64(row); pl.segStart.push_back(row); open = true; }
-            pl.rowOf[v] = row; row += 6;
+            pl.rowOf[v] = row; row += bw;
         }
     }
     row = up64(row);
@@ -814,12 +807,12 @@ void plan_for(const PlanGraph& G, const std::vector<int>& prA, const std::vector
         for (int gq = step; gq <= (int)cut.size(); gq += 2 * step) gorder.push_back(gq);
     for (int gq : gorder) {
         row = up64(row);
-        for (int p = 0; p < nFa; p++) { const int v = line[p]; if (sep[v] == gq) { pl.rowOf[v] = row; row += 6; } }
+        for (int p = 0; p < nFa; p++) { const int v = line[p]; if (sep[v] == gq) { pl.rowOf[v] = row; row += bw; } }
     }
     pl.N = std::max(64, up64(row));
     pl.segStart.push_back(pl.sepStart);      // (sentinel: segment s spans rows [segStart[s], segStart[s + 1]))
     pl.rowCam.assign((size_t)pl.N, -1);
-    for (int v = 0; v < nFa; v++) for (int q = 0; q < 6; q++) pl.rowCam[pl.rowOf[v] + q] = v * 6 + q;
+    for (int v = 0; v < nFa; v++) for (int q = 0; q < bw; q++) pl.rowCam[pl.rowOf[v] + q] = v * bw + q;
     const int N = pl.N, tN = N >> 6, T = tN + 1;
     pl.T = T; pl.RP = T * 64;
     // ---- live tiles + fill-in
@@ -827,7 +820,7 @@ void plan_for(const PlanGraph& G, const std::vector<int>& prA, const std::vector
     auto mark = [&](int r, int c) { const int a = r >> 6, b = c >> 6; live[(size_t)std::max(a, b) * T + std::min(a, b)] = 1; };
     for (size_t k = 0; k < prA.size(); k++) {
         const int ra = pl.rowOf[prA[k]], rb = pl.rowOf[prB[k]];
-        mark(ra, rb); mark(ra + 5, rb); mark(ra, rb + 5); mark(ra + 5, rb + 5);
+        mark(ra, rb); mark(ra + bw - 1, rb); mark(ra, rb + bw - 1); mark(ra + bw - 1, rb + bw - 1);
     }
     for (int t = 0; t < T; t++) live[(size_t)t * T + t] = 1;
     for (int t = 0; t <= tN; t++) live[(size_t)tN * T + t] = 1;
@@ -962,6 +955,22 @@ eao_status gba_attributes() {
 void gba_enqueue_pair_fill(const BALaunch& L) {
     if (L.d.nPairsNZ > 0) hipLaunchKernelGGL(k_bal_pair_fill, dim3(eao::cdiv(L.d.nPairsNZ, 4), 1, 1), dim3(256), 0, L.s, L.W, L.wp(0));
 }
+// The factor chain on an assembled system (working tiles, right-hand side row, identity padding in place): the panel factorisation, the inverses of the diagonal
+// blocks and the back substitution; x lands in W's xp in the vertices' natural order.  Shared by the bundle adjustment's trial and the essential graph (essential_graph.hip).
+void gba_enqueue_factor_solve(const BADev* W, int wpar, const GbaPlan& pl, BigStepArgs A, hipStream_t s) {
+    // the factorisation: one launch per level of the schedule (GbaPlan::launches) -- the panels of independent segments side by side
+    for (const GbaPlan::Launch& Lq : pl.launches) {
+        if (Lq.diagCnt) hipLaunchKernelGGL(k_bal_diag, dim3(Lq.diagCnt), dim3(64), 0, s, W, wpar, Lq.diagOff);
+        if (Lq.cnt) {
+            A.nByValue = std::min(Lq.cnt, kBigByValue);
+            std::memcpy(A.rec, pl.work.data() + 2 * (size_t)Lq.off, (size_t)A.nByValue * 2 * sizeof(int4));
+            hipLaunchKernelGGL(k_bal_step, dim3(Lq.cnt), dim3(256), 0, s, A, Lq.off);
+        }
+    }
+    hipLaunchKernelGGL(k_bal_linv, dim3(eao::cdiv(pl.nbk, 2)), dim3(64), 0, s, W, wpar, pl.nbk);
+    for (const GbaPlan::SbLaunch& Sq : pl.sbLaunches)
+        hipLaunchKernelGGL(k_bal_backsolve, dim3(Sq.maxChunks, Sq.cnt), dim3(256), (kBigSB / kBigNB) * kBigNB * kBigNB * sizeof(double), s, W, wpar, Sq.off);
+}
 void gba_enqueue_trial(const BALaunch& L, int par, bool firstTrial) {
     const BADims& d = L.d;
     const BADev* W = L.W;
@@ -973,18 +982,7 @@ void gba_enqueue_trial(const BALaunch& L, int par, bool firstTrial) {
     if (d.nPairsSlots > d.nPairsLong) hipLaunchKernelGGL(k_bal_schur_pairs<64>, dim3(d.nPairsSlots - d.nPairsLong), dim3(64), 0, s, W, wp(par), firstTrial ? 1 : 0, d.nPairsLong);
     BigStepArgs A = d.bigArgs;
     A.ctl = d.bigCtl0 + 8 * (par & 1);
-    // the factorisation: one launch per level of the schedule (GbaPlan::launches) -- the panels of independent segments side by side
-    for (const GbaPlan::Launch& Lq : pl.launches) {
-        if (Lq.diagCnt) hipLaunchKernelGGL(k_bal_diag, dim3(Lq.diagCnt), dim3(64), 0, s, W, wp(par), Lq.diagOff);
-        if (Lq.cnt) {
-            A.nByValue = std::min(Lq.cnt, kBigByValue);
-            std::memcpy(A.rec, pl.work.data() + 2 * (size_t)Lq.off, (size_t)A.nByValue * 2 * sizeof(int4));
-            hipLaunchKernelGGL(k_bal_step, dim3(Lq.cnt), dim3(256), 0, s, A, Lq.off);
-        }
-    }
-    hipLaunchKernelGGL(k_bal_linv, dim3(eao::cdiv(pl.nbk, 2)), dim3(64), 0, s, W, wp(par), pl.nbk);
-    for (const GbaPlan::SbLaunch& Sq : pl.sbLaunches)
-        hipLaunchKernelGGL(k_bal_backsolve, dim3(Sq.maxChunks, Sq.cnt), dim3(256), (kBigSB / kBigNB) * kBigNB * kBigNB * sizeof(double), s, W, wp(par), Sq.off);
+    gba_enqueue_factor_solve(W, wp(par), pl, A, s);
     hipLaunchKernelGGL(k_bal_apply, dim3(eao::cdiv(std::max(d.nC, 1), 256)), dim3(256), 0, s, W, wp(par));
 }
 }  // namespace lm

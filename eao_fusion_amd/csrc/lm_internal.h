@@ -232,7 +232,7 @@ struct GbaPlan {
     std::vector<SbLaunch> sbLaunches;
 };
 uint64_t gba_pattern_hash(int nFa, const std::vector<int>& prA, const std::vector<int>& prB);
-void gba_build_plan(int nFa, const std::vector<int>& prA, const std::vector<int>& prB, int forceP, GbaPlan& pl);
+void gba_build_plan(int nFa, const std::vector<int>& prA, const std::vector<int>& prB, int forceP, GbaPlan& pl, int bw = 6);
 
 struct LMTraceHost {
     std::vector<double> lambda, chi2;
@@ -332,6 +332,7 @@ struct BALaunch {      // (member functions: lba.hip -- they launch its kernels;
 eao_status gba_attributes();
 void gba_enqueue_trial(const BALaunch& L, int par, bool firstTrial);
 void gba_enqueue_pair_fill(const BALaunch& L);
+void gba_enqueue_factor_solve(const BADev* W, int wpar, const GbaPlan& pl, BigStepArgs A, hipStream_t s);
 
 }  // namespace lm
 }  // namespace eao
@@ -747,6 +748,15 @@ __device__ inline void dinv3(const double* Hll, double lambda, double Di[9]) {
     Di[0] = c00 * id; Di[1] = (A[2] * A[7] - A[1] * A[8]) * id; Di[2] = (A[1] * A[5] - A[2] * A[4]) * id;
     Di[3] = c01 * id; Di[4] = (A[0] * A[8] - A[2] * A[6]) * id; Di[5] = (A[2] * A[3] - A[0] * A[5]) * id;
     Di[6] = c02 * id; Di[7] = (A[1] * A[6] - A[0] * A[7]) * id; Di[8] = (A[0] * A[4] - A[1] * A[3]) * id;
+}
+
+// ---- the tile pools of the map-scale path (gba.hip; essential_graph.hip assembles its 7-wide system into the same layout)
+// (every tile live -- a map in which every keyframe sees every other one: the slots are the row-major numbering of the lower triangle, no table look-up)
+__device__ __forceinline__ int big_slot(const BADev& P, int ti, int tj) { return P.bigDense ? ti * (ti + 1) / 2 + tj : P.bigTile[ti * P.bigT + tj]; }
+__device__ __forceinline__ double* big_tile(double* pool, int slot) { return pool + ((size_t)slot << 12); }
+// element (r, c), c <= r, of a pool; the caller knows the tile exists
+__device__ __forceinline__ double* big_elem(const BADev& P, double* pool, int r, int c) {
+    return big_tile(pool, big_slot(P, r >> 6, c >> 6)) + ((r & 63) << 6) + (c & 63);
 }
 
 typedef double v4d __attribute__((ext_vector_type(4)));

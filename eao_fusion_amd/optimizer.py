@@ -244,3 +244,45 @@ def optimize_sim3_batch(probs, packed=None):
         o["timing"] = tm
         outs.append(o)
     return outs
+
+
+# ---------------------------------------------------------------------- Optimizer::OptimizeEssentialGraph (src/Optimizer.cc:1141-1435)
+def _pack_essential_graph(prob):
+    n = int(prob["n"])
+    keep = dict(Scw=np.ascontiguousarray(prob["Scw"], np.float64).reshape(-1, 8), Snc=np.ascontiguousarray(prob["Snc"], np.float64).reshape(-1, 8),
+                has=np.ascontiguousarray(prob["has_nc"], np.uint8), edges=np.ascontiguousarray(prob["edges"], np.int32).reshape(-1, 3),
+                Xw=np.ascontiguousarray(prob["Xw"], np.float32).reshape(-1, 3), ref=np.ascontiguousarray(prob["ref"], np.int32))
+    assert len(keep["Scw"]) == n and len(keep["Snc"]) == n and len(keep["has"]) == n and len(keep["ref"]) == len(keep["Xw"])
+    P = _lib.EssentialGraphProblem(n, int(prob["fixed"]), 1 if prob["fix_scale"] else 0, _lib.ptr(keep["Scw"]), _lib.ptr(keep["has"]), _lib.ptr(keep["Snc"]),
+                                   len(keep["edges"]), _lib.ptr(keep["edges"]), len(keep["Xw"]), _lib.ptr(keep["Xw"]), _lib.ptr(keep["ref"]))
+    return P, keep, n
+
+
+def optimize_essential_graph(prob):
+    """Optimizer::OptimizeEssentialGraph of one flattened pose graph (eao_optimize_essential_graph).  prob: n, fixed, fix_scale, Scw (n, 8) f64
+    (q in x, y, z, w order, t, s), has_nc (n,) u8, Snc (n, 8) f64, edges (m, 3) i32 (i, j, kind), Xw (p, 3) f32, ref (p,) i32.  Returns dict(Scw, Tiw
+    (n, 16) f32, Xw_corrected (p, 3) f32, lm_iterations, trials / lambda / chi2 per iteration, chi2_initial, n_active, timing)."""
+    P, keep, n = _pack_essential_graph(prob)
+    npts = len(keep["Xw"])
+    oS, oT, oX = np.zeros((max(n, 1), 8)), np.zeros((max(n, 1), 16), np.float32), np.zeros((max(npts, 1), 3), np.float32)
+    R = _lib.EssentialGraphResult()
+    R.Scw, R.Tiw, R.Xw_corrected = _lib.ptr(oS), _lib.ptr(oT), _lib.ptr(oX)
+    _lib.check(_lib.load().eao_optimize_essential_graph(C.byref(P), C.byref(R)))
+    its = int(R.lm_iterations)
+    return {"Scw": oS[:n], "Tiw": oT[:n], "Xw_corrected": oX[:npts], "lm_iterations": its, "trials": np.array(R.trials[:its], np.int32),
+            "lambda": np.array(R.lambda_[:its]), "chi2": np.array(R.chi2[:its]), "chi2_initial": float(R.chi2_initial), "n_active": int(R.n_active),
+            "timing": _timing()}
+
+
+def essential_graph_plan(prob):
+    """The elimination plan of a pose graph (eao_essential_graph_plan; needs no device): dict(rows, tile_rows, tiles, segments, separators, launches,
+    row_of (n,), tile_map (T, T))."""
+    P, keep, n = _pack_essential_graph(prob)
+    info = (C.c_int32 * 17)()
+    row_of = np.zeros(max(n, 1), np.int32)
+    _lib.check(_lib.load().eao_essential_graph_plan(C.byref(P), info, _lib.ptr(row_of), None, 0))
+    T = int(info[2])
+    tile_map = np.zeros((T, T), np.int32)
+    _lib.check(_lib.load().eao_essential_graph_plan(C.byref(P), info, _lib.ptr(row_of), _lib.ptr(tile_map), T * T))
+    return dict(rows=int(info[1]), tile_rows=T, tiles=int(info[4]), segments=int(info[5]), separators=int(info[6]), launches=int(info[12]) + int(info[16]),
+                row_of=row_of[:n], tile_map=tile_map)

@@ -734,6 +734,52 @@ eao_status eao_optimize_sim3(const eao_sim3_problem* p, eao_sim3_result* r);
  * candidates at once.  results[i] is bit-identical to what eao_optimize_sim3(&problems[i], &results[i]) returns. */
 eao_status eao_optimize_sim3_batch(const eao_sim3_problem* problems, int32_t n, eao_sim3_result* results);
 
+/* ------------------------------------------------------------------------------------------------
+ * Optimizer::OptimizeEssentialGraph(pMap, pLoopKF, pCurKF, NonCorrectedSim3, CorrectedSim3, LoopConnections, bFixScale) -- reference
+ * include/Optimizer.h, src/Optimizer.cc:1141-1435: the Sim3 pose graph of LoopClosing::CorrectLoop (g2o: types/types_seven_dof_expmap.h:48-126,
+ * types/sim3.h:70-230, core/base_binary_edge.hpp:147-196, core/optimization_algorithm_levenberg.cpp:61-189 with lambda0 = 1e-16,
+ * solvers/linear_solver_eigen.h:95-125).  Keyframes carry a dense index 0 .. n-1 (the adapter compacts mnId).  A Sim3 is 8 doubles: the
+ * rotation's coefficients in Eigen's order x, y, z, w, the translation, the scale.
+ * ------------------------------------------------------------------------------------------------ */
+typedef struct {
+    int32_t n;                  /* keyframes that got a vertex (not isBad()) */
+    int32_t fixed;              /* index of pLoopKF: the fixed vertex */
+    int32_t fix_scale;          /* bFixScale: VertexSim3Expmap::_fix_scale */
+    const double* Scw;          /* n*8: vScw -- CorrectedSim3 where the keyframe is in that map, else (GetRotation(), GetTranslation(), 1) */
+    const uint8_t* has_nc;      /* n: 1 where the keyframe is in NonCorrectedSim3 */
+    const double* Snc;          /* n*8: NonCorrectedSim3 (read where has_nc) */
+    int32_t n_edges;
+    const int32_t* edges;       /* n_edges*3: (i, j, kind), vertex 0 of the edge is i and vertex 1 is j, in the order upstream adds them.
+                                 * kind 0 = loop connection: measurement vScw[j] * vScw[i]^-1; kind 1 = spanning tree / loop edge / covisibility:
+                                 * the same with NonCorrectedSim3 in place of vScw where has_nc.  Duplicates all count. */
+    int32_t n_points;
+    const float* Xw;            /* n_points*3: GetWorldPos() of the good map points */
+    const int32_t* ref;         /* n_points: index of the keyframe a point is corrected through (src/Optimizer.cc:1381-1390); -1: none, the point
+                                 * comes back as it is */
+} eao_essential_graph_problem;
+
+typedef struct {
+    double* Scw;                /* n*8 (caller-allocated): the optimised vertices; the fixed one and those without an edge bit-equal to the input */
+    float* Tiw;                 /* n*16: toRotationMatrix() of the quaternion, t * (1 / s), rounded once to float (row-major 4x4) */
+    float* Xw_corrected;        /* n_points*3: correctedSwr.map(Srw.map(X)) in double, rounded once to float */
+    int32_t lm_iterations;      /* outer LM iterations of optimize(20) */
+    int32_t trials[20];         /* per iteration: the trials it took, */
+    double lambda[20];          /*   lambda as the iteration left it, */
+    double chi2[20];            /*   chi2 of the estimate it ended with */
+    double chi2_initial;
+    int32_t n_active;           /* vertices with at least one edge (initializeOptimization() activates no other) */
+} eao_essential_graph_result;
+
+/* At most 8192 free keyframes with an edge (the capacity of eao_bundle_adjustment's map-scale solver, whose factor chain this runs on).
+ * Non-finite input, `fixed` or an edge index out of range and an edge with i == j fail with EAO_ERR_INVALID before anything is written.
+ * Two calls on the same problem return the same bytes. */
+eao_status eao_optimize_essential_graph(const eao_essential_graph_problem* p, eao_essential_graph_result* r);
+
+/* The elimination plan eao_optimize_essential_graph would solve this problem on (host only, no device needed; the same argument checks): the solver's
+ * figures, row_of[n] = first of a keyframe's seven rows in the elimination order (-1: fixed or without an edge), tile_map[T * T] = slot of each 64 x 64 tile
+ * of the lower triangle or -1 (copied when cap_tile_map is large enough; row_of and tile_map may be NULL). */
+eao_status eao_essential_graph_plan(const eao_essential_graph_problem* p, eao_gba_plan_info* info, int32_t* row_of, int32_t* tile_map, int32_t cap_tile_map);
+
 /* The value of EAO_ABI_VERSION the library was built with.  Bumped whenever an entry point's parameter list or a struct's layout changes (round 3
  * changed eao_tracker_track_local_map and eao_track_result in place); a caller compiled against another version must not call into the library.
  * Result structs are zero-initialised by the caller (`eao_track_result R = {0};`) before their array pointers are set: a pointer member the
