@@ -84,6 +84,23 @@ class Sim3Result(C.Structure):   # eao_sim3_result
                 ("n_inliers", C.c_int32), ("lm_iterations", C.c_int32 * 2), ("early_exit", C.c_int32)]
 
 
+class Sim3SolverProblem(C.Structure):   # eao_sim3_solver_problem
+    _fields_ = [("n", C.c_int32), ("T1w", C.c_void_p), ("T2w", C.c_void_p), ("Xw1", C.c_void_p), ("Xw2", C.c_void_p),
+                ("sigma2_1", C.c_void_p), ("sigma2_2", C.c_void_p),
+                ("fx1", C.c_float), ("fy1", C.c_float), ("cx1", C.c_float), ("cy1", C.c_float),
+                ("fx2", C.c_float), ("fy2", C.c_float), ("cx2", C.c_float), ("cy2", C.c_float), ("fix_scale", C.c_int32)]
+
+
+class Sim3SolverState(C.Structure):   # eao_sim3_solver_state
+    _fields_ = [("iterations", C.c_int32), ("best_inliers", C.c_int32), ("best_T12", C.c_float * 16), ("best_R", C.c_float * 9),
+                ("best_t", C.c_float * 3), ("best_s", C.c_float)]
+
+
+class Sim3SolverResult(C.Structure):   # eao_sim3_solver_result
+    _fields_ = [("returned", C.c_int32), ("n_inliers", C.c_int32), ("T12", C.c_float * 16), ("inlier", C.c_void_p), ("no_more", C.c_int32),
+                ("hyp_inliers", C.c_void_p), ("hyp_T12", C.c_void_p), ("hyp_T21", C.c_void_p), ("hyp_inlier", C.c_void_p)]
+
+
 class EssentialGraphProblem(C.Structure):   # eao_essential_graph_problem
     _fields_ = [("n", C.c_int32), ("fixed", C.c_int32), ("fix_scale", C.c_int32), ("Scw", C.c_void_p), ("has_nc", C.c_void_p), ("Snc", C.c_void_p),
                 ("n_edges", C.c_int32), ("edges", C.c_void_p), ("n_points", C.c_int32), ("Xw", C.c_void_p), ("ref", C.c_void_p)]
@@ -153,6 +170,8 @@ SYMBOLS = {
     "eao_last_lm_timing": (_I, [C.POINTER(C.c_float), C.POINTER(_I)]),
     "eao_optimize_sim3": (_I, [C.POINTER(Sim3Problem), C.POINTER(Sim3Result)]),
     "eao_optimize_sim3_batch": (_I, [C.POINTER(Sim3Problem), _I, C.POINTER(Sim3Result)]),
+    "eao_sim3_solver_iterate": (_I, [C.POINTER(Sim3SolverProblem), _I, _I, C.POINTER(Sim3SolverState), _P, _I, C.POINTER(Sim3SolverResult)]),
+    "eao_sim3_solver_iterate_batch": (_I, [_I, C.POINTER(Sim3SolverProblem), _P, _P, C.POINTER(Sim3SolverState), _P, _P, C.POINTER(Sim3SolverResult)]),
     "eao_optimize_essential_graph": (_I, [C.POINTER(EssentialGraphProblem), C.POINTER(EssentialGraphResult)]),
     "eao_essential_graph_plan": (_I, [C.POINTER(EssentialGraphProblem), _P, _P, _P, _I]),
     "eao_bundle_adjustment_plan": (_I, [_I, _I, _P, _P, _I, _P, _P, _P, _I, _P, _I, _P, _I, _P, _I, _P, _I, _P, _I]),

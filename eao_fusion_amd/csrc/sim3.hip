@@ -1,5 +1,5 @@
 // sim3.hip -- Optimizer::OptimizeSim3 (reference src/Optimizer.cc:1437-1632): the Sim3 refinement of LoopClosing::ComputeSim3
-// (src/LoopClosing.cc:292-345) between Sim3Solver's RANSAC and the nInliers >= 20 decision.
+// (src/LoopClosing.cc:292-345) between Sim3Solver's RANSAC (sim3_solver.hip) and the nInliers >= 20 decision.
 //
 // The problem is small and dense like PoseOptimization: ONE free 7-dof vertex (VertexSim3Expmap), fixed camera-frame points,
 // two edges per correspondence (EdgeSim3ProjectXYZ: obs1 vs S12 * X2c in camera 1; EdgeInverseSim3ProjectXYZ: obs2 vs S12^-1 * X1c

@@ -780,7 +780,70 @@ eao_status eao_optimize_essential_graph(const eao_essential_graph_problem* p, ea
  * of the lower triangle or -1 (copied when cap_tile_map is large enough; row_of and tile_map may be NULL). */
 eao_status eao_essential_graph_plan(const eao_essential_graph_problem* p, eao_gba_plan_info* info, int32_t* row_of, int32_t* tile_map, int32_t cap_tile_map);
 
-/* The value of EAO_ABI_VERSION the library was built with.  Bumped whenever an entry point's parameter list or a struct's layout changes (round 3
+/* ------------------------------------------------------------------------------------------------
+ * Sim3Solver (reference include/Sim3Solver.h, src/Sim3Solver.cc): the Horn RANSAC of LoopClosing::ComputeSim3 (src/LoopClosing.cc:286-311),
+ * between SearchByBoW and SearchBySim3.  One call is one Sim3Solver::iterate: its hypotheses are evaluated together (one wavefront each:
+ * ComputeSim3 :226-337, CheckInliers :340-364), then the sequential part of the loop (:158-206) is replayed over their counts on the device.
+ * ------------------------------------------------------------------------------------------------ */
+typedef struct {
+    int32_t n;                  /* correspondences that pass the constructor's filters (src/Sim3Solver.cc:62-102), in index order */
+    const float* T1w;           /* 16 floats, row-major 4x4: pKF1 pose (GetRotation() / GetTranslation(), :54-55) */
+    const float* T2w;           /* 16 floats: pKF2 (:56-57) */
+    const float* Xw1;           /* n*3: pMP1->GetWorldPos() (:94) */
+    const float* Xw2;           /* n*3: pMP2->GetWorldPos() (:97) */
+    const float* sigma2_1;      /* n: pKF1->mvLevelSigma2[kp1.octave] (:84); finite, 0 <= sigma2 <= 1e12 */
+    const float* sigma2_2;      /* n: pKF2->mvLevelSigma2[kp2.octave] (:85) */
+    float fx1, fy1, cx1, cy1;   /* pKF1->mK (:105) */
+    float fx2, fy2, cx2, cy2;   /* pKF2->mK (:106) */
+    int32_t fix_scale;          /* mbFixScale */
+} eao_sim3_solver_problem;
+
+/* What survives between iterate calls (in/out).  A new solver starts from all zeros (SetRansacParameters :137, the constructor :38). */
+typedef struct {
+    int32_t iterations;         /* mnIterations */
+    int32_t best_inliers;       /* mnBestInliers */
+    float best_T12[16];         /* mBestT12, row-major 4x4 */
+    float best_R[9];            /* mBestRotation */
+    float best_t[3];            /* mBestTranslation */
+    float best_s;               /* mBestScale */
+} eao_sim3_solver_state;
+
+typedef struct {
+    int32_t returned;           /* position within the chunk of the hypothesis iterate returns (:192-199), or -1 */
+    int32_t n_inliers;          /* nInliers (0 unless returned >= 0) */
+    float T12[16];              /* the returned mBestT12 (zeros unless returned >= 0) */
+    uint8_t* inlier;            /* n flags over the filtered correspondences (caller-allocated), written only when returned >= 0 */
+    int32_t no_more;            /* bNoMore: n < min_inliers (:146-150; nothing is evaluated and the state is untouched), or
+                                 * iterations >= max_its after the loop when nothing returned (:203-204) */
+    /* inspection, each written when non-NULL; entries of hypotheses the call does not evaluate are zero */
+    int32_t* hyp_inliers;       /* n_hyp: mnInliersi */
+    float* hyp_T12;             /* n_hyp*16: mT12i */
+    float* hyp_T21;             /* n_hyp*16: mT21i */
+    uint8_t* hyp_inlier;        /* n_hyp*n: mvbInliersi */
+} eao_sim3_solver_result;
+
+/* Sim3Solver::iterate(n_hyp, ...) with mRansacMinInliers = min_inliers and mRansacMaxIts = max_its (the value SetRansacParameters :135 left).
+ * triples: n_hyp*3 indices into 0 .. n-1 in draw order (:166-177); an index may repeat inside a triple (the sampling loop can produce
+ * that), one out of range fails with EAO_ERR_INVALID before anything is written.  The first min(n_hyp, max_its - state->iterations)
+ * hypotheses are evaluated; then, in order: one with inliers >= best_inliers becomes the best (a tie goes to the later one), and if its
+ * inliers > min_inliers the call returns it -- iterations advances up to and including it, later hypotheses leave no trace in the state.
+ * Arithmetic: float where upstream holds CV_32F, double where it holds double.  Camera-frame points as eao_optimize_sim3 makes them (the
+ * product accumulates in double and rounds once to float, the translation is added in float); every small matrix product likewise; a double
+ * scalar times a float matrix multiplies in double and rounds once; Mat::dot and cv::norm accumulate in double; the quaternion is the
+ * eigenvector of a cyclic Jacobi solve in double, rounded to float.  The gate of correspondence i is (float)(size_t)(9.210 * sigma2[i])
+ * (include/Sim3Solver.h:78-79 hold size_t).  Nothing is repaired: a zero imaginary part gives a NaN T12, a zero depth gives inf / NaN, and
+ * a correspondence whose error is NaN is an outlier.  Two calls on the same arguments return the same bytes. */
+eao_status eao_sim3_solver_iterate(const eao_sim3_solver_problem* problem, int32_t min_inliers, int32_t max_its, eao_sim3_solver_state* state,
+                                   const int32_t* triples, int32_t n_hyp, eao_sim3_solver_result* result);
+
+/* One round of ComputeSim3's round-robin over `n_problems` candidates (src/LoopClosing.cc:286-311) for an offline replay, in one launch chain:
+ * problem b with min_inliers[b], max_its[b], states[b], triples[b] (n_hyp[b]*3 indices) and results[b].  Each result and state is
+ * bit-identical to what eao_sim3_solver_iterate returns for it.  Any invalid problem fails the call before anything is written. */
+eao_status eao_sim3_solver_iterate_batch(int32_t n_problems, const eao_sim3_solver_problem* problems, const int32_t* min_inliers, const int32_t* max_its,
+                                         eao_sim3_solver_state* states, const int32_t* const* triples, const int32_t* n_hyp,
+                                         eao_sim3_solver_result* results);
+
+/* The value of EAO_ABI_VERSION the library was built with. Bumped whenever an entry point's parameter list or a struct's layout changes (round 3
  * changed eao_tracker_track_local_map and eao_track_result in place); a caller compiled against another version must not call into the library.
  * Result structs are zero-initialised by the caller (`eao_track_result R = {0};`) before their array pointers are set: a pointer member the
  * caller's header does not know yet then reads as NULL = "not wanted". */
