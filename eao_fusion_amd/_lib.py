@@ -152,6 +152,9 @@ SYMBOLS = {
     "eao_keyframe_create": None, "eao_keyframe_update_points": None, "eao_keyframe_destroy": None, "eao_keyframe_size": None,
     "eao_kf_search_by_bow": None, "eao_kf_search_for_triangulation": None, "eao_kf_fuse_search": None, "eao_kf_search_by_projection_sim3": None,
     "eao_kf_search_by_projection_kf": None, "eao_kf_search_for_initialization": None, "eao_kf_search_by_sim3": None,
+    # the triangulation half of CreateNewMapPoints: argument lists live in search.py (TriangulationBinding)
+    "eao_triangulate_matches_batch": None, "eao_keyframe_set_depth": None, "eao_kf_create_new_map_points": None,
+    "eao_kf_last_triangulation_ms": (_I, [C.POINTER(C.c_float)]),
     # f1, second half (the device-resident tracked frame): argument lists live in tracker.py
     "eao_tracker_create": None, "eao_tracker_destroy": None, "eao_tracker_set_local_map": None, "eao_tracker_track_local_map": None, "eao_tracker_set_options": None, "eao_tracker_set_distortion": None,
     "eao_tracker_track_with_motion_model": None, "eao_tracker_track_reference_keyframe": None, "eao_abi_version": (_I, []),

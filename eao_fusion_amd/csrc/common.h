@@ -53,6 +53,26 @@ struct DevBuf {
     }
 };
 
+// Grow-only pinned host buffer.  With hipHostMallocMapped it is device-visible (kernels read and write it in place) and d is its device address; with
+// hipHostMallocDefault it stages asynchronous copies and d stays null.
+template <unsigned kFlags>
+struct PinBuf {
+    unsigned char* p = nullptr;
+    unsigned char* d = nullptr;
+    size_t n = 0;
+    eao_status reserve(size_t need) {
+        if (need <= n) return EAO_OK;
+        if (p) (void)hipHostFree(p);
+        p = nullptr; d = nullptr; n = 0;
+        const size_t cap = need + (need >> 2) + 4096;
+        EAO_HIP(hipHostMalloc((void**)&p, cap, kFlags));
+        if (kFlags & hipHostMallocMapped) EAO_HIP(hipHostGetDevicePointer((void**)&d, p, 0));
+        n = cap;
+        return EAO_OK;
+    }
+    ~PinBuf() { if (p) (void)hipHostFree(p); }
+};
+
 inline int cdiv(int a, int b) { return (a + b - 1) / b; }
 
 // Stream classes (round 6).  Upstream runs three threads at once on ONE device -- Tracking (per frame, real time), LocalMapping

@@ -27,6 +27,7 @@
 #include "common.h"
 #include "match_internal.h"
 #include "search_internal.h"
+#include "triangulate_internal.h"
 
 namespace {
 
@@ -432,21 +433,7 @@ __global__ __launch_bounds__(256) void k_kf_upload(const uint4* __restrict__ src
     for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n16; i += (size_t)gridDim.x * 256) dst[i] = src[i];
 }
 
-struct PinBuf {   // grow-only mapped pinned host buffer
-    unsigned char* p = nullptr; unsigned char* d = nullptr;
-    size_t n = 0;
-    eao_status reserve(size_t need) {
-        if (need <= n) return EAO_OK;
-        if (p) (void)hipHostFree(p);
-        p = nullptr; d = nullptr; n = 0;
-        const size_t cap = need + (need >> 2) + 4096;
-        EAO_HIP(hipHostMalloc((void**)&p, cap, hipHostMallocMapped));
-        EAO_HIP(hipHostGetDevicePointer((void**)&d, p, 0));
-        n = cap;
-        return EAO_OK;
-    }
-    ~PinBuf() { if (p) (void)hipHostFree(p); }
-};
+using PinBuf = eao::PinBuf<hipHostMallocMapped>;   // kernels read and write it in place through .d
 struct Ctx {   // per host thread, grow-only
     hipStream_t stream = nullptr;
     PinBuf in, out;
@@ -455,6 +442,9 @@ struct Ctx {   // per host thread, grow-only
     eao::DevBuf<int> ticket;       // finish workgroups of all calls so far take their tickets here (a device counter that only grows)
     int ticketNext = 0;
     PinBuf doneWord;
+    PinBuf tri;                    // eao_kf_create_new_map_points: [verdicts | points] in mapped host memory
+    hipEvent_t triEv[2] = {nullptr, nullptr};      // EAO_TRI_EVENTS=1: around the triangulation launches (tools/bench_triangulation.py)
+    float triMs = -1.f;
     long long* dbg = nullptr;
     int seq = 0;
     int gen = 0;
@@ -477,6 +467,10 @@ struct eao_keyframe {
     bool hasFv = false, fvUnique = true;
     unsigned char* dev = nullptr;      // one device block: [KfDev | arrays]
     size_t oOcc = 0;
+    // eao_keyframe_set_depth: mvDepth and mvKeys[i].pt (host copies, and one more device block [depth | raw_x | raw_y])
+    std::vector<float> depth, rawx, rawy;
+    unsigned char* devDepth = nullptr;
+    const float* dDepth = nullptr; const float* dRawx = nullptr; const float* dRawy = nullptr;
     KfDev D;
     eao::match::Resident res;
 };
@@ -611,7 +605,27 @@ eao_status eao_keyframe_update_points(eao_keyframe* h, const uint8_t* occupied) 
 void eao_keyframe_destroy(eao_keyframe* h) {
     if (!h) return;
     if (h->dev) (void)hipFree(h->dev);
+    if (h->devDepth) (void)hipFree(h->devDepth);
     delete h;
+}
+
+eao_status eao_keyframe_set_depth(eao_keyframe* h, const float* depth, const float* raw_x, const float* raw_y) {
+    EAO_REQUIRE(h, "null handle");
+    const size_t n = (size_t)h->D.n;
+    EAO_REQUIRE(n == 0 || depth, "depth missing");
+    EAO_REQUIRE(!raw_x == !raw_y, "raw_x and raw_y come together");
+    const size_t seg = al256(4 * std::max<size_t>(n, 1));
+    if (!h->devDepth && hipMalloc((void**)&h->devDepth, 3 * seg) != hipSuccess) { h->devDepth = nullptr; eao::set_error("hipMalloc of %zu bytes failed", 3 * seg); return EAO_ERR_NO_DEVICE; }
+    h->depth.assign(depth, depth + n);
+    if (raw_x) { h->rawx.assign(raw_x, raw_x + n); h->rawy.assign(raw_y, raw_y + n); }
+    else { h->rawx = h->kx; h->rawy = h->ky; }
+    if (n) {
+        EAO_HIP(hipMemcpy(h->devDepth, h->depth.data(), 4 * n, hipMemcpyHostToDevice));
+        EAO_HIP(hipMemcpy(h->devDepth + seg, h->rawx.data(), 4 * n, hipMemcpyHostToDevice));
+        EAO_HIP(hipMemcpy(h->devDepth + 2 * seg, h->rawy.data(), 4 * n, hipMemcpyHostToDevice));
+    }
+    h->dDepth = (const float*)h->devDepth; h->dRawx = (const float*)(h->devDepth + seg); h->dRawy = (const float*)(h->devDepth + 2 * seg);
+    return EAO_OK;
 }
 
 int32_t eao_keyframe_size(const eao_keyframe* h) { return h ? h->D.n : -1; }
@@ -627,9 +641,21 @@ eao_status ctx_ready(Ctx& c) {
     return EAO_OK;
 }
 
+// eao_kf_create_new_map_points: the triangulation of csrc/triangulate.hip enqueued behind the search's last launch, over the table the finish kernel wrote
+struct TriTail { const eao_tri_camera* cam1; const eao_tri_camera* cams2; float ratioFactor; int32_t* verdict; float* x3d; };
+
+eao::tri::Side tri_side(const eao_keyframe* k) {
+    eao::tri::Side S;
+    S.n = k->D.n; S.nlevels = k->D.nlevels;
+    S.kx = k->D.kx; S.ky = k->D.ky; S.ur = k->D.ur; S.depth = k->dDepth; S.rawx = k->dRawx; S.rawy = k->dRawy; S.oct = k->D.oct; S.sf = k->D.sf; S.s2 = k->D.s2;
+    return S;
+}
+
 // the shared driver of the vocabulary-node searches: MODE as in k_kf_nodes; problems in chunks of kMaxProb per launch pair, ONE synchronisation
+// (tail: the triangulation kernels follow on the same stream and the one wait is the stream's, behind them)
 eao_status run_nodes(int mode, const eao_keyframe* k1, int nProb, const eao_keyframe* const* k2s, const float* F12s, const float* exs, const float* eys,
-                     const uint8_t* valid1, const uint8_t* valid2, float nnratio, int onlyStereo, int checkOrientation, int32_t* match12, int32_t* nmatches) {
+                     const uint8_t* valid1, const uint8_t* valid2, float nnratio, int onlyStereo, int checkOrientation, int32_t* match12, int32_t* nmatches,
+                     const TriTail* tail = nullptr) {
     Ctx& c = g_kctx;
     eao_status st = ctx_ready(c);
     if (st) return st;
@@ -650,6 +676,8 @@ eao_status run_nodes(int mode, const eao_keyframe* k1, int nProb, const eao_keyf
     if (valid2) std::memcpy(c.in.p + oV2, valid2, k2s[0]->D.n);
     const size_t oTab = al256(4 * (size_t)nProb);
     if ((st = c.out.reserve(oTab + 4 * cells))) return st;
+    const size_t oX3 = al256(4 * cells);
+    if (tail && (st = c.tri.reserve(oX3 + 12 * cells))) return st;
     if (!c.ticket.p) {
         if ((st = c.ticket.reserve(1))) return st;
         EAO_HIP(hipMemsetAsync(c.ticket.p, 0, sizeof(int), c.stream));
@@ -712,8 +740,36 @@ eao_status run_nodes(int mode, const eao_keyframe* k1, int nProb, const eao_keyf
         return EAO_ERR_NO_DEVICE;
     }
     c.ticketNext += nProb;
+    if (tail) {
+        static const bool envEvents = getenv("EAO_TRI_EVENTS") && atoi(getenv("EAO_TRI_EVENTS"));
+        // the events are a diagnostic: the kernels above are enqueued and write into this thread's mapped buffers, so nothing here returns before the wait --
+        // an event call that fails only costs the measurement (triMs stays -1)
+        bool ev = envEvents;
+        for (int e = 0; ev && e < 2; e++)
+            if (!c.triEv[e]) ev = hipEventCreate(&c.triEv[e]) == hipSuccess;
+        ev = ev && hipEventRecord(c.triEv[0], c.stream) == hipSuccess;
+        if (envEvents && !ev) (void)hipGetLastError();      // (not a launch error of the kernels below)
+        const eao::tri::Side S1 = tri_side(k1);
+        for (int p0 = 0; p0 < nProb; p0 += eao::tri::kMaxProb) {
+            const int np = std::min(eao::tri::kMaxProb, nProb - p0);
+            eao::tri::Prob P[eao::tri::kMaxProb];
+            for (int q = 0; q < np; q++) {
+                P[q].K2 = tri_side(k2s[p0 + q]);
+                P[q].cam2 = tail->cams2[p0 + q];
+                P[q].match = (const int*)(c.out.d + oTab) + (size_t)(p0 + q) * n1;      // where k_kf_finish left the row
+            }
+            eao::tri::launch(c.stream, S1, *tail->cam1, tail->ratioFactor, np, P, (int*)c.tri.d + (size_t)p0 * n1, (float*)(c.tri.d + oX3) + (size_t)p0 * n1 * 3);
+        }
+        const hipError_t triErr = hipGetLastError();
+        ev = ev && hipEventRecord(c.triEv[1], c.stream) == hipSuccess;
+        EAO_HIP(eao::wait_latency(c.stream));
+        EAO_HIP(triErr);
+        if (!(ev && hipEventElapsedTime(&c.triMs, c.triEv[0], c.triEv[1]) == hipSuccess)) c.triMs = -1.f;
+        if (envEvents && !ev) (void)hipGetLastError();      // (a failed event call is not this call's failure)
+        seen = true;
+    }
     const auto t0 = std::chrono::steady_clock::now();
-    for (unsigned spins = 0; !(seen = *doneHost == seq); spins++)
+    for (unsigned spins = 0; !seen && !(seen = *doneHost == seq); spins++)
         if ((spins & 1023) == 1023 && std::chrono::steady_clock::now() - t0 > std::chrono::milliseconds(50)) break;
     std::atomic_thread_fence(std::memory_order_acquire);
     if (!seen) {
@@ -729,6 +785,10 @@ eao_status run_nodes(int mode, const eao_keyframe* k1, int nProb, const eao_keyf
     }
     std::memcpy(nmatches, c.out.p, 4 * (size_t)nProb);
     std::memcpy(match12, c.out.p + oTab, 4 * cells);
+    if (tail) {
+        std::memcpy(tail->verdict, c.tri.p, 4 * cells);
+        std::memcpy(tail->x3d, c.tri.p + oX3, 12 * cells);
+    }
     return EAO_OK;
 }
 
@@ -771,6 +831,41 @@ eao_status eao_kf_search_for_triangulation(const eao_keyframe* kf1, int32_t n_nb
         return eao_search_for_triangulation_batch(&kf1->view, &kf1->fv, n_nb, vs.data(), fs.data(), F12s, exs, eys, only_stereo, check_orientation, match12, nmatches);
     }
     return run_nodes(2, kf1, n_nb, kf2s, F12s, exs, eys, nullptr, nullptr, 0.f, only_stereo, check_orientation, match12, nmatches);
+}
+
+eao_status eao_kf_create_new_map_points(const eao_keyframe* kf1, const eao_tri_camera* cam1, int32_t n_nb, const eao_keyframe* const* kf2s,
+                                        const eao_tri_camera* cams2, const float* F12s, const float* exs, const float* eys, int32_t only_stereo,
+                                        int32_t check_orientation, float ratio_factor, int32_t* match12, int32_t* nmatches, int32_t* verdict, float* x3d) {
+    EAO_REQUIRE(kf1 && cam1 && n_nb >= 0 && (n_nb == 0 || (kf2s && cams2 && F12s && exs && eys && match12 && nmatches && verdict && x3d)), "bad argument");
+    if (n_nb == 0) return EAO_OK;
+    EAO_REQUIRE(kf1->hasFv, "the handle needs its feature vector (eao_keyframe_create with fv)");
+    EAO_REQUIRE(kf1->dDepth && kf1->view.level_sigma2, "keyframe 1: no depth (eao_keyframe_set_depth) or no level_sigma2 in its view");
+    bool unique = kf1->fvUnique;
+    for (int k = 0; k < n_nb; k++) {
+        EAO_REQUIRE(kf2s[k] && kf2s[k]->hasFv && kf2s[k]->view.level_sigma2, "neighbour %d: no handle, no feature vector or no level_sigma2 in its view", k);
+        EAO_REQUIRE(kf2s[k]->dDepth, "neighbour %d: no depth (eao_keyframe_set_depth)", k);
+        EAO_REQUIRE(finite_n(F12s + 9 * (size_t)k, 9), "neighbour %d: F12 holds a NaN / Inf", k);
+        unique = unique && kf2s[k]->fvUnique;
+    }
+    if (!unique) {      // the host replay of the search (as eao_kf_search_for_triangulation), then the triangulation over host arrays
+        std::vector<const eao_frame_view*> vs(n_nb);
+        std::vector<const eao_feature_vector*> fs(n_nb);
+        std::vector<const float*> dp(n_nb), rx(n_nb), ry(n_nb);
+        for (int k = 0; k < n_nb; k++) { vs[k] = &kf2s[k]->view; fs[k] = &kf2s[k]->fv; dp[k] = kf2s[k]->depth.data(); rx[k] = kf2s[k]->rawx.data(); ry[k] = kf2s[k]->rawy.data(); }
+        eao_status st = eao_search_for_triangulation_batch(&kf1->view, &kf1->fv, n_nb, vs.data(), fs.data(), F12s, exs, eys, only_stereo, check_orientation, match12, nmatches);
+        if (st) return st;
+        return eao_triangulate_matches_batch(&kf1->view, cam1, kf1->depth.data(), kf1->rawx.data(), kf1->rawy.data(), n_nb, vs.data(), cams2, dp.data(), rx.data(), ry.data(),
+                                             match12, ratio_factor, verdict, x3d);
+    }
+    const TriTail tail{cam1, cams2, ratio_factor, verdict, x3d};
+    return run_nodes(2, kf1, n_nb, kf2s, F12s, exs, eys, nullptr, nullptr, 0.f, only_stereo, check_orientation, match12, nmatches, &tail);
+}
+
+eao_status eao_kf_last_triangulation_ms(float* ms) {
+    EAO_REQUIRE(ms, "null argument");
+    EAO_REQUIRE(g_kctx.triMs >= 0.f, "no measurement on this thread: EAO_TRI_EVENTS=1 and a call of eao_kf_create_new_map_points come first");
+    *ms = g_kctx.triMs;
+    return EAO_OK;
 }
 
 eao_status eao_kf_fuse_search(int32_t n_kf, const eao_keyframe* const* kfs, int32_t use_sim3, const float* poses, float fx, float fy, float cx, float cy, float bf,

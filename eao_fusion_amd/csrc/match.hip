@@ -190,20 +190,7 @@ __global__ __launch_bounds__(256) void k_match_candidates(FrameDev F, const Quer
     }
 }
 
-struct PinBuf {   // grow-only pinned host buffer (device-visible: kernels write results straight into it)
-    unsigned char* p = nullptr;
-    size_t n = 0;
-    eao_status reserve(size_t need) {
-        if (need <= n) return EAO_OK;
-        if (p) (void)hipHostFree(p);
-        p = nullptr; n = 0;
-        const size_t cap = need + (need >> 2) + 4096;
-        EAO_HIP(hipHostMalloc((void**)&p, cap, hipHostMallocMapped));
-        n = cap;
-        return EAO_OK;
-    }
-    ~PinBuf() { if (p) (void)hipHostFree(p); }
-};
+using PinBuf = eao::PinBuf<hipHostMallocMapped>;   // device-visible: kernels write results straight into it
 struct HostView {   // what the old std::vector staging offered
     PinBuf buf;
     eao_status resize(size_t n) { return buf.reserve(n); }

@@ -33,8 +33,46 @@ class FeatureVector(C.Structure):
     _fields_ = [("n_nodes", _I), ("node_id", _P), ("node_start", _P), ("index", _P)]
 
 
+class TriCamera(C.Structure):   # eao_tri_camera
+    _fields_ = [("Rcw", _F * 9), ("tcw", _F * 3), ("Ow", _F * 3), ("fx", _F), ("fy", _F), ("cx", _F), ("cy", _F), ("invfx", _F), ("invfy", _F), ("mb", _F),
+                ("mbf", _F)]
+
+
+# eao_tri_verdict (include/eao_fusion.h); codes 1..3 accept
+TRI_EMPTY, TRI_TRIANGULATED, TRI_UNPROJECTED_1, TRI_UNPROJECTED_2, TRI_LOW_PARALLAX, TRI_W_ZERO, TRI_BEHIND_1, TRI_BEHIND_2, TRI_REPROJ_1, TRI_REPROJ_2, \
+    TRI_ZERO_DIST, TRI_SCALE, TRI_NO_DEPTH = range(13)
+TRI_CAMERA_SCALARS = ("fx", "fy", "cx", "cy", "invfx", "invfy", "mb", "mbf")
+
+
 def _p(a):
     return None if a is None else a.ctypes.data
+
+
+def tri_camera(cam):
+    """eao_tri_camera of a dict: Rcw (3,3), tcw (3), Ow (3) and the scalars of TRI_CAMERA_SCALARS, all float32 as the caller's KeyFrame holds them."""
+    c = TriCamera()
+    c.Rcw[:] = [float(v) for v in np.asarray(cam["Rcw"], np.float32).ravel()]
+    c.tcw[:] = [float(v) for v in np.asarray(cam["tcw"], np.float32).ravel()]
+    c.Ow[:] = [float(v) for v in np.asarray(cam["Ow"], np.float32).ravel()]
+    for k in TRI_CAMERA_SCALARS:
+        setattr(c, k, float(np.float32(cam[k])))
+    return c
+
+
+def tri_frame_view(frame):
+    """The eao_frame_view the triangulation reads: kp_x, kp_y, kp_octave, u_right, scale_factors, level_sigma2 (every other field zero / NULL); a frame dict
+    of the searches serves as it is."""
+    keep = {k: np.ascontiguousarray(frame[k], dt) for k, dt in (("kp_x", np.float32), ("kp_y", np.float32), ("kp_octave", np.int32), ("u_right", np.float32),
+                                                                ("scale_factors", np.float32), ("level_sigma2", np.float32))}
+    v = FrameView()
+    v.n, v.kp_x, v.kp_y, v.kp_octave, v.u_right = len(keep["kp_x"]), _p(keep["kp_x"]), _p(keep["kp_y"]), _p(keep["kp_octave"]), _p(keep["u_right"])
+    v.scale_factors, v.nlevels, v.level_sigma2 = _p(keep["scale_factors"]), len(keep["scale_factors"]), _p(keep["level_sigma2"])
+    return v, keep
+
+
+def _f32_or_none(frame, key):
+    v = frame.get(key)
+    return None if v is None else np.ascontiguousarray(v, np.float32)
 
 
 def frame_view(frame):
@@ -181,6 +219,30 @@ class ProductBinding(Binding):
         lib.eao_fuse_search_batch.restype = _I
         lib.eao_fuse_search_batch.argtypes = [_I, _P, _I, _P, _F, _F, _F, _F, _F, _MP, _F, _P, _P]
 
+    def triangulate_matches_batch(self, k1, cam1, k2s, cams2, match12, ratio_factor, out=None, n_nb=None):
+        """The loop of LocalMapping::CreateNewMapPoints (src/LocalMapping.cc:288-454) over the tables search_for_triangulation_batch returns.  Frame dicts carry
+        `depth` (mvDepth) and optionally `raw_x` / `raw_y` (mvKeys[i].pt); cam dicts as tri_camera() reads them.  Returns (verdict[n_nb, n1], x3d[n_nb, n1, 3]).
+        out = (verdict, x3d): the caller's arrays (None entries are passed as NULL); n_nb: the count handed to the library instead of len(k2s)."""
+        fn = self.lib.eao_triangulate_matches_batch      # (bound on first use: a library built from csrc/search.hip alone, as the host-replay test builds it, lacks it)
+        fn.restype, fn.argtypes = _I, [_FR, C.POINTER(TriCamera), _P, _P, _P, _I, _P, _P, _P, _P, _P, _P, _F, _P, _P]
+        v1, keep1 = tri_frame_view(k1)
+        d1, rx1, ry1 = np.ascontiguousarray(k1["depth"], np.float32), _f32_or_none(k1, "raw_x"), _f32_or_none(k1, "raw_y")
+        views = [tri_frame_view(k) for k in k2s]
+        nb = len(views)
+        vp = (C.POINTER(FrameView) * max(nb, 1))(*[C.pointer(v[0]) for v in views])
+        c1 = tri_camera(cam1)
+        cs = (TriCamera * max(nb, 1))(*[tri_camera(c) for c in cams2])
+        d2 = [np.ascontiguousarray(k["depth"], np.float32) for k in k2s]
+        rx2, ry2 = [_f32_or_none(k, "raw_x") for k in k2s], [_f32_or_none(k, "raw_y") for k in k2s]
+        dp = (_P * max(nb, 1))(*[_p(a) for a in d2])
+        rxp = (_P * max(nb, 1))(*[_p(a) for a in rx2])
+        ryp = (_P * max(nb, 1))(*[_p(a) for a in ry2])
+        m = np.ascontiguousarray(np.asarray(match12, np.int32).reshape(nb, v1.n))
+        verdict, x3d = out if out is not None else (np.full((nb, v1.n), -1, np.int32), np.full((nb, v1.n, 3), np.float32(-1), np.float32))
+        self.check(fn(C.byref(v1), C.byref(c1), _p(d1), _p(rx1), _p(ry1), nb if n_nb is None else int(n_nb), C.cast(vp, _P), C.cast(cs, _P), C.cast(dp, _P),
+                                                          C.cast(rxp, _P), C.cast(ryp, _P), _p(m), float(ratio_factor), _p(verdict), _p(x3d)))
+        return verdict, x3d
+
     def search_for_triangulation_batch(self, k1, fv1, k2s, fv2s, F12s, exs, eys, only_stereo, check_orientation=True):
         """Returns (nmatches[n_nb], match12[n_nb, n1])."""
         v1, keep1 = frame_view(k1)
@@ -224,6 +286,14 @@ class KeyFrameHandle:
         check(lib.eao_keyframe_create(C.byref(v), None if f is None else C.byref(f), C.byref(self.h)))
         self.n = v.n
 
+    def set_depth(self, depth, raw_x=None, raw_y=None):
+        """mvDepth and mvKeys[i].pt (None: the handle's kp_x / kp_y), copied into the handle (eao_keyframe_set_depth)."""
+        d = np.ascontiguousarray(depth, np.float32)
+        rx = None if raw_x is None else np.ascontiguousarray(raw_x, np.float32)
+        ry = None if raw_y is None else np.ascontiguousarray(raw_y, np.float32)
+        assert len(d) == self.n and (rx is None or len(rx) == self.n) and (ry is None or len(ry) == self.n)
+        self.check(self.lib.eao_keyframe_set_depth(self.h, _p(d), _p(rx), _p(ry)))
+
     def update_points(self, occupied):
         occ = None if occupied is None else np.ascontiguousarray(occupied, np.uint8)
         self.check(self.lib.eao_keyframe_update_points(self.h, _p(occ)))
@@ -254,6 +324,8 @@ class HandleBinding(ProductBinding):
             "eao_kf_search_by_projection_kf": [K, _P, _P, _F, _F, _F, _F, _MP, _P, _F, _I, _I, _P, C.POINTER(_I)],
             "eao_kf_search_for_initialization": [_I, _P, _P, _P, K, _P, _I, _F, _I, _P, C.POINTER(_I)],
             "eao_kf_search_by_sim3": [K, _P, _MP, K, _P, _MP, _F, _F, _F, _F, _F, _P, _P, _F, _P, C.POINTER(_I)],
+            "eao_keyframe_set_depth": [K, _P, _P, _P],
+            "eao_kf_create_new_map_points": [K, C.POINTER(TriCamera), _I, _P, _P, _P, _P, _P, _I, _I, _F, _P, _P, _P, _P],
         }
         for name, args in sigs.items():
             fn = getattr(lib, name)
@@ -287,6 +359,24 @@ class HandleBinding(ProductBinding):
         out, nm = np.full((nb, h1.n), -1, np.int32), np.zeros(nb, np.int32)
         self.check(self.lib.eao_kf_search_for_triangulation(h1.h, nb, C.cast(hp, _P), _p(F), _p(ex), _p(ey), int(only_stereo), int(check_orientation), _p(out), _p(nm)))
         return nm, out
+
+    def create_new_map_points_h(self, h1, cam1, h2s, cams2, F12s, exs, eys, only_stereo, ratio_factor, check_orientation=True, out=None):
+        """eao_kf_create_new_map_points: the search of search_for_triangulation_h and the triangulation of its tables in one call.
+        Returns (nmatches[n_nb], match12[n_nb, n1], verdict[n_nb, n1], x3d[n_nb, n1, 3]).  out: the caller's four arrays in that order (None = NULL)."""
+        nb = len(h2s)
+        hp = (_P * max(nb, 1))(*[h.h for h in h2s])
+        c1 = tri_camera(cam1)
+        cs = (TriCamera * max(nb, 1))(*[tri_camera(c) for c in cams2])
+        F = np.ascontiguousarray(np.asarray(F12s, np.float32).reshape(nb, 9))
+        ex, ey = np.ascontiguousarray(exs, np.float32), np.ascontiguousarray(eys, np.float32)
+        if out is not None:
+            nm, m12, verdict, x3d = out
+        else:
+            nm, m12 = np.zeros(nb, np.int32), np.full((nb, h1.n), -1, np.int32)
+            verdict, x3d = np.full((nb, h1.n), -1, np.int32), np.full((nb, h1.n, 3), np.float32(-1), np.float32)
+        self.check(self.lib.eao_kf_create_new_map_points(h1.h, C.byref(c1), nb, C.cast(hp, _P), C.cast(cs, _P), _p(F), _p(ex), _p(ey), int(only_stereo),
+                                                         int(check_orientation), float(ratio_factor), _p(m12), _p(nm), _p(verdict), _p(x3d)))
+        return nm, m12, verdict, x3d
 
     def fuse_search_h(self, hs, use_sim3, poses, K, bf, pts, th):
         nk = len(hs)
@@ -385,3 +475,19 @@ def product():
         from . import _lib
         _binding = ProductBinding(_lib.load(), _lib.check)
     return _binding
+
+
+def triangulate_matches_batch(k1, cam1, k2s, cams2, match12, ratio_factor):
+    """eao_triangulate_matches_batch over frame dicts (ProductBinding.triangulate_matches_batch)."""
+    return product().triangulate_matches_batch(k1, cam1, k2s, cams2, match12, ratio_factor)
+
+
+def keyframe_set_depth(handle, depth, raw_x=None, raw_y=None):
+    """eao_keyframe_set_depth on a KeyFrameHandle."""
+    product_handles()
+    handle.set_depth(depth, raw_x, raw_y)
+
+
+def kf_create_new_map_points(h1, cam1, h2s, cams2, F12s, exs, eys, only_stereo, ratio_factor, check_orientation=True):
+    """eao_kf_create_new_map_points over KeyFrameHandles (HandleBinding.create_new_map_points_h)."""
+    return product_handles().create_new_map_points_h(h1, cam1, h2s, cams2, F12s, exs, eys, only_stereo, ratio_factor, check_orientation)

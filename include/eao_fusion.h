@@ -384,6 +384,61 @@ eao_status eao_kf_search_by_sim3(const eao_keyframe* k1, const float* T1w, const
                                  const eao_map_points* pts2, float fx, float fy, float cx, float cy, float s12, const float* R12, const float* t12, float th,
                                  int32_t* match12, int32_t* nfound);
 
+/* ---- the second half of LocalMapping::CreateNewMapPoints: triangulate and gate the matched pairs -- src/LocalMapping.cc:288-454 ----
+ * Per matched pair (idx1 of the current keyframe, idx2 = match12[idx1] of a neighbour): the parallax test and the branch choice (:303-353: linear
+ * triangulation, KeyFrame::UnprojectStereo of keyframe 1 or 2 -- src/KeyFrame.cc:654-670 --, or "no stereo and very low parallax"), then the gates of
+ * :355-435 in upstream's order.  One verdict per slot of the match table; creating the MapPoint and its observations (:437-453) stays with the caller.
+ * Arithmetic: cv::Mat products, dot and norm accumulate in double in storage order and round once; the chi2 gates compare
+ * 5.991 * sigma2 / 7.8 * sigma2 in double against the float sum; the singular vector comes from a cyclic Jacobi solve in double on A^T A (fixed sweeps). */
+typedef enum {
+    EAO_TRI_EMPTY = 0,           /* match12 slot is -1: no pair, no point */
+    EAO_TRI_TRIANGULATED = 1,    /* accepted, linear triangulation (:324-343) */
+    EAO_TRI_UNPROJECTED_1 = 2,   /* accepted, mpCurrentKeyFrame->UnprojectStereo(idx1) (:344-347) */
+    EAO_TRI_UNPROJECTED_2 = 3,   /* accepted, pKF2->UnprojectStereo(idx2) (:348-351) */
+    EAO_TRI_LOW_PARALLAX = 4,    /* "No stereo and very low parallax" (:352-353); no point */
+    EAO_TRI_W_ZERO = 5,          /* x3D.at<float>(3) == 0 (:337); no point */
+    EAO_TRI_BEHIND_1 = 6,        /* z1 <= 0 (:359) */
+    EAO_TRI_BEHIND_2 = 7,        /* z2 <= 0 (:363) */
+    EAO_TRI_REPROJ_1 = 8,        /* reprojection gate in keyframe 1 (:372-391) */
+    EAO_TRI_REPROJ_2 = 9,        /* reprojection gate in keyframe 2 (:398-417) */
+    EAO_TRI_ZERO_DIST = 10,      /* dist1 == 0 || dist2 == 0 (:426) */
+    EAO_TRI_SCALE = 11,          /* scale consistency (:434) */
+    EAO_TRI_NO_DEPTH = 12        /* an unprojection branch met !(depth > 0): upstream would dereference the empty Mat UnprojectStereo returns; here no point */
+} eao_tri_verdict;
+/* verdicts 1..3 accept.  x3d of a rejected slot is left as computed when the point existed (verdicts 6..11) and is zero when it did not (0, 4, 5, 12). */
+
+/* What the loop reads of a keyframe's pose and camera: GetRotation() (row-major), GetTranslation(), GetCameraCenter() as the caller's KeyFrame returns them
+ * (Rwc is the transpose of Rcw, the translation of Twc is Ow), and fx, fy, cx, cy, invfx, invfy, mb, mbf. */
+typedef struct {
+    float Rcw[9], tcw[3], Ow[3];
+    float fx, fy, cx, cy, invfx, invfy, mb, mbf;
+} eao_tri_camera;
+
+/* Host arrays, all neighbours in one call (src/LocalMapping.cc:288-454 over the tables eao_search_for_triangulation_batch returns).  K1 / K2s: the views'
+ * kp_x, kp_y, kp_octave, u_right, scale_factors, level_sigma2 are read; depth = mvDepth; raw_x / raw_y = mvKeys[i].pt, which KeyFrame::UnprojectStereo reads
+ * instead of mvKeysUn (src/KeyFrame.cc:659-660) -- NULL: they equal kp_x / kp_y.  depth2s / raw_x2s / raw_y2s: n_nb pointers (raw_x2s / raw_y2s or single
+ * entries of them may be NULL).  match12: n_nb x K1->n, -1 for an empty slot, otherwise an index below K2s[k]->n; ratio_factor = 1.5f * mfScaleFactor (:236).
+ * verdict: n_nb x K1->n eao_tri_verdict codes; x3d: n_nb x K1->n x 3.  A malformed table or view fails with EAO_ERR_INVALID before anything is written. */
+eao_status eao_triangulate_matches_batch(const eao_frame_view* K1, const eao_tri_camera* cam1, const float* depth1, const float* raw_x1, const float* raw_y1,
+                                         int32_t n_nb, const eao_frame_view* const* K2s, const eao_tri_camera* cams2, const float* const* depth2s,
+                                         const float* const* raw_x2s, const float* const* raw_y2s, const int32_t* match12, float ratio_factor,
+                                         int32_t* verdict, float* x3d);
+
+/* mvDepth and mvKeys[i].pt of a resident keyframe (raw_x / raw_y NULL: the handle's kp_x / kp_y), copied into the handle once like its other arrays.
+ * depth: eao_keyframe_size(kf) floats.  Not while another thread searches this handle (as eao_keyframe_update_points). */
+eao_status eao_keyframe_set_depth(eao_keyframe* kf, const float* depth, const float* raw_x, const float* raw_y);
+
+/* CreateNewMapPoints over resident keyframes: the search of eao_kf_search_for_triangulation (same arguments, same match12 / nmatches byte for byte) and the
+ * triangulation of eao_triangulate_matches_batch over its tables, on one stream with no host hop between them and one wait: the triangulation kernel reads
+ * the match table where the selection kernel left it.  cams2: n_nb records.  Every handle needs its depth (eao_keyframe_set_depth): one without fails
+ * with EAO_ERR_INVALID before anything is written. */
+eao_status eao_kf_create_new_map_points(const eao_keyframe* kf1, const eao_tri_camera* cam1, int32_t n_nb, const eao_keyframe* const* kf2s,
+                                        const eao_tri_camera* cams2, const float* F12s, const float* exs, const float* eys, int32_t only_stereo,
+                                        int32_t check_orientation, float ratio_factor, int32_t* match12, int32_t* nmatches, int32_t* verdict, float* x3d);
+/* Diagnostic (tools/bench_triangulation.py): with EAO_TRI_EVENTS=1 in the environment, the device time in ms of the triangulation launches of this thread's last
+ * eao_kf_create_new_map_points, from HIP events on its stream.  EAO_ERR_INVALID when there is no measurement. */
+eao_status eao_kf_last_triangulation_ms(float* ms);
+
 /* ---- f1  Frame glue either side of the matcher ------------------------------------------------------------------ */
 
 /* What Frame::isInFrustum reads of the frame: mTcw (16 floats row-major: mRcw, mtcw), mOw, the static intrinsics and image

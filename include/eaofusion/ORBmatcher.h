@@ -715,6 +715,7 @@ public:
         eao_keyframe* h = nullptr;
         ORBmatcher::check(eao_keyframe_create(&v, &f, &h), "eao_keyframe_create");
         map_[(const void*)pKF] = h;
+        send_depth(pKF, h, 0);
         return h;
     }
     template <class KeyFrameT>
@@ -735,6 +736,18 @@ public:
     }
     size_t size() const { return map_.size(); }
 private:
+    // mvDepth and mvKeys[i].pt travel with the upload (eao_keyframe_set_depth: what the triangulation of include/eaofusion/LocalMapping.h reads through
+    // KeyFrame::UnprojectStereo, src/KeyFrame.cc:654-670).  A keyframe class without the two members (a search-only stand-in) uploads without them.
+    template <class KeyFrameT>
+    static auto send_depth(KeyFrameT* pKF, eao_keyframe* h, int) -> decltype((void)pKF->mvDepth, (void)pKF->mvKeys, void()) {
+        const int n = eao_keyframe_size(h);
+        std::vector<float> d(pKF->mvDepth.begin(), pKF->mvDepth.end()), rx(n > 0 ? n : 1), ry(n > 0 ? n : 1);
+        d.resize(n > 0 ? n : 1, -1.f);
+        for (int i = 0; i < n; i++) { rx[i] = pKF->mvKeys[i].pt.x; ry[i] = pKF->mvKeys[i].pt.y; }
+        ORBmatcher::check(eao_keyframe_set_depth(h, d.data(), rx.data(), ry.data()), "eao_keyframe_set_depth");
+    }
+    template <class KeyFrameT>
+    static void send_depth(KeyFrameT*, eao_keyframe*, long) {}
     std::map<const void*, eao_keyframe*> map_;
 };
 
