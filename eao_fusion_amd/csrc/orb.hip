@@ -15,8 +15,9 @@
 //                     the std::list order is reproduced by prefix sums, the (size, pointer) sort by a rank
 //   k_blur7           separable 7x7 fixed-point Gaussian: 4 px per lane, one dwordx3 per source row, v_dot4_u32_u8
 //                     horizontal and v_dot2_u32_u16 vertical passes, window of row pairs in registers
-//   k_orient_describe one wavefront per keypoint: integer moments reduced across lanes, fastAtan2, 256 point
-//                     pairs (4 per lane) packed into the descriptor with 4 wave ballots
+//   k_orient_describe one wavefront per TWO keypoints of a level, one per half-wave: integer moments reduced across the
+//                     32 lanes of a half, fastAtan2 and the fp64 sincos once per wave, 256 point pairs (8 per lane)
+//                     packed into the two descriptors with 8 wave ballots (low / high 32 bits)
 //
 // Float semantics: this file is compiled with -ffp-contract=off (see Makefile): the reference's float
 // expressions are rounded op by op.
@@ -788,21 +789,22 @@ __global__ __launch_bounds__(256) void k_blur7(const Geom* __restrict__ g, ImgSr
     else blur_strip<0>(src, pitch, dst, L.pitch, x4, y0, L.w, L.h);
 }
 
-// Sum over the 64 lanes on the VALU (DPP: two quad permutes, half-row and row mirrors, then the row broadcasts 15 / 31), the
-// total read from lane 63 into an SGPR: six v_add with DPP + one v_readlane instead of six ds_bpermute round trips.
-__device__ __forceinline__ int wave_sum_i32(int v) {
+// Sum over the 32 lanes of each half-wave on the VALU, both halves at once (DPP: two quad permutes, half-row and row mirrors, then
+// row_bcast15 into rows 1 and 3, whose lanes then hold the sums of their halves); the two totals are read from lanes 31 and 63 into
+// SGPRs and every lane takes the one of its half: five v_add with DPP + two v_readlane + one v_cndmask.
+__device__ __forceinline__ int half_sum_i32(int v, int half) {
     v += __builtin_amdgcn_update_dpp(0, v, 0xB1, 0xF, 0xF, true);    // quad_perm [1,0,3,2]
     v += __builtin_amdgcn_update_dpp(0, v, 0x4E, 0xF, 0xF, true);    // quad_perm [2,3,0,1]
     v += __builtin_amdgcn_update_dpp(0, v, 0x141, 0xF, 0xF, true);   // row_half_mirror
     v += __builtin_amdgcn_update_dpp(0, v, 0x140, 0xF, 0xF, true);   // row_mirror: every lane of a row holds the row sum
     v += __builtin_amdgcn_update_dpp(0, v, 0x142, 0xA, 0xF, true);   // row_bcast15 into rows 1 and 3
-    v += __builtin_amdgcn_update_dpp(0, v, 0x143, 0xC, 0xF, true);   // row_bcast31 into rows 2 and 3
-    return __builtin_amdgcn_readlane(v, 63);
+    const int lo = __builtin_amdgcn_readlane(v, 31), hi = __builtin_amdgcn_readlane(v, 63);
+    return half ? hi : lo;
 }
 
 // end of each row of the radius-15 disc by |v| (the table of reference src/ORBextractor.cc:455-469, verified against the
-// computed one at handle creation); [16] closes the upper half-wave's sixteenth step (there is no row 16)
-constexpr int kUmaxTab[17] = {15, 15, 15, 15, 14, 14, 14, 13, 13, 12, 11, 10, 9, 8, 6, 3, -1};
+// computed one at handle creation)
+constexpr int kUmaxTab[16] = {15, 15, 15, 15, 14, 14, 14, 13, 13, 12, 11, 10, 9, 8, 6, 3};
 
 // ---------------------------------------------------------------------------------------------- orientation + rBRIEF
 // sin/cos of a float angle in [0, 2*pi], evaluated in double (Cody-Waite reduction by pi/2 + the classic
@@ -819,13 +821,10 @@ __device__ __forceinline__ void sincos_f32_via_f64(float angle, float* sn, float
     const double pc = 4.16666666666666019037e-02 + z * (-1.38888888888741095749e-03 + z * (2.48015872894767294178e-05 +
                       z * (-2.75573143513906633035e-07 + z * (2.08757232129817482790e-09 + z * -1.13596475577881948265e-11))));
     const double cr = 1.0 - 0.5 * z + z * z * pc;
-    double sv, cv;
-    switch (k & 3) {
-        case 0: sv = sr; cv = cr; break;
-        case 1: sv = cr; cv = -sr; break;
-        case 2: sv = -sr; cv = -cr; break;
-        default: sv = -cr; cv = sr; break;
-    }
+    // quadrant k & 3: (sr, cr), (cr, -sr), (-sr, -cr), (-cr, sr) -- as selects: the two half-waves of k_orient_describe differ in k
+    double sv = (k & 1) ? cr : sr, cv = (k & 1) ? sr : cr;
+    if (k & 2) sv = -sv;
+    if ((k + 1) & 2) cv = -cv;
     *sn = (float)sv;
     *cs = (float)cv;
 }
@@ -837,152 +836,177 @@ __device__ __forceinline__ float fast_atan2_deg(float y, float x) {
     const float p7 = -0.04432655554792128f * (float)(180 / 3.1415926535897932384626433832795);
     const float eps = (float)2.2204460492503131e-16;
     const float ax = fabsf(x), ay = fabsf(y);
-    float a, c, c2;
-    if (ax >= ay) {
-        c = ay / (ax + eps);
-        c2 = c * c;
-        a = (((p7 * c2 + p5) * c2 + p3) * c2 + p1) * c;
-    } else {
-        c = ax / (ay + eps);
-        c2 = c * c;
-        a = 90.f - (((p7 * c2 + p5) * c2 + p3) * c2 + p1) * c;
-    }
+    // (the two branches of the reference, ay / (ax + eps) and 90 - the same of ax / (ay + eps), as selects around ONE division and ONE
+    //  polynomial: the same operations on the same operands, and the two half-waves of k_orient_describe may differ in the branch)
+    const bool ge = ax >= ay;
+    const float c = (ge ? ay : ax) / ((ge ? ax : ay) + eps);
+    const float c2 = c * c;
+    const float poly = (((p7 * c2 + p5) * c2 + p3) * c2 + p1) * c;
+    float a = ge ? poly : 90.f - poly;
     if (x < 0) a = 180.f - a;
     if (y < 0) a = 360.f - a;
     return a;
 }
 
+// Keypoints per workgroup (two per wave, four waves), staged-window geometry of a keypoint.  The 37 x 37 window of the blurred level
+// (the 256 test pairs, rotated, stay inside radius 18.4 of the keypoint: |pattern| <= sqrt(338)) and the 31 x 31 window of the raw
+// level (intensity centroid) are staged in LDS as rows of aligned words: 37 (31) bytes + up to 3 bytes of alignment phase = 10 (9)
+// words per row.  A half-wave fetches 3 rows per load instruction -- lane = row-in-step * words-per-row + word, 30 (27) of its 32
+// lanes busy, the lane's offset advanced by three pitches per load -- so the LDS word of load k is simply lane + 30 k (27 k).
+constexpr int kDescKp = 8;
+constexpr int kPR = 18, kPW = 10, kPRows = 2 * kPR + 1, kPLoads = (kPRows + 2) / 3;   // 13 loads, the last one holds row 36 only
+constexpr int kMR = 15, kMW = 9, kMRows = 2 * kMR + 1, kMLoads = (kMRows + 2) / 3;    // 11 loads, the last one holds row 30 only
+
 __global__ __launch_bounds__(256) void k_orient_describe(const Geom* __restrict__ g, ImgSrc s, const uint8_t* __restrict__ blur,
                                                          const unsigned* __restrict__ levelkps, const int* __restrict__ levelcnt,
                                                          eao_keypoint* __restrict__ kps, uint8_t* __restrict__ desc,
-                                                         int* __restrict__ nout, int cap, int f0, int nlevels, int lFirst, int lEnd, int writeN) {
-    // Levels [lFirst, lEnd) of every frame: blockIdx.x * 4 + wave counts the keypoints of THOSE levels; a launch over the lower levels may run
+                                                         int* __restrict__ nout, int cap, int f0, int nlevels, int lFirst, int lEnd, int writeN,
+                                                         int frameAffinity) {
+    // TWO keypoints per wavefront, one per half-wave: lanes 0-31 take keypoint 2p of a level, lanes 32-63 keypoint 2p + 1 of the SAME level,
+    // so the level -- its geometry, base pointers and pitch -- stays wave-uniform (SGPRs, scalar loads, SGPR base + 32-bit lane offset
+    // addressing) while the prologue, fastAtan2 and the fp64 sincos are paid once for two keypoints.  A level with an odd count leaves the
+    // upper half of its last wave idle: that half shadows keypoint 2p (every access stays in bounds) and stores nothing.
+    // Levels [lFirst, lEnd) of every frame: workgroup * 4 + wave counts the PAIRS of those levels; a launch over the lower levels may run
     // while the upper levels' quad-trees are still at work (their counts are not read), the launch that covers the last level writes the
     // frame's keypoint count (writeN).
-    // (the wave index through readfirstlane: the compiler then KNOWS that the keypoint -- index, key, position, level --
-    //  is wave-uniform, keeps it in SGPRs, loads it with scalar loads and addresses the two windows as SGPR base + 32-bit
-    //  lane offset instead of per-lane 64-bit pointer arithmetic)
+    // (the wave index through readfirstlane: the compiler then KNOWS that the pair -- index, level -- is wave-uniform)
     const int lane = threadIdx.x & 63, wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    // the lane's four test pairs (xa, ya, xb, yb as int8) depend on nothing: fetch them first, under the other loads
-    unsigned pat[4];
-#pragma unroll
-    for (int k = 0; k < 4; k++) pat[k] = reinterpret_cast<const unsigned*>(c_pattern)[lane + 64 * k];
+    const int hl = lane & 31, half = lane >> 5;
     // Workgroups are dealt round-robin over the 8 XCDs and every XCD has its own L2: with the plain (blockIdx.y = frame)
-    // order the patches of one frame are pulled into all eight L2s.  When the batch is a multiple of 8, frame f is served
-    // by XCD f % 8 only (speed only: any placement gives the same results).
-    int bx = blockIdx.x, fy = blockIdx.y;
-    if ((gridDim.y & 7) == 0) {
-        const unsigned b = blockIdx.x + gridDim.x * blockIdx.y, xcd = b & 7, slot = b >> 3;
-        fy = (int)(xcd + 8 * (slot / gridDim.x));
-        bx = (int)(slot % gridDim.x);
-    }
-    int j = bx * 4 + wv;   // compact output index inside the frame (relative to the first keypoint of level lFirst until the counts are known)
+    // order the patches of one frame are pulled into all eight L2s.  When the batch is a multiple of 8 (frameAffinity), frame f is served
+    // by XCD f % 8 only (speed only: any placement gives the same results): the grid is then (8 * workgroups per frame, batch / 8), so that
+    // XCD and slot are the low bits and the rest of blockIdx.x -- no division.
+    const int bx = frameAffinity ? (int)(blockIdx.x >> 3) : (int)blockIdx.x;
+    const int fy = frameAffinity ? (int)((blockIdx.x & 7) + 8 * blockIdx.y) : (int)blockIdx.y;
+    int p = bx * 4 + wv;   // pair index inside the frame (relative to the first pair of level lFirst until the counts are known)
     const int f = fy + f0;
-    // level of compact index j: the level counts are wave-uniform -- independent scalar loads and a running sum on the
-    // scalar unit (the first version scanned them across lanes: four ds_bpermute round trips before anything else could start)
-    // (lanes 0 .. nlevels-1 hold the level counts, an inclusive DPP scan inside the 16-lane row gives the level ends, a ballot
-    //  counts the levels that end at or before j: a dozen instructions.  As a scalar loop over the sixteen possible levels it
-    //  was ~90 SALU instructions per wave, in a kernel that issues as many scalar as vector instructions -- one scalar unit per CU)
-    int total, l, lbase;
+    // level of pair p: lanes 0 .. nlevels-1 hold the level counts, inclusive DPP scans inside the 16-lane row give the level ends in keypoints
+    // (the output slots) and in pairs ((count + 1) >> 1 per level), a ballot counts the levels that end at or before p: two dozen instructions
+    // (as a scalar loop over the sixteen possible levels it was ~90 SALU instructions per wave)
+    int total, l, kbase, pbase, cntl;
     {
-        int inc = lane < lEnd ? levelcnt[f * nlevels + lane] : 0;
-        inc += __builtin_amdgcn_update_dpp(0, inc, 0x111, 0xF, 0xF, true);   // row_shr:1
-        inc += __builtin_amdgcn_update_dpp(0, inc, 0x112, 0xF, 0xF, true);   // row_shr:2
-        inc += __builtin_amdgcn_update_dpp(0, inc, 0x114, 0xF, 0xF, true);   // row_shr:4
-        inc += __builtin_amdgcn_update_dpp(0, inc, 0x118, 0xF, 0xF, true);   // row_shr:8
-        total = __builtin_amdgcn_readlane(inc, 15);
-        if (lFirst > 0) j += __builtin_amdgcn_readlane(inc, lFirst - 1);
-        l = (int)__popcll(__ballot(lane < nlevels && inc <= j));                // levels that end at or before j (levels >= lEnd: the flat tail of the scan)
-        lbase = l > 0 ? __builtin_amdgcn_readlane(inc, min(l, kMaxLevels) - 1) : 0;
+        int cinc = lane < lEnd ? levelcnt[f * nlevels + lane] : 0;
+        int pinc = (cinc + 1) >> 1;
+        cinc += __builtin_amdgcn_update_dpp(0, cinc, 0x111, 0xF, 0xF, true);   // row_shr:1
+        pinc += __builtin_amdgcn_update_dpp(0, pinc, 0x111, 0xF, 0xF, true);
+        cinc += __builtin_amdgcn_update_dpp(0, cinc, 0x112, 0xF, 0xF, true);   // row_shr:2
+        pinc += __builtin_amdgcn_update_dpp(0, pinc, 0x112, 0xF, 0xF, true);
+        cinc += __builtin_amdgcn_update_dpp(0, cinc, 0x114, 0xF, 0xF, true);   // row_shr:4
+        pinc += __builtin_amdgcn_update_dpp(0, pinc, 0x114, 0xF, 0xF, true);
+        cinc += __builtin_amdgcn_update_dpp(0, cinc, 0x118, 0xF, 0xF, true);   // row_shr:8
+        pinc += __builtin_amdgcn_update_dpp(0, pinc, 0x118, 0xF, 0xF, true);
+        total = __builtin_amdgcn_readlane(cinc, 15);
+        if (lFirst > 0) p += __builtin_amdgcn_readlane(pinc, lFirst - 1);
+        l = (int)__popcll(__ballot(lane < nlevels && pinc <= p));               // levels that end at or before p (levels >= lEnd: the flat tail of the scan)
+        const int lprev = min(l, kMaxLevels) - 1;
+        pbase = l > 0 ? __builtin_amdgcn_readlane(pinc, lprev) : 0;
+        kbase = l > 0 ? __builtin_amdgcn_readlane(cinc, lprev) : 0;
+        cntl = __builtin_amdgcn_readlane(cinc, min(l, kMaxLevels - 1)) - kbase;  // keypoints of level l
     }
-    const int jout = j;
     if (writeN && bx == 0 && threadIdx.x == 0) nout[f] = min(total, cap);
-    if (l >= nlevels || jout >= cap) return;
-    j -= lbase;
+    const int j0 = 2 * (p - pbase);   // the lower half's keypoint inside level l; its output slot is kbase + j0
+    if (l >= nlevels || kbase + j0 >= cap) return;
+    const bool hasB = j0 + 1 < cntl && kbase + j0 + 1 < cap;   // the upper half has a keypoint of its own (wave-uniform)
     const LevelGeom L = g->L[l];
-    const unsigned key = levelkps[(long long)f * g->totalKpCap + L.kpBase + j];
+    const unsigned* lk = levelkps + (long long)f * g->totalKpCap + L.kpBase + j0;
+    const unsigned keyA = lk[0], keyB = lk[hasB ? 1 : 0];
+    const unsigned key = half ? keyB : keyA;
     const int cx = (int)(key & 0xFFF) + kMinBorder, cy = (int)((key >> 12) & 0xFFF) + kMinBorder;
     int pitch;
     const uint8_t* img = level_ptr(g, s, l, f, &pitch);
-    // The 256 test pairs, rotated, stay inside radius 18.4 of the keypoint (|pattern| <= sqrt(338)): the 37 x 37 window of
-    // the blurred level is staged in LDS with aligned word loads (6 per lane, issued before the moment loads) and the
-    // 512 scattered byte reads of the wave go to LDS instead of the texture path.
-    constexpr int kPR = 18, kPW = 10;   // window radius; words per staged row (37 + up to 3 bytes of alignment)
-    __shared__ unsigned patch[4][(2 * kPR + 1) * kPW];
+    // one LDS buffer per keypoint serves both windows: the raw one is dead (moments summed) before the blurred one is written
+    __shared__ unsigned win[kDescKp][kPRows * kPW];
+    unsigned* wbuf = win[wv * 2 + half];
+    // the blurred window: 13 aligned word loads per lane, issued before the moment loads, parked in registers until the moments are done
     const int ph = (cx - kPR) & 3;
-    const uint8_t* bw = blur + (long long)f * g->pyrFrameBytes + L.off + (cy - kPR) * L.pitch + (cx - kPR - ph);
-    unsigned pw[6];
+    const uint8_t* bw = blur + (long long)f * g->pyrFrameBytes + L.off;
+    unsigned pw[kPLoads];
+    {
+        const int pl = min(hl, 3 * kPW - 1);   // (lanes 30, 31 shadow lane 29 and store nothing)
+        const int r0 = pl >= 2 * kPW ? 2 : (pl >= kPW ? 1 : 0), w0 = pl - r0 * kPW;
+        const unsigned o0 = (unsigned)((cy - kPR + r0) * L.pitch + (cx - kPR - ph) + 4 * w0);
+        const unsigned step = (unsigned)(3 * L.pitch), olast = o0 + (unsigned)((kPRows - 1 - r0) * L.pitch);   // rows 37, 38 do not exist: row 36 again
 #pragma unroll
-    for (int k = 0; k < 6; k++) {
-        const int i = min(lane + 64 * k, (2 * kPR + 1) * kPW - 1), r = (i * 6554) >> 16;   // i / 10
-        pw[k] = *reinterpret_cast<const unsigned*>(bw + (unsigned)(r * L.pitch + 4 * (i - r * kPW)));
+        for (int k = 0; k < kPLoads; k++)
+            pw[k] = k < kPLoads - 1 ? *reinterpret_cast<const unsigned*>(bw + (unsigned)k * step + o0) : *reinterpret_cast<const unsigned*>(bw + olast);
     }
-    // the 31 x 31 window of the (unblurred) level for the intensity centroid goes through LDS the same way: 5 aligned word
-    // loads per lane instead of 16 byte loads
-    constexpr int kMR = 15, kMW = 9;    // 31 + up to 3 bytes of alignment = 9 words per row
-    __shared__ unsigned mpatch[4][(2 * kMR + 1) * kMW];
+    // the raw window for the intensity centroid goes through LDS the same way: 11 aligned word loads per lane
     const bool imgAligned = ((((uintptr_t)img | (uintptr_t)pitch) & 3) == 0);   // (an unaligned caller image: byte loads)
     const int mph = (cx - kMR) & 3;
     if (imgAligned) {
-        const uint8_t* mw = img + (cy - kMR) * pitch + (cx - kMR - mph);
-        unsigned mv[5];
+        const int ml = min(hl, 3 * kMW - 1);   // (lanes 27 .. 31 shadow lane 26 and store nothing)
+        const int r0 = ml >= 2 * kMW ? 2 : (ml >= kMW ? 1 : 0), w0 = ml - r0 * kMW;
+        const unsigned o0 = (unsigned)((cy - kMR + r0) * pitch + (cx - kMR - mph) + 4 * w0);
+        const unsigned step = (unsigned)(3 * pitch), olast = o0 + (unsigned)((kMRows - 1 - r0) * pitch);   // rows 31, 32 do not exist: row 30 again
+        unsigned mv[kMLoads];
 #pragma unroll
-        for (int k = 0; k < 5; k++) {
-            const int i = min(lane + 64 * k, (2 * kMR + 1) * kMW - 1), r = (i * 7282) >> 16;   // i / 9
-            mv[k] = *reinterpret_cast<const unsigned*>(mw + (unsigned)(r * pitch + 4 * (i - r * kMW)));
+        for (int k = 0; k < kMLoads; k++)
+            mv[k] = k < kMLoads - 1 ? *reinterpret_cast<const unsigned*>(img + (unsigned)k * step + o0) : *reinterpret_cast<const unsigned*>(img + olast);
+        if (hl < 3 * kMW) {
+#pragma unroll
+            for (int k = 0; k < kMLoads - 1; k++) wbuf[hl + 3 * kMW * k] = mv[k];
+            if (hl < kMW) wbuf[hl + 3 * kMW * (kMLoads - 1)] = mv[kMLoads - 1];
         }
-#pragma unroll
-        for (int k = 0; k < 5; k++)
-            if (lane + 64 * k < (2 * kMR + 1) * kMW) mpatch[wv][lane + 64 * k] = mv[k];
     } else {
-        uint8_t* mb = reinterpret_cast<uint8_t*>(mpatch[wv]);
-        for (int i = lane; i < (2 * kMR + 1) * (2 * kMR + 1); i += 64) {
-            const int r = i / (2 * kMR + 1), c = i - r * (2 * kMR + 1);
+        uint8_t* mb = reinterpret_cast<uint8_t*>(wbuf);
+        // (the rare path: vectorised or unrolled, its 64-bit addresses would set the register count of the whole kernel)
+#pragma clang loop vectorize(disable) interleave(disable) unroll(disable)
+        for (int i = hl; i < kMRows * kMRows; i += 32) {
+            const int r = i / kMRows, c = i - r * kMRows;
             mb[r * (4 * kMW) + c + mph] = img[(long long)(cy - kMR + r) * pitch + cx - kMR + c];
         }
     }
     eao::wave_sync();
-    // intensity centroid over the radius-15 disc: lanes 0..30 / 32..62 take column u, the halves split the rows
-    const int u = (lane & 31) - 15, half = lane >> 5;
-    int m10 = 0, m01 = 0;
-    if (u <= 15) {
-        // rows v = -15..0 (lower half-wave) / 1..15 (upper); end of each row of the radius-15 disc = kUmaxTab[|v|]
-        const uint8_t* c0 = reinterpret_cast<const uint8_t*>(mpatch[wv]) + kMR * (4 * kMW) + kMR + mph + u;
+    // the lane's eight test pairs (xa, ya, xb, yb as int8), word hl + 32 k of the pattern: fetched here, under the moments and the trigonometry
+    // (ahead of the window loads they would be eight more live registers where the kernel holds the most)
+    unsigned pat[8];
+#pragma unroll
+    for (int k = 0; k < 8; k++) pat[k] = reinterpret_cast<const unsigned*>(c_pattern)[hl + 32 * k];
+    // intensity centroid over the radius-15 disc: lanes 0..30 of a half-wave take column u and walk the 31 rows; pixels outside the
+    // disc count as zero (the window holds every (u, v) with |u|, |v| <= 15).  Integer sums only, re-associated: a lane sums its
+    // column once (m10 = u * sum) and takes rows v and -v, which share their bound, together (m01 += v * (p(v) - p(-v))).
+    const int u = hl - kMR;
+    int colsum = 0, m01 = 0;
+    if (hl < kMRows) {
+        const uint8_t* c0 = reinterpret_cast<const uint8_t*>(wbuf) + kMR * (4 * kMW) + kMR + mph + u;
         const int au = u < 0 ? -u : u;
-        // One row per step and half-wave; the row ends come into the code as IMMEDIATES (template constants).  Written as a
-        // loop over a constexpr table the compiler selected between two table ADDRESSES and loaded the bound from constant
-        // memory -- a dependent global load (plus s_waitcnt vmcnt(0)) in every one of the sixteen steps: 85 of the kernel's
-        // 300 us.  Pixels outside the disc count as zero (the window holds every (u, v) with |u|, |v| <= 15).
-        auto row = [&](auto kc) {
-            constexpr int k = decltype(kc)::value;
-            constexpr int umLo = kUmaxTab[15 - k], umHi = kUmaxTab[k + 1];
-            const int v = half ? k + 1 : k - 15;
-            const int um = half ? umHi : umLo;
-            const int pix = c0[v * (4 * kMW)];
-            const int val = au <= um ? pix : 0;
-            m10 += u * val;
-            m01 += v * val;
+        colsum = c0[0];
+        // The row ends come into the code as IMMEDIATES (template constants).  Written as a loop over a constexpr table the compiler
+        // selected between table ADDRESSES and loaded the bound from constant memory -- a dependent global load (plus s_waitcnt
+        // vmcnt(0)) in every step: 85 of the kernel's 300 us at the time.
+        auto rows = [&](auto vc) {
+            constexpr int v = decltype(vc)::value, um = kUmaxTab[v];
+            const int pp = c0[v * (4 * kMW)], pn = c0[-v * (4 * kMW)];
+            const bool in = um >= kMR || au <= um;
+            colsum += in ? pp + pn : 0;
+            m01 += v * (in ? pp - pn : 0);
         };
-#define EAO_ROW(K) row(std::integral_constant<int, K>{});
-        EAO_ROW(0) EAO_ROW(1) EAO_ROW(2) EAO_ROW(3) EAO_ROW(4) EAO_ROW(5) EAO_ROW(6) EAO_ROW(7)
-        EAO_ROW(8) EAO_ROW(9) EAO_ROW(10) EAO_ROW(11) EAO_ROW(12) EAO_ROW(13) EAO_ROW(14) EAO_ROW(15)
-#undef EAO_ROW
+#define EAO_ROWS(V) rows(std::integral_constant<int, V>{});
+        EAO_ROWS(1) EAO_ROWS(2) EAO_ROWS(3) EAO_ROWS(4) EAO_ROWS(5) EAO_ROWS(6) EAO_ROWS(7) EAO_ROWS(8)
+        EAO_ROWS(9) EAO_ROWS(10) EAO_ROWS(11) EAO_ROWS(12) EAO_ROWS(13) EAO_ROWS(14) EAO_ROWS(15)
+#undef EAO_ROWS
     }
-    m10 = wave_sum_i32(m10);
-    m01 = wave_sum_i32(m01);
+    const int m10 = half_sum_i32(u * colsum, half);
+    m01 = half_sum_i32(m01, half);
+    // once per wave, on the values of the lane's half
     const float angle = fast_atan2_deg((float)m01, (float)m10);
     // steered BRIEF on the blurred level
     const float factorPI = (float)(3.1415926535897932384626433832795 / 180.f);
     float a, b;
     sincos_f32_via_f64(angle * factorPI, &b, &a);
+    // (a wave's LDS accesses are served in order: the moment reads above are done with the buffer before these writes land)
+    if (hl < 3 * kPW) {
 #pragma unroll
-    for (int k = 0; k < 6; k++)
-        if (lane + 64 * k < (2 * kPR + 1) * kPW) patch[wv][lane + 64 * k] = pw[k];
-    eao::wave_sync();   // (one wave per keypoint: LDS writes of a wave are ordered before its later reads)
-    const uint8_t* bc = reinterpret_cast<const uint8_t*>(patch[wv]) + kPR * (4 * kPW) + kPR + ph;
-    unsigned long long words[4];
+        for (int k = 0; k < kPLoads - 1; k++) wbuf[hl + 3 * kPW * k] = pw[k];
+        if (hl < kPW) wbuf[hl + 3 * kPW * (kPLoads - 1)] = pw[kPLoads - 1];
+    }
+    eao::wave_sync();
+    const uint8_t* bc = reinterpret_cast<const uint8_t*>(wbuf) + kPR * (4 * kPW) + kPR + ph;
+    // test pair hl + 32 k is bit hl of descriptor word k: ballot k holds word k of the lower half's keypoint in its low and of the upper
+    // half's in its high 32 bits
+    unsigned long long words[8];
 #pragma unroll
-    for (int k = 0; k < 4; k++) {
+    for (int k = 0; k < 8; k++) {
         const float xa = (float)(signed char)(pat[k] & 0xFF), ya = (float)(signed char)((pat[k] >> 8) & 0xFF);
         const float xb = (float)(signed char)((pat[k] >> 16) & 0xFF), yb = (float)(signed char)(pat[k] >> 24);
         const int ra = __float2int_rn(xa * b + ya * a), ca = __float2int_rn(xa * a - ya * b);
@@ -990,9 +1014,14 @@ __global__ __launch_bounds__(256) void k_orient_describe(const Geom* __restrict_
         const int t0 = bc[ra * (4 * kPW) + ca], t1 = bc[rb * (4 * kPW) + cb];
         words[k] = __ballot(t0 < t1);
     }
-    if (lane == 0) {
+    if (hl == 0 && (half == 0 || hasB)) {
+        const int jout = kbase + j0 + half;
+        unsigned w[8];
+#pragma unroll
+        for (int k = 0; k < 8; k++) w[k] = half ? (unsigned)(words[k] >> 32) : (unsigned)words[k];
         unsigned long long* d = reinterpret_cast<unsigned long long*>(desc + ((long long)f * cap + jout) * 32);
-        d[0] = words[0]; d[1] = words[1]; d[2] = words[2]; d[3] = words[3];
+#pragma unroll
+        for (int k = 0; k < 4; k++) d[k] = (unsigned long long)w[2 * k] | ((unsigned long long)w[2 * k + 1] << 32);
         eao_keypoint kp;
         const float fxp = (float)cx, fyp = (float)cy;
         kp.x = l ? fxp * L.scale : fxp;
@@ -1188,7 +1217,7 @@ eao_status enqueue(eao_orb* h, const uint8_t* d_img, int pitch0, long long fs0, 
     };
     // Schedule of a (non-profiled) batch -- FAST and the blur are both VALU-bound, the quad-tree leaves the machine
     // almost idle, so the blur runs beside the quad-tree, not beside FAST:
-    //   main:  resize 1..n-1 -> FAST(levels >= mid) -> quad-tree -> orientation + description
+    //   main:  resize 1..n-1 -> FAST(levels >= mid) -> quad-tree -> orientation + description (ONE launch, two keypoints per wave, behind evJoin)
     //   side:  FAST(level 0) -> FAST(levels 1..mid-1) once they exist -> (all FAST done) blur
     // mid = 3: FAST of levels 1 and 2 joins level 0 on the side stream as soon as they exist, beside the rest of the pyramid
     // chain, whose small launches leave the machine idle (measured, ms per step, mid 0 / 3: batch 32 0.296 / 0.296, 64
@@ -1214,6 +1243,17 @@ eao_status enqueue(eao_orb* h, const uint8_t* d_img, int pitch0, long long fs0, 
         if (prof) EAO_HIP(hipEventRecord(ev[7], ss));
         EAO_HIP(hipEventRecord(h->evJoin, ss));
         return EAO_OK;
+    };
+    // orientation + description of levels [lFirst, lEnd): a wave takes two keypoints of one level, so the grid covers the PAIR capacity of those
+    // levels (a level of listCap slots holds at most ceil(listCap / 2) pairs; no more pairs than output slots + one odd pair per level either),
+    // four waves per workgroup; with frame affinity the XCD (= frame % 8) is the low three bits of blockIdx.x (see the kernel)
+    auto describe = [&](hipStream_t str, int lFirst, int lEnd, int writeN) {
+        eao::Range rg("orb: orientation + description");
+        int pairs = 0;
+        for (int l = lFirst; l < lEnd; l++) pairs += eao::cdiv(g.L[l].listCap, 2);
+        const int gx = std::max(1, eao::cdiv(std::min(pairs, eao::cdiv(cap, 2) + g.nlevels), 4));
+        hipLaunchKernelGGL(k_orient_describe, aff ? dim3(8 * gx, batch / 8) : dim3(gx, batch), dim3(256), 0, str,
+                           h->d_geom.p, s, h->d_blur.p, h->d_levelkps.p, h->d_levelcnt.p, d_kps, d_desc, d_n, cap, 0, g.nlevels, lFirst, lEnd, writeN, aff);
     };
     // Measured (device-resident step, ms): batch 1: 0.117 fused vs 0.142 chain, 8: 0.136 / 0.160, 32: 0.231 / 0.235, 64: 0.353 /
     // 0.309 -- small batches are bound by the chain of dependent launches, large ones by the VALU, where the fused kernel's
@@ -1305,8 +1345,7 @@ eao_status enqueue(eao_orb* h, const uint8_t* d_img, int pitch0, long long fs0, 
         EAO_HIP(hipStreamWaitEvent(st, h->evJoin, 0));
         if (prof) EAO_HIP(hipEventRecord(ev[4], st));
     }
-    { eao::Range rg("orb: orientation + description"); hipLaunchKernelGGL(k_orient_describe, dim3(eao::cdiv(std::min(cap, g.totalKpCap), 4), batch), dim3(256), 0, st,
-                       h->d_geom.p, s, h->d_blur.p, h->d_levelkps.p, h->d_levelcnt.p, d_kps, d_desc, d_n, cap, 0, g.nlevels, 0, g.nlevels, 1); }
+    describe(st, 0, g.nlevels, 1);
     if (prof) {
         EAO_HIP(hipEventRecord(ev[5], st));
         EAO_HIP(hipEventRecord(ev[8], st));
