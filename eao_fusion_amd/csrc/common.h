@@ -74,6 +74,8 @@ struct PinBuf {
 };
 
 inline int cdiv(int a, int b) { return (a + b - 1) / b; }
+// every slice of a device arena / staging block starts on a 256-byte boundary
+inline size_t align256(size_t v) { return (v + 255) & ~(size_t)255; }
 
 // Stream classes (round 6).  Upstream runs three threads at once on ONE device -- Tracking (per frame, real time), LocalMapping
 // (LocalBundleAdjustment, src/LocalMapping.cc:75) and LoopClosing's global BundleAdjustment thread (src/LoopClosing.cc:594; all started
@@ -97,6 +99,32 @@ hipError_t wait_latency(hipStream_t s);
 // 0.77 idle); with two groups 1.08 / 1.64 ms, the batch 2.87 -> 3.13 ms per call.  No latency-class call within the last 100 ms: four groups, as in the benchmark.
 void note_latency_call();
 bool latency_caller_alive();
+
+// One host thread's stream (a member of the thread_local context of an entry point) and, on request, a pair of timing events.  ready() is the first thing a
+// call does; nothing is taken for ready that was not created (a call after a failed one starts over), and whatever was created goes with the thread.
+struct ThreadStream {
+    hipStream_t stream = nullptr;
+    hipEvent_t ev0 = nullptr, ev1 = nullptr;
+    ThreadStream() = default;
+    ThreadStream(const ThreadStream&) = delete;
+    ThreadStream& operator=(const ThreadStream&) = delete;
+    eao_status ready(StreamClass c) {
+        eao_status st = require_device();
+        if (st) return st;
+        if (!stream) EAO_HIP(create_stream(&stream, c));
+        return EAO_OK;
+    }
+    eao_status timing() {
+        if (!ev0) EAO_HIP(hipEventCreate(&ev0));
+        if (!ev1) EAO_HIP(hipEventCreate(&ev1));
+        return EAO_OK;
+    }
+    ~ThreadStream() {
+        if (ev0) (void)hipEventDestroy(ev0);
+        if (ev1) (void)hipEventDestroy(ev1);
+        if (stream) (void)hipStreamDestroy(stream);
+    }
+};
 
 #if defined(__HIPCC__)
 // THE hand-over point between the lanes of ONE wavefront through LDS (or through memory the wave alone touches): the

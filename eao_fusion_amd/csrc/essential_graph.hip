@@ -417,32 +417,14 @@ __global__ __launch_bounds__(256) void k_eg_finish(EgDev D) {
 }
 
 // ---------------------------------------------------------------------- host side
-struct EgCtx {      // per host thread, grow-only
-    hipStream_t stream = nullptr;
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;
+struct EgCtx : ThreadStream {      // per host thread, grow-only; the stream class of the map bundle adjustment (LoopClosing's thread)
     EgStatus* status = nullptr;      // pinned + mapped
     DevBuf<unsigned char> dev;
     std::vector<unsigned char> host;
     GbaPlan plan;
-    ~EgCtx() {
-        if (status) (void)hipHostFree(status);
-        if (ev0) (void)hipEventDestroy(ev0);
-        if (ev1) (void)hipEventDestroy(ev1);
-        if (stream) (void)hipStreamDestroy(stream);
-    }
+    ~EgCtx() { if (status) (void)hipHostFree(status); }
 };
 thread_local EgCtx g_eg;
-
-eao_status eg_ctx_init(EgCtx& c) {
-    if (c.stream) return EAO_OK;
-    eao_status st = require_device();
-    if (st) return st;
-    EAO_HIP(hipHostMalloc((void**)&c.status, sizeof(EgStatus), hipHostMallocMapped));
-    EAO_HIP(hipEventCreate(&c.ev0));
-    EAO_HIP(hipEventCreate(&c.ev1));
-    EAO_HIP(create_stream(&c.stream, StreamClass::Bulk));      // the stream class of the map bundle adjustment: LoopClosing's thread
-    return EAO_OK;
-}
 
 bool finite_rows(const double* a, size_t cnt) {
     for (size_t i = 0; i < cnt; i++) if (!std::isfinite(a[i])) return false;
@@ -572,7 +554,7 @@ struct EgLayout {
         work = a.take<int4>(pl ? std::max<size_t>(pl->work.size(), 1) : 1);
         sb = a.take<int4>(pl ? std::max<size_t>(pl->sb.size(), 1) : 1);
         diagList = a.take<int>(pl ? std::max<size_t>(pl->diagList.size(), 1) : 1);
-        upEnd = (a.off + 255) & ~(size_t)255;
+        upEnd = align256(a.off);
         D.C = a.take<Sim3>(m1);
         D.e = a.take<double>((size_t)m1 * 7); D.Ji = a.take<double>((size_t)m1 * 49); D.Jj = a.take<double>((size_t)m1 * 49); D.echi = a.take<double>(m1);
         D.Hblk = a.take<double>((size_t)b1 * 49); D.bvec = a.take<double>((size_t)f1 * 7);
@@ -583,7 +565,7 @@ struct EgLayout {
         bigDiag = a.take<double>(std::max<size_t>((size_t)N * kBigNB, 8));
         bigLinv = a.take<double>(std::max<size_t>((size_t)N * kBigNB, 8));
         bigFail = a.take<int>(4);
-        scratchEnd = (a.off + 255) & ~(size_t)255;
+        scratchEnd = align256(a.off);
         D.outS = a.take<double>((size_t)n * 8);
         outOff = (size_t)((unsigned char*)D.outS - base);
         D.outT = a.take<float>((size_t)n * 16); D.outX = a.take<float>((size_t)p1 * 3);
@@ -600,7 +582,8 @@ eao_status run_essential_graph(const eao_essential_graph_problem* p, eao_essenti
     GbaPlan& pl = c.plan;
     if ((st = eg_structure(p, g, pl))) return st;      // (the capacity error included: before the device is touched and before anything is written)
     const int nf = g.nf, nBlocks = g.nBlocks;
-    if ((st = eg_ctx_init(c))) return st;
+    if ((st = c.ready(StreamClass::Bulk)) || (st = c.timing())) return st;
+    if (!c.status) EAO_HIP(hipHostMalloc((void**)&c.status, sizeof(EgStatus), hipHostMallocMapped));
     if ((st = gba_attributes())) return st;
     const bool solve = nf > 0 && m > 0;
     const int N = solve ? pl.N : 0;

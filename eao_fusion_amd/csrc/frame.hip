@@ -98,34 +98,12 @@ __global__ __launch_bounds__(256) void k_stereo_from_rgbd(int n, const float* __
     outDepth[i] = dz;
 }
 
-struct FCtx {   // per-thread workspace, grow-only
-    hipStream_t stream = nullptr;
+struct FCtx : eao::ThreadStream {   // per-thread workspace, grow-only
     eao::DevBuf<unsigned char> dev;
-    unsigned char* host = nullptr;   // pinned staging
-    size_t hostCap = 0;
-    eao_status pin(size_t need) {
-        if (need <= hostCap) return EAO_OK;
-        if (host) (void)hipHostFree(host);
-        host = nullptr; hostCap = 0;
-        const size_t cap = need + (need >> 2) + 4096;
-        EAO_HIP(hipHostMalloc((void**)&host, cap, hipHostMallocDefault));
-        hostCap = cap;
-        return EAO_OK;
-    }
-    eao_status ready() {
-        eao_status st = eao::require_device();
-        if (st) return st;
-        if (!stream) EAO_HIP(eao::create_stream(&stream, eao::StreamClass::Latency));
-        return EAO_OK;
-    }
-    ~FCtx() {
-        if (host) (void)hipHostFree(host);
-        if (stream) (void)hipStreamDestroy(stream);
-    }
+    eao::PinBuf<hipHostMallocDefault> host;   // pinned staging
 };
 thread_local FCtx g_fctx;
-
-inline size_t al256(size_t v) { return (v + 255) & ~(size_t)255; }
+using eao::align256;
 
 }  // namespace
 
@@ -139,26 +117,26 @@ eao_status eao_frame_is_in_frustum(const eao_frustum_frame* Fr, const eao_map_po
     EAO_REQUIRE(in_view && proj_x && proj_y && proj_xr && view_cos && pred_level, "null output array");
     EAO_REQUIRE(pts->Xw && pts->normal && pts->min_dist_inv && pts->max_dist_inv && pts->max_dist, "incomplete map-point arrays");
     FCtx& c = g_fctx;
-    eao_status st = c.ready();
+    eao_status st = c.ready(eao::StreamClass::Latency);
     if (st) return st;
     // staging: Xw normal (3n floats each) | min max num (n floats each)  ->  outputs: u v ur cos (n floats) | level (n int) | in_view (n)
-    const size_t fN = al256(4 * (size_t)n), f3 = al256(12 * (size_t)n);
+    const size_t fN = align256(4 * (size_t)n), f3 = align256(12 * (size_t)n);
     const size_t oX = 0, oN = f3, oMin = 2 * f3, oMax = oMin + fN, oNum = oMax + fN, inBytes = oNum + fN;
-    const size_t oU = inBytes, oV = oU + fN, oUr = oV + fN, oCos = oUr + fN, oLvl = oCos + fN, oIn = oLvl + fN, total = oIn + al256(n);
-    if ((st = c.pin(total))) return st;
+    const size_t oU = inBytes, oV = oU + fN, oUr = oV + fN, oCos = oUr + fN, oLvl = oCos + fN, oIn = oLvl + fN, total = oIn + align256(n);
+    if ((st = c.host.reserve(total))) return st;
     if ((st = c.dev.reserve(total))) return st;
-    std::memcpy(c.host + oX, pts->Xw, 12 * (size_t)n);
-    std::memcpy(c.host + oN, pts->normal, 12 * (size_t)n);
-    std::memcpy(c.host + oMin, pts->min_dist_inv, 4 * (size_t)n);
-    std::memcpy(c.host + oMax, pts->max_dist_inv, 4 * (size_t)n);
-    std::memcpy(c.host + oNum, pts->max_dist, 4 * (size_t)n);
+    std::memcpy(c.host.p + oX, pts->Xw, 12 * (size_t)n);
+    std::memcpy(c.host.p + oN, pts->normal, 12 * (size_t)n);
+    std::memcpy(c.host.p + oMin, pts->min_dist_inv, 4 * (size_t)n);
+    std::memcpy(c.host.p + oMax, pts->max_dist_inv, 4 * (size_t)n);
+    std::memcpy(c.host.p + oNum, pts->max_dist, 4 * (size_t)n);
     hipStream_t s = c.stream;
-    EAO_HIP(hipMemcpyAsync(c.dev.p, c.host, inBytes, hipMemcpyHostToDevice, s));
+    EAO_HIP(hipMemcpyAsync(c.dev.p, c.host.p, inBytes, hipMemcpyHostToDevice, s));
     // outputs of points that are not in view stay as the caller left them: seed the device copies with the caller's values
-    std::memcpy(c.host + oU, proj_x, 4 * (size_t)n); std::memcpy(c.host + oV, proj_y, 4 * (size_t)n);
-    std::memcpy(c.host + oUr, proj_xr, 4 * (size_t)n); std::memcpy(c.host + oCos, view_cos, 4 * (size_t)n);
-    std::memcpy(c.host + oLvl, pred_level, 4 * (size_t)n);
-    EAO_HIP(hipMemcpyAsync(c.dev.p + oU, c.host + oU, oIn - oU, hipMemcpyHostToDevice, s));
+    std::memcpy(c.host.p + oU, proj_x, 4 * (size_t)n); std::memcpy(c.host.p + oV, proj_y, 4 * (size_t)n);
+    std::memcpy(c.host.p + oUr, proj_xr, 4 * (size_t)n); std::memcpy(c.host.p + oCos, view_cos, 4 * (size_t)n);
+    std::memcpy(c.host.p + oLvl, pred_level, 4 * (size_t)n);
+    EAO_HIP(hipMemcpyAsync(c.dev.p + oU, c.host.p + oU, oIn - oU, hipMemcpyHostToDevice, s));
     FrustumArgs A;
     A.n = n;
     A.Xw = (const float*)(c.dev.p + oX); A.normal = (const float*)(c.dev.p + oN); A.minDist = (const float*)(c.dev.p + oMin);
@@ -174,12 +152,12 @@ eao_status eao_frame_is_in_frustum(const eao_frustum_frame* Fr, const eao_map_po
     A.projX = (float*)(c.dev.p + oU); A.projY = (float*)(c.dev.p + oV); A.projXR = (float*)(c.dev.p + oUr);
     A.viewCos = (float*)(c.dev.p + oCos); A.level = (int*)(c.dev.p + oLvl); A.inView = c.dev.p + oIn;
     hipLaunchKernelGGL(k_is_in_frustum, dim3(eao::cdiv(n, 256)), dim3(256), 0, s, A);
-    EAO_HIP(hipMemcpyAsync(c.host + oU, c.dev.p + oU, total - oU, hipMemcpyDeviceToHost, s));
+    EAO_HIP(hipMemcpyAsync(c.host.p + oU, c.dev.p + oU, total - oU, hipMemcpyDeviceToHost, s));
     EAO_HIP(eao::wait_latency(s));
     EAO_HIP(hipGetLastError());
-    std::memcpy(proj_x, c.host + oU, 4 * (size_t)n); std::memcpy(proj_y, c.host + oV, 4 * (size_t)n);
-    std::memcpy(proj_xr, c.host + oUr, 4 * (size_t)n); std::memcpy(view_cos, c.host + oCos, 4 * (size_t)n);
-    std::memcpy(pred_level, c.host + oLvl, 4 * (size_t)n); std::memcpy(in_view, c.host + oIn, (size_t)n);
+    std::memcpy(proj_x, c.host.p + oU, 4 * (size_t)n); std::memcpy(proj_y, c.host.p + oV, 4 * (size_t)n);
+    std::memcpy(proj_xr, c.host.p + oUr, 4 * (size_t)n); std::memcpy(view_cos, c.host.p + oCos, 4 * (size_t)n);
+    std::memcpy(pred_level, c.host.p + oLvl, 4 * (size_t)n); std::memcpy(in_view, c.host.p + oIn, (size_t)n);
     return EAO_OK;
 }
 
@@ -192,25 +170,25 @@ eao_status eao_assign_features_to_grid(int32_t n, const float* kp_x, const float
     if (n == 0) { for (int c = 0; c <= nCells; c++) cell_start[c] = 0; return EAO_OK; }
     EAO_REQUIRE(kp_x && kp_y && items, "null keypoint arrays");
     FCtx& c = g_fctx;
-    eao_status st = c.ready();
+    eao_status st = c.ready(eao::StreamClass::Latency);
     if (st) return st;
     int npow2 = 64;
     while (npow2 < n) npow2 <<= 1;
-    const size_t fN = al256(4 * (size_t)n), oX = 0, oY = fN, oS = 2 * fN, oI = oS + al256(4 * (size_t)(nCells + 1)), total = oI + fN;
-    if ((st = c.pin(total))) return st;
+    const size_t fN = align256(4 * (size_t)n), oX = 0, oY = fN, oS = 2 * fN, oI = oS + align256(4 * (size_t)(nCells + 1)), total = oI + fN;
+    if ((st = c.host.reserve(total))) return st;
     if ((st = c.dev.reserve(total))) return st;
-    std::memcpy(c.host + oX, kp_x, 4 * (size_t)n); std::memcpy(c.host + oY, kp_y, 4 * (size_t)n);
+    std::memcpy(c.host.p + oX, kp_x, 4 * (size_t)n); std::memcpy(c.host.p + oY, kp_y, 4 * (size_t)n);
     hipStream_t s = c.stream;
-    EAO_HIP(hipMemcpyAsync(c.dev.p, c.host, oS, hipMemcpyHostToDevice, s));
+    EAO_HIP(hipMemcpyAsync(c.dev.p, c.host.p, oS, hipMemcpyHostToDevice, s));
     const size_t lds = (size_t)npow2 * sizeof(unsigned);
     EAO_HIP(hipFuncSetAttribute((const void*)k_grid_assign, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     hipLaunchKernelGGL(k_grid_assign, dim3(1), dim3(kGridThreads), lds, s, n, (const float*)(c.dev.p + oX), (const float*)(c.dev.p + oY),
                        min_x, min_y, grid_inv_w, grid_inv_h, cols, rows, npow2, (int*)(c.dev.p + oS), (int*)(c.dev.p + oI));
-    EAO_HIP(hipMemcpyAsync(c.host + oS, c.dev.p + oS, total - oS, hipMemcpyDeviceToHost, s));
+    EAO_HIP(hipMemcpyAsync(c.host.p + oS, c.dev.p + oS, total - oS, hipMemcpyDeviceToHost, s));
     EAO_HIP(eao::wait_latency(s));
     EAO_HIP(hipGetLastError());
-    std::memcpy(cell_start, c.host + oS, 4 * (size_t)(nCells + 1));
-    std::memcpy(items, c.host + oI, 4 * (size_t)cell_start[nCells]);
+    std::memcpy(cell_start, c.host.p + oS, 4 * (size_t)(nCells + 1));
+    std::memcpy(items, c.host.p + oI, 4 * (size_t)cell_start[nCells]);
     return EAO_OK;
 }
 
@@ -223,23 +201,23 @@ eao_status eao_compute_stereo_from_rgbd(int32_t n, const float* kp_x, const floa
     for (int i = 0; i < n; i++)   // cv::Mat::at does not check either: a keypoint outside the image is a caller bug, refuse it
         EAO_REQUIRE((int)kp_x[i] >= 0 && (int)kp_x[i] < width && (int)kp_y[i] >= 0 && (int)kp_y[i] < height, "keypoint %d outside the depth image", i);
     FCtx& c = g_fctx;
-    eao_status st = c.ready();
+    eao_status st = c.ready(eao::StreamClass::Latency);
     if (st) return st;
-    const size_t fN = al256(4 * (size_t)n), img = depth_on_device ? 0 : al256(4 * (size_t)pitch * height);
+    const size_t fN = align256(4 * (size_t)n), img = depth_on_device ? 0 : align256(4 * (size_t)pitch * height);
     const size_t oX = 0, oY = fN, oU = 2 * fN, oD = 3 * fN, inBytes = oD + img, oUr = inBytes, oZ = oUr + fN, total = oZ + fN;
-    if ((st = c.pin(total))) return st;
+    if ((st = c.host.reserve(total))) return st;
     if ((st = c.dev.reserve(total))) return st;
-    std::memcpy(c.host + oX, kp_x, 4 * (size_t)n); std::memcpy(c.host + oY, kp_y, 4 * (size_t)n); std::memcpy(c.host + oU, kpu_x, 4 * (size_t)n);
-    if (!depth_on_device) std::memcpy(c.host + oD, depth, 4 * (size_t)pitch * height);
+    std::memcpy(c.host.p + oX, kp_x, 4 * (size_t)n); std::memcpy(c.host.p + oY, kp_y, 4 * (size_t)n); std::memcpy(c.host.p + oU, kpu_x, 4 * (size_t)n);
+    if (!depth_on_device) std::memcpy(c.host.p + oD, depth, 4 * (size_t)pitch * height);
     hipStream_t s = c.stream;
-    EAO_HIP(hipMemcpyAsync(c.dev.p, c.host, inBytes, hipMemcpyHostToDevice, s));
+    EAO_HIP(hipMemcpyAsync(c.dev.p, c.host.p, inBytes, hipMemcpyHostToDevice, s));
     const float* dDepth = depth_on_device ? depth : (const float*)(c.dev.p + oD);
     hipLaunchKernelGGL(k_stereo_from_rgbd, dim3(eao::cdiv(n, 256)), dim3(256), 0, s, n, (const float*)(c.dev.p + oX), (const float*)(c.dev.p + oY),
                        (const float*)(c.dev.p + oU), dDepth, pitch, mbf, (float*)(c.dev.p + oUr), (float*)(c.dev.p + oZ));
-    EAO_HIP(hipMemcpyAsync(c.host + oUr, c.dev.p + oUr, total - oUr, hipMemcpyDeviceToHost, s));
+    EAO_HIP(hipMemcpyAsync(c.host.p + oUr, c.dev.p + oUr, total - oUr, hipMemcpyDeviceToHost, s));
     EAO_HIP(eao::wait_latency(s));
     EAO_HIP(hipGetLastError());
-    std::memcpy(u_right, c.host + oUr, 4 * (size_t)n); std::memcpy(out_depth, c.host + oZ, 4 * (size_t)n);
+    std::memcpy(u_right, c.host.p + oUr, 4 * (size_t)n); std::memcpy(out_depth, c.host.p + oZ, 4 * (size_t)n);
     return EAO_OK;
 }
 
@@ -251,20 +229,20 @@ eao_status eao_undistort_keypoints(int32_t n, const float* kp_x, const float* kp
     eao::frame::Distortion D;
     eao::frame::fill_distortion(D, fx, fy, cx, cy, dist_coef, n_coef);
     FCtx& c = g_fctx;
-    eao_status st = c.ready();
+    eao_status st = c.ready(eao::StreamClass::Latency);
     if (st) return st;
-    const size_t fN = al256(4 * (size_t)n), total = 4 * fN;
-    if ((st = c.pin(total))) return st;
+    const size_t fN = align256(4 * (size_t)n), total = 4 * fN;
+    if ((st = c.host.reserve(total))) return st;
     if ((st = c.dev.reserve(total))) return st;
-    std::memcpy(c.host, kp_x, 4 * (size_t)n); std::memcpy(c.host + fN, kp_y, 4 * (size_t)n);
+    std::memcpy(c.host.p, kp_x, 4 * (size_t)n); std::memcpy(c.host.p + fN, kp_y, 4 * (size_t)n);
     hipStream_t s = c.stream;
-    EAO_HIP(hipMemcpyAsync(c.dev.p, c.host, 2 * fN, hipMemcpyHostToDevice, s));
+    EAO_HIP(hipMemcpyAsync(c.dev.p, c.host.p, 2 * fN, hipMemcpyHostToDevice, s));
     hipLaunchKernelGGL(k_undistort, dim3(eao::cdiv(n, 256)), dim3(256), 0, s, D, n, (const float*)c.dev.p, (const float*)(c.dev.p + fN), (float*)(c.dev.p + 2 * fN),
                        (float*)(c.dev.p + 3 * fN));
-    EAO_HIP(hipMemcpyAsync(c.host + 2 * fN, c.dev.p + 2 * fN, 2 * fN, hipMemcpyDeviceToHost, s));
+    EAO_HIP(hipMemcpyAsync(c.host.p + 2 * fN, c.dev.p + 2 * fN, 2 * fN, hipMemcpyDeviceToHost, s));
     EAO_HIP(eao::wait_latency(s));
     EAO_HIP(hipGetLastError());
-    std::memcpy(out_x, c.host + 2 * fN, 4 * (size_t)n); std::memcpy(out_y, c.host + 3 * fN, 4 * (size_t)n);
+    std::memcpy(out_x, c.host.p + 2 * fN, 4 * (size_t)n); std::memcpy(out_y, c.host.p + 3 * fN, 4 * (size_t)n);
     return EAO_OK;
 }
 

@@ -434,8 +434,7 @@ __global__ __launch_bounds__(256) void k_kf_upload(const uint4* __restrict__ src
 }
 
 using PinBuf = eao::PinBuf<hipHostMallocMapped>;   // kernels read and write it in place through .d
-struct Ctx {   // per host thread, grow-only
-    hipStream_t stream = nullptr;
+struct Ctx : eao::ThreadStream {   // per host thread, grow-only; the events, under EAO_TRI_EVENTS=1: around the triangulation launches (tools/bench_triangulation.py)
     PinBuf in, out;
     eao::DevBuf<int2> match;
     eao::DevBuf<unsigned char> dev;
@@ -443,16 +442,14 @@ struct Ctx {   // per host thread, grow-only
     int ticketNext = 0;
     PinBuf doneWord;
     PinBuf tri;                    // eao_kf_create_new_map_points: [verdicts | points] in mapped host memory
-    hipEvent_t triEv[2] = {nullptr, nullptr};      // EAO_TRI_EVENTS=1: around the triangulation launches (tools/bench_triangulation.py)
     float triMs = -1.f;
-    long long* dbg = nullptr;
+    eao::DevBuf<long long> dbg;
     int seq = 0;
     int gen = 0;
-    ~Ctx() { if (stream) (void)hipStreamDestroy(stream); }
 };
 thread_local Ctx g_kctx;
 
-inline size_t al256(size_t v) { return (v + 255) & ~(size_t)255; }
+using eao::align256;
 
 }  // namespace
 
@@ -543,24 +540,24 @@ eao_status eao_keyframe_create(const eao_frame_view* F, const eao_feature_vector
     }
     // one device block
     const size_t n1 = std::max(n, 1), no1 = std::max(no, 1), nn1 = std::max(nn, 1), ni = std::max<size_t>(h->index.size(), 1);
-    size_t off = al256(sizeof(KfDev));
-    const size_t oKx = off; off = al256(off + 4 * n1);
-    const size_t oKy = off; off = al256(off + 4 * n1);
-    const size_t oUr = off; off = al256(off + 4 * n1);
-    const size_t oAn = off; off = al256(off + 4 * n1);
-    const size_t oOc = off; off = al256(off + 4 * n1);
-    const size_t oDe = off; off = al256(off + 32 * n1);
-    const size_t oOr = off; off = al256(off + 4 * no1);
-    const size_t oCx = off; off = al256(off + 2 * no1);
-    const size_t oCy = off; off = al256(off + 2 * no1);
-    const size_t oCs = off; off = al256(off + 4 * (size_t)(cols + 1));
-    const size_t oOcc = off; off = al256(off + n1);
-    const size_t oNi = off; off = al256(off + 4 * nn1);
-    const size_t oNs = off; off = al256(off + 4 * (nn1 + 1));
-    const size_t oIx = off; off = al256(off + 4 * ni);
-    const size_t oSf = off; off = al256(off + 4 * (size_t)nl);
-    const size_t oS2 = off; off = al256(off + 4 * (size_t)nl);
-    const size_t oI2 = off; off = al256(off + 4 * (size_t)nl);
+    size_t off = align256(sizeof(KfDev));
+    const size_t oKx = off; off = align256(off + 4 * n1);
+    const size_t oKy = off; off = align256(off + 4 * n1);
+    const size_t oUr = off; off = align256(off + 4 * n1);
+    const size_t oAn = off; off = align256(off + 4 * n1);
+    const size_t oOc = off; off = align256(off + 4 * n1);
+    const size_t oDe = off; off = align256(off + 32 * n1);
+    const size_t oOr = off; off = align256(off + 4 * no1);
+    const size_t oCx = off; off = align256(off + 2 * no1);
+    const size_t oCy = off; off = align256(off + 2 * no1);
+    const size_t oCs = off; off = align256(off + 4 * (size_t)(cols + 1));
+    const size_t oOcc = off; off = align256(off + n1);
+    const size_t oNi = off; off = align256(off + 4 * nn1);
+    const size_t oNs = off; off = align256(off + 4 * (nn1 + 1));
+    const size_t oIx = off; off = align256(off + 4 * ni);
+    const size_t oSf = off; off = align256(off + 4 * (size_t)nl);
+    const size_t oS2 = off; off = align256(off + 4 * (size_t)nl);
+    const size_t oI2 = off; off = align256(off + 4 * (size_t)nl);
     std::vector<unsigned char> hb(off, 0);
     if (hipMalloc((void**)&h->dev, off) != hipSuccess) { delete h; eao::set_error("hipMalloc of %zu bytes failed", off); return EAO_ERR_NO_DEVICE; }
     unsigned char* dv = h->dev;
@@ -614,7 +611,7 @@ eao_status eao_keyframe_set_depth(eao_keyframe* h, const float* depth, const flo
     const size_t n = (size_t)h->D.n;
     EAO_REQUIRE(n == 0 || depth, "depth missing");
     EAO_REQUIRE(!raw_x == !raw_y, "raw_x and raw_y come together");
-    const size_t seg = al256(4 * std::max<size_t>(n, 1));
+    const size_t seg = align256(4 * std::max<size_t>(n, 1));
     if (!h->devDepth && hipMalloc((void**)&h->devDepth, 3 * seg) != hipSuccess) { h->devDepth = nullptr; eao::set_error("hipMalloc of %zu bytes failed", 3 * seg); return EAO_ERR_NO_DEVICE; }
     h->depth.assign(depth, depth + n);
     if (raw_x) { h->rawx.assign(raw_x, raw_x + n); h->rawy.assign(raw_y, raw_y + n); }
@@ -634,13 +631,6 @@ int32_t eao_keyframe_size(const eao_keyframe* h) { return h ? h->D.n : -1; }
 
 namespace {
 
-eao_status ctx_ready(Ctx& c) {
-    eao_status st = eao::require_device();
-    if (st) return st;
-    if (!c.stream) EAO_HIP(eao::create_stream(&c.stream, eao::StreamClass::Latency));
-    return EAO_OK;
-}
-
 // eao_kf_create_new_map_points: the triangulation of csrc/triangulate.hip enqueued behind the search's last launch, over the table the finish kernel wrote
 struct TriTail { const eao_tri_camera* cam1; const eao_tri_camera* cams2; float ratioFactor; int32_t* verdict; float* x3d; };
 
@@ -657,7 +647,7 @@ eao_status run_nodes(int mode, const eao_keyframe* k1, int nProb, const eao_keyf
                      const uint8_t* valid1, const uint8_t* valid2, float nnratio, int onlyStereo, int checkOrientation, int32_t* match12, int32_t* nmatches,
                      const TriTail* tail = nullptr) {
     Ctx& c = g_kctx;
-    eao_status st = ctx_ready(c);
+    eao_status st = c.ready(eao::StreamClass::Latency);
     if (st) return st;
     const int n1 = k1->D.n;
     if (n1 == 0 || nProb == 0) { for (int p = 0; p < nProb; p++) nmatches[p] = 0; return EAO_OK; }
@@ -670,13 +660,13 @@ eao_status run_nodes(int mode, const eao_keyframe* k1, int nProb, const eao_keyf
     if (c.gen == 0x7FFFFFFF) { EAO_HIP(hipMemsetAsync(c.match.p, 0, c.match.n * sizeof(int2), c.stream)); c.gen = 0; }
     c.gen++;
     // mapped input block: the BoW validity flags; mapped output block: [counts | tables]
-    const size_t oV1 = 0, oV2 = al256((size_t)n1), inBytes = oV2 + al256(valid2 ? (size_t)k2s[0]->D.n : 1);
+    const size_t oV1 = 0, oV2 = align256((size_t)n1), inBytes = oV2 + align256(valid2 ? (size_t)k2s[0]->D.n : 1);
     if ((st = c.in.reserve(inBytes))) return st;
     if (valid1) std::memcpy(c.in.p + oV1, valid1, n1);
     if (valid2) std::memcpy(c.in.p + oV2, valid2, k2s[0]->D.n);
-    const size_t oTab = al256(4 * (size_t)nProb);
+    const size_t oTab = align256(4 * (size_t)nProb);
     if ((st = c.out.reserve(oTab + 4 * cells))) return st;
-    const size_t oX3 = al256(4 * cells);
+    const size_t oX3 = align256(4 * cells);
     if (tail && (st = c.tri.reserve(oX3 + 12 * cells))) return st;
     if (!c.ticket.p) {
         if ((st = c.ticket.reserve(1))) return st;
@@ -695,8 +685,8 @@ eao_status run_nodes(int mode, const eao_keyframe* k1, int nProb, const eao_keyf
         A.valid1 = valid1 ? c.in.d + oV1 : nullptr; A.valid2 = valid2 ? c.in.d + oV2 : nullptr;
         A.match = c.match.p + (size_t)p0 * n1; A.gen = c.gen; A.n1 = n1;
         static const bool envStamps = getenv("EAO_DEBUG_STAMPS") && atoi(getenv("EAO_DEBUG_STAMPS"));
-        if (envStamps && !c.dbg) EAO_HIP(hipMalloc((void**)&c.dbg, 64 * sizeof(long long)));
-        A.dbg = c.dbg;
+        if (envStamps && (st = c.dbg.reserve(64))) return st;
+        A.dbg = c.dbg.p;
         A.single = 0;
         if (nProb == 1 && k1->D.nNodes <= kPairCap && k2s[0]->D.nNodes < 32768) {
             A.single = 1;
@@ -745,9 +735,9 @@ eao_status run_nodes(int mode, const eao_keyframe* k1, int nProb, const eao_keyf
         // the events are a diagnostic: the kernels above are enqueued and write into this thread's mapped buffers, so nothing here returns before the wait --
         // an event call that fails only costs the measurement (triMs stays -1)
         bool ev = envEvents;
-        for (int e = 0; ev && e < 2; e++)
-            if (!c.triEv[e]) ev = hipEventCreate(&c.triEv[e]) == hipSuccess;
-        ev = ev && hipEventRecord(c.triEv[0], c.stream) == hipSuccess;
+        for (hipEvent_t* e : {&c.ev0, &c.ev1})
+            if (ev && !*e) ev = hipEventCreate(e) == hipSuccess;
+        ev = ev && hipEventRecord(c.ev0, c.stream) == hipSuccess;
         if (envEvents && !ev) (void)hipGetLastError();      // (not a launch error of the kernels below)
         const eao::tri::Side S1 = tri_side(k1);
         for (int p0 = 0; p0 < nProb; p0 += eao::tri::kMaxProb) {
@@ -761,10 +751,10 @@ eao_status run_nodes(int mode, const eao_keyframe* k1, int nProb, const eao_keyf
             eao::tri::launch(c.stream, S1, *tail->cam1, tail->ratioFactor, np, P, (int*)c.tri.d + (size_t)p0 * n1, (float*)(c.tri.d + oX3) + (size_t)p0 * n1 * 3);
         }
         const hipError_t triErr = hipGetLastError();
-        ev = ev && hipEventRecord(c.triEv[1], c.stream) == hipSuccess;
+        ev = ev && hipEventRecord(c.ev1, c.stream) == hipSuccess;
         EAO_HIP(eao::wait_latency(c.stream));
         EAO_HIP(triErr);
-        if (!(ev && hipEventElapsedTime(&c.triMs, c.triEv[0], c.triEv[1]) == hipSuccess)) c.triMs = -1.f;
+        if (!(ev && hipEventElapsedTime(&c.triMs, c.ev0, c.ev1) == hipSuccess)) c.triMs = -1.f;
         if (envEvents && !ev) (void)hipGetLastError();      // (a failed event call is not this call's failure)
         seen = true;
     }
@@ -777,9 +767,9 @@ eao_status run_nodes(int mode, const eao_keyframe* k1, int nProb, const eao_keyf
         EAO_HIP(hipMemsetAsync(c.ticket.p, 0, sizeof(int), c.stream)); EAO_HIP(eao::wait_latency(c.stream)); c.ticketNext = 0;
     }
     EAO_HIP(hipGetLastError());
-    if (c.dbg) {
+    if (c.dbg.p) {
         long long st[8];
-        EAO_HIP(hipMemcpy(st, c.dbg, sizeof(st), hipMemcpyDeviceToHost));
+        EAO_HIP(hipMemcpy(st, c.dbg.p, sizeof(st), hipMemcpyDeviceToHost));
         fprintf(stderr, "[eao kf nodes stamps] node 0 (%lld x %lld features): head %lld, side 2 in registers %lld, side 1 in registers %lld, walk %lld ticks of 10 ns\n", st[6], st[7],
                 st[1] - st[0], st[2] - st[1], st[3] - st[2], st[4] - st[3]);
     }
@@ -882,12 +872,12 @@ eao_status eao_kf_fuse_search(int32_t n_kf, const eao_keyframe* const* kfs, int3
     }
     if (n == 0) return EAO_OK;
     Ctx& c = g_kctx;
-    eao_status st = ctx_ready(c);
+    eao_status st = c.ready(eao::StreamClass::Latency);
     if (st) return st;
     // the points: one staging block in mapped memory, one upload kernel
     const size_t N = n;
-    const size_t oAc = 0, oXw = al256(N), oNr = al256(oXw + 12 * N), oMn = al256(oNr + 12 * N), oMx = al256(oMn + 4 * N), oDr = al256(oMx + 4 * N), oDe = al256(oDr + 4 * N),
-                 bytes = al256(oDe + 32 * N);
+    const size_t oAc = 0, oXw = align256(N), oNr = align256(oXw + 12 * N), oMn = align256(oNr + 12 * N), oMx = align256(oMn + 4 * N), oDr = align256(oMx + 4 * N), oDe = align256(oDr + 4 * N),
+                 bytes = align256(oDe + 32 * N);
     if ((st = c.in.reserve(bytes))) return st;
     if ((st = c.dev.reserve(bytes))) return st;
     unsigned char* hb = c.in.p;

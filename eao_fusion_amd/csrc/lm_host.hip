@@ -471,7 +471,7 @@ struct BAJob {
         double* dpl0 = a.take<double>((size_t)nPl * 4 + 1);
         double* dpmeas = a.take<double>((size_t)Epl * 4 + 1);
         dW = a.take<BADev>(2);
-        const size_t off1 = (a.off + 255) & ~(size_t)255;
+        const size_t off1 = eao::align256(a.off);
         // ---- device-only part
         int* dtable = bigPath ? nullptr : a.take<int>((size_t)nP * nC);      // (the map-scale path finds a landmark's edges in its pair lists)
         int* dlpPts = a.take<int>(bigPath ? lpEntries : 1);                  // (filled by k_bal_pair_fill)
@@ -522,25 +522,15 @@ struct BAJob {
         D.camsBuf[0] = dcams; D.camsBuf[1] = dcamsT; D.ptsBuf[0] = dpts; D.ptsBuf[1] = dptsT;
         D.ctl0 = dctl; D.ctl = dctl; D.lm = D.lm0;
         D.status = c.status;
-        if (c.pinCap < off1) {
-            if (c.pin) (void)hipHostFree(c.pin);
-            c.pin = nullptr; c.pinCap = 0;
-            EAO_HIP(hipHostMalloc((void**)&c.pin, off1 + (off1 >> 2), hipHostMallocDefault));
-            c.pinCap = off1 + (off1 >> 2);
-        }
+        if ((st = c.pin.reserve(off1))) return st;
         const size_t outBytes = (size_t)nC * sizeof(SE3) + (size_t)nP * 24 + (size_t)nPl * 32 + (((size_t)E + 15) & ~(size_t)15) + 64;
-        if (c.pinOutCap < outBytes) {
-            if (c.pinOut) (void)hipHostFree(c.pinOut);
-            c.pinOut = nullptr; c.pinOutCap = 0;
-            EAO_HIP(hipHostMalloc((void**)&c.pinOut, outBytes + (outBytes >> 2), hipHostMallocMapped));
-            c.pinOutCap = outBytes + (outBytes >> 2);
-        }
-        outCams = (SE3*)c.pinOut;
-        outPts = (double*)(c.pinOut + (((size_t)nC * sizeof(SE3) + 15) & ~(size_t)15));
+        if ((st = c.pinOut.reserve(outBytes))) return st;
+        outCams = (SE3*)c.pinOut.p;
+        outPts = (double*)(c.pinOut.p + (((size_t)nC * sizeof(SE3) + 15) & ~(size_t)15));
         outPlanes = outPts + (size_t)nP * 3;
         outCls = (unsigned char*)(outPlanes + (size_t)nPl * 4);
         D.outCams = outCams; D.outPts = outPts; D.outPlanes = outPlanes; D.outCls = outCls;
-        auto hostp = [&](const void* dev) { return c.pin + ((const unsigned char*)dev - a.base); };
+        auto hostp = [&](const void* dev) { return c.pin.p + ((const unsigned char*)dev - a.base); };
         size_t offSplit = off0;
         {
             unsigned char* const hf = (unsigned char*)hostp(dflag);      // edge flags: bit0 stereo, bit2 robust kernel present (bit1 = level 1 is only ever set on the device)
@@ -578,7 +568,7 @@ struct BAJob {
             // the active structure below; the structure follows in a second copy.
             offSplit = (size_t)((unsigned char*)dcamIdx - a.base) & ~(size_t)255;
             hs_lap(1);
-            if (!deferUpload) EAO_HIP(hipMemcpyAsync(a.base + off0, c.pin + off0, offSplit - off0, hipMemcpyHostToDevice, s));
+            if (!deferUpload) EAO_HIP(hipMemcpyAsync(a.base + off0, c.pin.p + off0, offSplit - off0, hipMemcpyHostToDevice, s));
             // ---- active structure: SparseOptimizer::initializeOptimization(level 0) + buildIndexMapping
             int* camIdx = (int*)hostp(dcamIdx); int* ptIdx = (int*)hostp(dptIdx);
             int* actCam = (int*)hostp(dactCam); int* actPt = (int*)hostp(dactPt);
@@ -732,8 +722,8 @@ struct BAJob {
         d.bigArgs = BigStepArgs{D.big, D.bigL, D.bigDiag, D.bigFail, D.bigWork, D.ctl0, D.dbg, d.gB.N, 0, {}};
         // the window record itself travels with the structure
         write_records((BADev*)hostp(dW));
-        if (!deferUpload) EAO_HIP(hipMemcpyAsync(a.base + offSplit, c.pin + offSplit, off1 - offSplit, hipMemcpyHostToDevice, s));
-        else { upSrc = c.pin + off0; upDst = a.base + off0; upBytes = (off1 - off0 + 15) & ~(size_t)15; }
+        if (!deferUpload) EAO_HIP(hipMemcpyAsync(a.base + offSplit, c.pin.p + offSplit, off1 - offSplit, hipMemcpyHostToDevice, s));
+        else { upSrc = c.pin.p + off0; upDst = a.base + off0; upBytes = (off1 - off0 + 15) & ~(size_t)15; }
         L.W = dW; L.nz = 1; L.s = s; L.seq = c.status->seq;
         c.status->ph[0].touched = c.status->ph[1].touched = 0;
         // map-scale runs (tens of milliseconds) are NOT enqueued speculatively when the caller can abort them: optimize() then

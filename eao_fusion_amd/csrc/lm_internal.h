@@ -248,10 +248,8 @@ struct LMContext {  // per-thread device workspace, grow-only
     hipStream_t byClass[3] = {nullptr, nullptr, nullptr};      // eao::StreamClass: PoseOptimization / LocalBundleAdjustment / map BundleAdjustment of this host thread
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
     BAStatus* status = nullptr;   // pinned + mapped
-    unsigned char* pin = nullptr; // pinned host mirror of the input part of the arena: ONE H2D copy per upload
-    size_t pinCap = 0;
-    unsigned char* pinOut = nullptr;   // pinned results, written by k_ba_finish
-    size_t pinOutCap = 0;
+    eao::PinBuf<hipHostMallocDefault> pin;     // pinned host mirror of the input part of the arena: ONE H2D copy per upload
+    eao::PinBuf<hipHostMallocMapped> pinOut;   // pinned results, written by k_ba_finish (which is handed the block's host address)
     eao::DevBuf<unsigned char> bytes;
     std::vector<int> scratch;     // host counters of the structure build (kept to avoid per-call allocation)
     // map-scale path: where every 32-column panel's work records start / the records themselves, as the HOST reads them when it enqueues the panel launches --
@@ -262,8 +260,6 @@ struct LMContext {  // per-thread device workspace, grow-only
     size_t used = 0;
     ~LMContext() {
         if (status) (void)hipHostFree(status);
-        if (pin) (void)hipHostFree(pin);
-        if (pinOut) (void)hipHostFree(pinOut);
         if (ev0) (void)hipEventDestroy(ev0);
         if (ev1) (void)hipEventDestroy(ev1);
         for (hipStream_t q : byClass) if (q) (void)hipStreamDestroy(q);
@@ -278,7 +274,7 @@ struct Arena {
     size_t cap, off = 0;
     template <typename T>
     T* take(size_t n) {
-        off = (off + 255) & ~(size_t)255;
+        off = eao::align256(off);
         T* p = reinterpret_cast<T*>(base + off);
         off += n * sizeof(T);
         return p;

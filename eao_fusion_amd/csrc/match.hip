@@ -24,6 +24,7 @@
 
 using eao::match::Query;
 using eao::match::Lists;
+using eao::align256;
 
 namespace {
 
@@ -191,20 +192,13 @@ __global__ __launch_bounds__(256) void k_match_candidates(FrameDev F, const Quer
 }
 
 using PinBuf = eao::PinBuf<hipHostMallocMapped>;   // device-visible: kernels write results straight into it
-struct HostView {   // what the old std::vector staging offered
-    PinBuf buf;
-    eao_status resize(size_t n) { return buf.reserve(n); }
-    unsigned char* data() { return buf.p; }
-};
-struct Ctx {   // per-thread workspace, grow-only
-    hipStream_t stream = nullptr;
+struct Ctx : eao::ThreadStream {   // per-thread workspace, grow-only
     eao::DevBuf<unsigned char> dev;
-    HostView host;           // pinned staging of everything uploaded: ONE asynchronous H2D copy per call
+    PinBuf host;             // pinned staging of everything uploaded: ONE asynchronous H2D copy per call
     PinBuf out;              // candidate items, written by the kernel over PCIe (zero-copy), read after the stream sync
     eao::DevBuf<int> metaDev; // segStart[nq], segCount[nq], cursor (device: the cursor is an atomic)
     PinBuf meta;             // their pinned copy (asynchronous D2H in the same stream)
     std::vector<int> cellOf, cellStart;      // scratch of the grid order's counting sort
-    ~Ctx() { if (stream) (void)hipStreamDestroy(stream); }
 };
 thread_local Ctx g_ctx;
 
@@ -216,10 +210,8 @@ thread_local Ctx g_ctx;
 eao_status eao::match::build_lists_multi(int nf, const eao_frame_view* const* Fs, const std::vector<Query>* qs, const uint8_t* const* qdescs, Lists* Ls,
                                          const Resident* const* res) {
     Ctx& c = g_ctx;
-    eao_status st = eao::require_device();
+    eao_status st = c.ready(eao::StreamClass::Latency);
     if (st) return st;
-    if (!c.stream) EAO_HIP(eao::create_stream(&c.stream, eao::StreamClass::Latency));
-    auto al = [](size_t v) { return (v + 255) & ~(size_t)255; };
     struct Ord { int cx, cy, i; };
     struct Plan { int n, nq, no; size_t oKx, oKy, oUr, oOc, oOr, oCx, oCy, oDe, oQ, oQd, oOut, oMeta; size_t outCap; std::vector<Ord> ord; };
     std::vector<Plan> plan(nf);
@@ -238,11 +230,11 @@ eao_status eao::match::build_lists_multi(int nf, const eao_frame_view* const* Fs
             EAO_REQUIRE(R->n == P.n, "resident frame %d holds %d keypoints, the view %d", f, R->n, P.n);
             P.no = R->no;
             const size_t no = std::max(P.no, 1), nq = P.nq;
-            P.oQ = off; off = al(off + sizeof(Query) * nq);
+            P.oQ = off; off = align256(off + sizeof(Query) * nq);
             int shared = -1;
             for (int g = 0; g < f && shared < 0; g++) if (plan[g].nq == P.nq && qdescs[g] == qdescs[f]) shared = g;
             if (shared >= 0) P.oQd = plan[shared].oQd;
-            else { P.oQd = off; off = al(off + 32 * nq); }
+            else { P.oQd = off; off = align256(off + 32 * nq); }
             P.outCap = nq * no;
             P.oOut = outOff; outOff += P.outCap;
             P.oMeta = metaOff; metaOff += 2 * nq + 1;
@@ -269,27 +261,27 @@ eao_status eao::match::build_lists_multi(int nf, const eao_frame_view* const* Fs
         P.no = (int)P.ord.size();
         const size_t n = P.n, no = std::max(P.no, 1), nq = P.nq;
         // per frame: kx ky ur (float n) | oct (int n) | order (int no) | cellx celly (u16 no) | desc (32 n) | queries | (qdesc unless shared with an earlier frame)
-        P.oKx = off; off = al(off + 4 * n);
-        P.oKy = off; off = al(off + 4 * n);
-        P.oUr = off; off = al(off + 4 * n);
-        P.oOc = off; off = al(off + 4 * n);
-        P.oOr = off; off = al(off + 4 * no);
-        P.oCx = off; off = al(off + 2 * no);
-        P.oCy = off; off = al(off + 2 * no);
-        P.oDe = off; off = al(off + 32 * n);
-        P.oQ = off; off = al(off + sizeof(Query) * nq);
+        P.oKx = off; off = align256(off + 4 * n);
+        P.oKy = off; off = align256(off + 4 * n);
+        P.oUr = off; off = align256(off + 4 * n);
+        P.oOc = off; off = align256(off + 4 * n);
+        P.oOr = off; off = align256(off + 4 * no);
+        P.oCx = off; off = align256(off + 2 * no);
+        P.oCy = off; off = align256(off + 2 * no);
+        P.oDe = off; off = align256(off + 32 * n);
+        P.oQ = off; off = align256(off + sizeof(Query) * nq);
         int shared = -1;
         for (int g = 0; g < f && shared < 0; g++) if (plan[g].nq == P.nq && qdescs[g] == qdescs[f]) shared = g;
         if (shared >= 0) P.oQd = plan[shared].oQd;
-        else { P.oQd = off; off = al(off + 32 * nq); }
+        else { P.oQd = off; off = align256(off + 32 * nq); }
         P.outCap = nq * no;
         P.oOut = outOff; outOff += P.outCap;
         P.oMeta = metaOff; metaOff += 2 * nq + 1;
     }
     if (off == 0) return EAO_OK;
     EAO_REQUIRE(outOff < ((size_t)1 << 31), "candidate lists too large (%zu entries)", outOff);
-    if ((st = c.host.resize(off))) return st;
-    unsigned char* hb = c.host.data();
+    if ((st = c.host.reserve(off))) return st;
+    unsigned char* hb = c.host.p;
     for (int f = 0; f < nf; f++) {
         const eao_frame_view* F = Fs[f];
         const Plan& P = plan[f];
@@ -374,20 +366,18 @@ __global__ __launch_bounds__(256) void k_pair_distances(const uint4* __restrict_
 eao_status eao::match::pair_distances(const uint8_t* descA, int nA, const uint8_t* descB, int nB, const std::vector<int>& ia,
                                       const std::vector<int>& ib, std::vector<unsigned short>& dist) {
     Ctx& c = g_ctx;
-    eao_status st = eao::require_device();
+    eao_status st = c.ready(eao::StreamClass::Latency);
     if (st) return st;
-    if (!c.stream) EAO_HIP(eao::create_stream(&c.stream, eao::StreamClass::Latency));
     const size_t np = ia.size();
     dist.assign(np, 0);
     if (np == 0) return EAO_OK;
-    auto al = [](size_t v) { return (v + 255) & ~(size_t)255; };
     size_t off = 0;
-    const size_t oA = off; off = al(off + 32 * (size_t)nA);
-    const size_t oB = off; off = al(off + 32 * (size_t)nB);
-    const size_t oP = off; off = al(off + 8 * np);
-    const size_t oD = off; off = al(off + 2 * np);
-    if ((st = c.host.resize(off))) return st;
-    unsigned char* hb = c.host.data();
+    const size_t oA = off; off = align256(off + 32 * (size_t)nA);
+    const size_t oB = off; off = align256(off + 32 * (size_t)nB);
+    const size_t oP = off; off = align256(off + 8 * np);
+    const size_t oD = off; off = align256(off + 2 * np);
+    if ((st = c.host.reserve(off))) return st;
+    unsigned char* hb = c.host.p;
     std::memcpy(hb + oA, descA, 32 * (size_t)nA);
     std::memcpy(hb + oB, descB, 32 * (size_t)nB);
     for (size_t k = 0; k < np; k++) { ((int*)(hb + oP))[2 * k] = ia[k]; ((int*)(hb + oP))[2 * k + 1] = ib[k]; }

@@ -1411,7 +1411,7 @@ eao_status enqueue_pyramid_export(eao_orb* h, int frame, int border) {
         L.dstPitch = (L.w + 2 * border + 63) & ~63;
         L.rowChunks = L.dstPitch / 16; L.chunkBase = chunks; L.dstOff = (long long)off;
         chunks += L.rowChunks * (L.h + 2 * border);
-        off = (off + (size_t)L.dstPitch * (L.h + 2 * border) + 255) & ~(size_t)255;
+        off = align256(off + (size_t)L.dstPitch * (L.h + 2 * border));
     }
     A.totalChunks = chunks;
     if (h->pinPyrCap < off) {
@@ -1509,14 +1509,13 @@ eao_status eao_compute_stereo_matches(eao_orb* left, eao_orb* right, int32_t fra
     if (!stw) stw = wait_last_extraction(right);
     if (stw) return stw;
     eao::DevBuf<unsigned char>& buf = left->d_stereo;
-    auto al = [](size_t v) { return (v + 255) & ~(size_t)255; };
     size_t off = 0;
-    const size_t oKl = off; off = al(off + sizeof(eao_keypoint) * (size_t)nl);
-    const size_t oKr = off; off = al(off + sizeof(eao_keypoint) * (size_t)nr);
-    const size_t oDl = off; off = al(off + 32 * (size_t)nl);
-    const size_t oDr = off; off = al(off + 32 * (size_t)nr);
-    const size_t oSc = off; off = al(off + 8 * (size_t)g.nlevels);
-    const size_t oOut = off; off = al(off + 12 * (size_t)nl);
+    const size_t oKl = off; off = eao::align256(off + sizeof(eao_keypoint) * (size_t)nl);
+    const size_t oKr = off; off = eao::align256(off + sizeof(eao_keypoint) * (size_t)nr);
+    const size_t oDl = off; off = eao::align256(off + 32 * (size_t)nl);
+    const size_t oDr = off; off = eao::align256(off + 32 * (size_t)nr);
+    const size_t oSc = off; off = eao::align256(off + 8 * (size_t)g.nlevels);
+    const size_t oOut = off; off = eao::align256(off + 12 * (size_t)nl);
     eao_status st = buf.reserve(off);
     if (st) return st;
     hipStream_t s = left->stream;

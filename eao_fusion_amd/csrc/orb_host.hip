@@ -37,7 +37,7 @@ eao_status build_geometry(eao_orb* h, int W, int H) {
         LevelGeom& L = g.L[l];
         L.pitch = (L.w + 63) & ~63;
         L.off = off;
-        off += ((L.pitch * ((L.h + kBlurRows - 1) / kBlurRows * kBlurRows)) + 255) & ~255;   // (padding rows: see k_blur7)
+        off += (int)align256((size_t)L.pitch * ((L.h + kBlurRows - 1) / kBlurRows * kBlurRows));   // (padding rows: see k_blur7)
         const int maxBX = L.w - kEdge + 3, maxBY = L.h - kEdge + 3;
         const float width = (float)(maxBX - kMinBorder), height = (float)(maxBY - kMinBorder);
         const int nCols = (int)(width / (float)refc::FAST_CELL), nRows = (int)(height / (float)refc::FAST_CELL);
@@ -182,7 +182,7 @@ eao_status build_geometry(eao_orb* h, int W, int H) {
         long long noff = 0;
         for (int l = 0; l < c.nlevels; l++) {
             g.L[l].nodeOff = noff;
-            noff += (((long long)g.L[l].listCap * (2 * sizeof(short4) + sizeof(int) * kQtNodeInts) + (long long)scanCap * sizeof(int)) + 255) & ~255LL;
+            noff += (long long)align256((size_t)g.L[l].listCap * (2 * sizeof(short4) + sizeof(int) * kQtNodeInts) + (size_t)scanCap * sizeof(int));
         }
         g.qtNodeFrameBytes = noff;
         h->quadLds = 0;
@@ -528,8 +528,8 @@ eao_status eao_orb_stream_create(eao_orb* h, int32_t width, int32_t height, int3
     h->sW = width; h->sH = height; h->sB = batch; h->sCap = g.totalKpCap; h->sPitch = g.L[0].pitch;
     const size_t B = batch, cap = h->sCap;
     h->sInBytes = B * (size_t)h->sPitch * height;
-    h->sOffK = (B * sizeof(int) + 255) & ~(size_t)255;
-    h->sOffD = (h->sOffK + B * cap * sizeof(eao_keypoint) + 255) & ~(size_t)255;
+    h->sOffK = eao::align256(B * sizeof(int));
+    h->sOffD = eao::align256(h->sOffK + B * cap * sizeof(eao_keypoint));
     h->sOutBytes = (h->sOffD + B * cap * 32 + 15) & ~(size_t)15;
     // Three plain streams.  HIP maps streams onto a few hardware queues and streams that share one run in submission order: with the
     // handle's eight unused lane streams in the way the upload stream shared a queue with the extraction's side stream and the next

@@ -2,6 +2,7 @@
 // the plane edges of src/g2oAddition/EdgePlane.h.  ONE persistent workgroup runs all 4 rounds x <= 10 LM iterations x <= 10 trials on the device (no host round trip):
 // per-edge 2x6 / 3x6 Jacobians in registers, fixed-order reductions of the 28 accumulators, the 6x6 LDL^T replicated per wave.  Shared pieces: lm_internal.h.
 #include "lm_internal.h"
+#include "chain_internal.h"
 
 namespace {
 
@@ -699,18 +700,29 @@ constexpr int kPoseWaves4 = 256;
 inline int pose_threads(int n) { return n <= 4 * kPoseWaves4 ? std::min(kPoseWaves4, std::max(64, (n + 63) / 64 * 64)) : kPoseThreads; }
 inline int pose_ept(int n) { return n <= kPoseWaves4 ? 1 : (n <= 2 * kPoseWaves4 ? 2 : 4); }
 inline int pose_class(int n) { return n <= kPoseWaves4 ? 0 : n <= 2 * kPoseWaves4 ? 1 : n <= 4 * kPoseWaves4 ? 2 : 3; }
+// The eight register variants: geometry class (pose_class) x plane edges -> the template arguments <EPT, PLANES, MAXT> of k_pose_optimization and
+// k_pose_optimization_batch, handed to f as integral constants.
+template <bool PLANES, typename F>
+inline void pose_variant_of(int cls, F&& f) {
+    using std::integral_constant;
+    const integral_constant<bool, PLANES> pl;
+    const integral_constant<int, kPoseWaves4> four;
+    switch (cls) {
+        case 0: f(integral_constant<int, 1>(), pl, four); break;
+        case 1: f(integral_constant<int, 2>(), pl, four); break;
+        case 2: f(integral_constant<int, 4>(), pl, four); break;
+        default: f(integral_constant<int, 4>(), pl, integral_constant<int, kPoseThreads>()); break;
+    }
+}
+template <typename F>
+inline void pose_variant(int cls, bool planes, F&& f) {
+    if (planes) pose_variant_of<true>(cls, f); else pose_variant_of<false>(cls, f);
+}
 inline void launch_pose_registers(const PoseDev& P, int n, bool planes, hipStream_t s) {
     const dim3 b(planes && n <= 4 * kPoseWaves4 ? std::max(pose_threads(n), std::min(kPoseWaves4, (13 * P.nPlanes + 63) / 64 * 64)) : pose_threads(n));
-    switch (pose_class(n) + (planes ? 4 : 0)) {
-        case 0: hipLaunchKernelGGL((k_pose_optimization<1, false, kPoseWaves4>), dim3(1), b, 0, s, P); break;
-        case 1: hipLaunchKernelGGL((k_pose_optimization<2, false, kPoseWaves4>), dim3(1), b, 0, s, P); break;
-        case 2: hipLaunchKernelGGL((k_pose_optimization<4, false, kPoseWaves4>), dim3(1), b, 0, s, P); break;
-        case 3: hipLaunchKernelGGL((k_pose_optimization<4, false, kPoseThreads>), dim3(1), b, 0, s, P); break;
-        case 4: hipLaunchKernelGGL((k_pose_optimization<1, true, kPoseWaves4>), dim3(1), b, 0, s, P); break;
-        case 5: hipLaunchKernelGGL((k_pose_optimization<2, true, kPoseWaves4>), dim3(1), b, 0, s, P); break;
-        case 6: hipLaunchKernelGGL((k_pose_optimization<4, true, kPoseWaves4>), dim3(1), b, 0, s, P); break;
-        default: hipLaunchKernelGGL((k_pose_optimization<4, true, kPoseThreads>), dim3(1), b, 0, s, P); break;
-    }
+    pose_variant(pose_class(n), planes, [&](auto ept, auto pl, auto maxt) {
+        hipLaunchKernelGGL((k_pose_optimization<decltype(ept)::value, decltype(pl)::value, decltype(maxt)::value>), dim3(1), b, 0, s, P);
+    });
 }
 
 // Generic variant: edges stay in global memory (frames with more than 4 * kPoseThreads correspondences).
@@ -748,7 +760,6 @@ __global__ __launch_bounds__(kPoseThreads) void k_pose_optimization_mem(PoseDev 
         }
         __syncthreads();
         const int active = s_active;
-        int lmNBad = 0;  // uniform copies of the LM state that only thread 0 updates live in LDS
         if (active) {
             bool ok = true;
             for (int it = 0; it < refc::POSE_ITS && ok; it++) {
@@ -933,7 +944,6 @@ __global__ __launch_bounds__(kPoseThreads) void k_pose_optimization_mem(PoseDev 
                 }
                 __syncthreads();
                 ok = !s_flag;
-                (void)lmNBad;
             }
         }
         // ---- inlier / outlier classification of every edge (src/Optimizer.cc:554-621)
@@ -968,6 +978,76 @@ __global__ __launch_bounds__(kPoseThreads) void k_pose_optimization_mem(PoseDev 
     if (t == 0) { *P.Tout = s_est; P.result[1] = s_iters; P.result[2] = s_ntrace; }
 }
 
+// ---------------------------------------------------------------------------------------------------------------------
+// Host side, shared by eao_pose_optimization, eao_pose_optimization_batch and the tracking chain's hook (enqueue_pose_device).
+
+// the part of a record that does not depend on where the edges live: camera, Huber deltas, start pose; everything else zero
+void pose_record(PoseDev& P, float fx, float fy, float cx, float cy, float bf, const float* Tcw0) {
+    std::memset((void*)&P, 0, sizeof(PoseDev));
+    P.T0 = se3_from_Tcw_f32(Tcw0);
+    P.cam.fx = fx; P.cam.fy = fy; P.cam.cx = cx; P.cam.cy = cy; P.cam.bf = bf; P.cam.bf_f = bf;
+    P.cam.deltaMono = (float)std::sqrt(refc::POSE_HUBER2_MONO); P.cam.deltaStereo = (float)std::sqrt(refc::POSE_HUBER2_STEREO);
+    P.deltaPlane = (float)std::sqrt(refc::PLANE_CHI2);
+}
+
+// one problem's uploaded slices of the arena
+struct PoseIn {
+    double *Xw, *obs, *info, *planes;
+    unsigned char* flags;
+    static PoseIn take(Arena& a, int n) {
+        PoseIn s;
+        s.Xw = a.take<double>((size_t)n * 3); s.obs = a.take<double>((size_t)n * 3); s.info = a.take<double>(n);
+        s.flags = a.take<unsigned char>(n); s.planes = a.take<double>((size_t)kPoseMaxPlanes * 10);
+        return s;
+    }
+    // the same slices of the arena's pinned host mirror
+    PoseIn mirror(const unsigned char* dev, unsigned char* pin) const {
+        auto h = [&](const void* q) { return pin + ((const unsigned char*)q - dev); };
+        return PoseIn{(double*)h(Xw), (double*)h(obs), (double*)h(info), (double*)h(planes), h(flags)};
+    }
+};
+// float -> double over one contiguous array (restrict-qualified and on its own, so that the host compiler vectorises it: the
+// interleaved per-correspondence loop it replaces ran scalar and was half of a 256-frame call's host time)
+inline void widen(double* __restrict dst, const float* __restrict src, size_t n) {
+    for (size_t i = 0; i < n; i++) dst[i] = (double)src[i];
+}
+// one problem's inputs into (the host mirror of) its slices: float32 -> double exactly as Converter / Eigen would promote them
+void pose_pack(const eao_pose_problem* p, const PoseIn& h) {
+    const int n = p->n;
+    widen(h.Xw, p->Xw, (size_t)n * 3); widen(h.obs, p->obs, (size_t)n * 3); widen(h.info, p->inv_sigma2, n);
+    for (int i = 0; i < n; i++) h.flags[i] = (unsigned char)((!(p->obs[3 * i + 2] < 0) ? 1 : 0) | 4);
+    eao::lm::pose_plane_records(p->n_planes, p->plane_world, p->plane_obs, p->plane_seen, h.planes);
+}
+
+// One problem's result block in mapped host memory, as the kernels write it: SE3 | 192 doubles of trace | 4 ints | kPoseMaxPlanes plane flags | n point flags
+struct PoseOut {
+    SE3* T; double* trace; int* res; unsigned char* planeOutlier; unsigned char* outlier;
+    static constexpr size_t kHead = (sizeof(SE3) + 15) & ~(size_t)15;
+    static size_t bytes(int n) { return (kHead + 192 * 8 + 16 + kPoseMaxPlanes + (size_t)n + 63) & ~(size_t)63; }
+    explicit PoseOut(unsigned char* base)
+        : T((SE3*)base), trace((double*)(base + kHead)), res((int*)(trace + 192)), planeOutlier((unsigned char*)(res + 4)), outlier(planeOutlier + kPoseMaxPlanes) {}
+    void clear(int n) const {      // (the memory variant of the kernel reads the flags before it first writes them)
+        std::memset(planeOutlier, 0, kPoseMaxPlanes + (size_t)n);
+        res[0] = res[1] = res[2] = res[3] = 0;
+    }
+    void read(const eao_pose_problem* p, eao_pose_result* r) const {
+        const SE3 Tout = *T;
+        std::memcpy(r->outlier, outlier, p->n);
+        if (p->n_planes) std::memcpy(r->plane_outlier, planeOutlier, p->n_planes);
+        se3_to_Tcw_f32(Tout, r->Tcw);
+        r->n_inliers = p->n + p->n_planes - res[0];
+        r->lm_iterations = res[1];
+    }
+};
+
+// the record of a host-staged problem: inputs in its arena slices, results into its block
+void pose_bind(PoseDev& P, const eao_pose_problem* p, const PoseIn& in, double* err, const PoseOut& o) {
+    pose_record(P, p->fx, p->fy, p->cx, p->cy, p->bf, p->Tcw);
+    P.n = p->n; P.Xw = in.Xw; P.obs = in.obs; P.info = in.info; P.err = err; P.flags = in.flags; P.outlier = o.outlier;
+    P.Tout = o.T; P.result = o.res; P.trace = o.trace;
+    P.nPlanes = p->n_planes; P.planes = in.planes; P.planeOutlier = o.planeOutlier;
+}
+
 }  // namespace
 
 extern "C" {
@@ -990,86 +1070,37 @@ eao_status eao_pose_optimization(const eao_pose_problem* p, eao_pose_result* r) 
         r->n_inliers = 0;
         return EAO_OK;
     }
-    // inputs are staged in the pinned mirror of the arena (float32 -> double exactly as Converter / Eigen would promote
-    // them) and sent with ONE copy; the results come back through pinned memory the kernel writes directly
+    // inputs are staged in the pinned mirror of the arena and sent with ONE copy; the results come back through pinned memory the kernel writes directly
     const size_t need = (size_t)n * (3 + 3 + 1 + 3) * 8 + (size_t)n * 2 + 40 * 256;
     if ((st = c.bytes.reserve(need))) return st;
     Arena a{c.bytes.p, c.bytes.n};
     const size_t off0 = a.off;
-    double* dXw = a.take<double>((size_t)n * 3);
-    double* dobs = a.take<double>((size_t)n * 3);
-    double* dinfo = a.take<double>(n);
-    unsigned char* dflags = a.take<unsigned char>(n);
-    double* dplanes = a.take<double>((size_t)kPoseMaxPlanes * 10);
-    const size_t off1 = (a.off + 255) & ~(size_t)255;
+    const PoseIn in = PoseIn::take(a, n);
+    const size_t off1 = eao::align256(a.off);
     double* derr = a.take<double>((size_t)n * 3);
     long long* ddbg = a.take<long long>(64);
-    if (c.pinCap < off1) {
-        if (c.pin) (void)hipHostFree(c.pin);
-        c.pin = nullptr; c.pinCap = 0;
-        EAO_HIP(hipHostMalloc((void**)&c.pin, off1 + (off1 >> 2), hipHostMallocDefault));
-        c.pinCap = off1 + (off1 >> 2);
-    }
-    const size_t outBytes = sizeof(SE3) + 16 + 192 * 8 + 16 + (size_t)n + 64 + kPoseMaxPlanes;
-    if (c.pinOutCap < outBytes) {
-        if (c.pinOut) (void)hipHostFree(c.pinOut);
-        c.pinOut = nullptr; c.pinOutCap = 0;
-        EAO_HIP(hipHostMalloc((void**)&c.pinOut, outBytes + (outBytes >> 2), hipHostMallocMapped));
-        c.pinOutCap = outBytes + (outBytes >> 2);
-    }
-    SE3* oT = (SE3*)c.pinOut;
-    double* otrace = (double*)(c.pinOut + ((sizeof(SE3) + 15) & ~(size_t)15));
-    int* ores = (int*)(otrace + 192);
-    unsigned char* opl = (unsigned char*)(ores + 4);          // kPoseMaxPlanes plane flags, then the point flags
-    unsigned char* ooutl = opl + kPoseMaxPlanes;
-    std::memset(opl, 0, kPoseMaxPlanes);
-    std::memset(ooutl, 0, n);     // the memory variant of the kernel reads the flags before it first writes them
-    ores[0] = ores[1] = ores[2] = ores[3] = 0;
-    auto hostp = [&](const void* dev) { return c.pin + ((const unsigned char*)dev - a.base); };
-    {
-        double* hX = (double*)hostp(dXw); double* hO = (double*)hostp(dobs); double* hI = (double*)hostp(dinfo);
-        unsigned char* hF = (unsigned char*)hostp(dflags);
-        for (int i = 0; i < n; i++) {
-            for (int k = 0; k < 3; k++) { hX[3 * i + k] = p->Xw[3 * i + k]; hO[3 * i + k] = p->obs[3 * i + k]; }
-            hI[i] = p->inv_sigma2[i];
-            hF[i] = (unsigned char)((!(p->obs[3 * i + 2] < 0) ? 1 : 0) | 4);
-        }
-        // planes: normalised world / measured coefficients and the two information values (src/Optimizer.cc:464-465, 503-516)
-        double* hP = (double*)hostp(dplanes);
-        const double angleInfo = refc::PLANE_ANGLE_INFO / (1.0 * 1.0), disInfo = refc::PLANE_DIST_INFO_ROOT * refc::PLANE_DIST_INFO_ROOT;
-        for (int i = 0; i < M; i++) {
-            plane_from_f32(p->plane_world + 4 * i, hP + 10 * i);
-            plane_from_f32(p->plane_obs + 4 * i, hP + 10 * i + 4);
-            const double f = p->plane_seen[i] ? 1.0 : 2.0;
-            hP[10 * i + 8] = f * angleInfo; hP[10 * i + 9] = f * disInfo;
-        }
-    }
+    if ((st = c.pin.reserve(off1)) || (st = c.pinOut.reserve(PoseOut::bytes(n)))) return st;
+    const PoseOut o(c.pinOut.p);
+    o.clear(n);
+    const PoseIn hin = in.mirror(a.base, c.pin.p);
+    pose_pack(p, hin);
     EAO_HIP(hipEventRecord(c.ev0, c.stream));
     // The register variants read every input exactly once: they take it straight from the pinned mirror over PCIe (~60 KB) --
     // an upload in front of the kernel is a copy-engine job plus a hand-over to the compute queue (~10 us).  The memory
     // variant walks the edges in every LM pass and gets its copy.
     const bool zeroCopy = n <= 4 * kPoseThreads && M == 0;      // (plane coefficients are re-read in every pass: uploaded)
-    if (!zeroCopy) EAO_HIP(hipMemcpyAsync(a.base + off0, c.pin + off0, off1 - off0, hipMemcpyHostToDevice, c.stream));
+    if (!zeroCopy) EAO_HIP(hipMemcpyAsync(a.base + off0, c.pin.p + off0, off1 - off0, hipMemcpyHostToDevice, c.stream));
     PoseDev P;
-    P.nDev = nullptr; P.scatterIdx = nullptr; P.scatterOut = nullptr; P.done = nullptr; P.doneSeq = 0;
-    P.n = n; P.Xw = dXw; P.obs = dobs; P.info = dinfo; P.err = derr; P.flags = dflags; P.outlier = ooutl;
-    if (zeroCopy) { P.Xw = (const double*)hostp(dXw); P.obs = (const double*)hostp(dobs); P.info = (const double*)hostp(dinfo); P.flags = (unsigned char*)hostp(dflags); }
-    P.T0 = se3_from_Tcw_f32(p->Tcw);
-    P.cam.fx = p->fx; P.cam.fy = p->fy; P.cam.cx = p->cx; P.cam.cy = p->cy; P.cam.bf = p->bf; P.cam.bf_f = p->bf;
-    P.cam.deltaMono = (float)std::sqrt(refc::POSE_HUBER2_MONO); P.cam.deltaStereo = (float)std::sqrt(refc::POSE_HUBER2_STEREO);
-    P.Tout = oT; P.result = ores; P.trace = otrace;
-    P.nPlanes = M; P.planes = dplanes; P.planeOutlier = opl; P.deltaPlane = (float)std::sqrt(refc::PLANE_CHI2);
+    pose_bind(P, p, in, derr, o);
+    if (zeroCopy) { P.Xw = hin.Xw; P.obs = hin.obs; P.info = hin.info; P.flags = hin.flags; }
     P.dbg = getenv("EAO_DEBUG_STAMPS") ? ddbg : nullptr;
     if (n > 4 * kPoseThreads) hipLaunchKernelGGL(k_pose_optimization_mem, dim3(1), dim3(kPoseThreads), 0, c.stream, P);
     else launch_pose_registers(P, n, M > 0, c.stream);
     EAO_HIP(hipEventRecord(c.ev1, c.stream));
     EAO_HIP(eao::wait_latency(c.stream));
     EAO_HIP(hipGetLastError());
-    const SE3 Tout = *oT;
-    const int* res = ores;
-    const double* trace = otrace;
-    std::memcpy(r->outlier, ooutl, n);
-    if (M) std::memcpy(r->plane_outlier, opl, M);
+    o.read(p, r);
+    const int* res = o.res;
     if (P.dbg) {
         long long st[64];
         EAO_HIP(hipMemcpy(st, P.dbg, sizeof(st), hipMemcpyDeviceToHost));
@@ -1078,11 +1109,8 @@ eao_status eao_pose_optimization(const eao_pose_problem* p, eao_pose_result* r) 
         for (int w = 0; w < (int)st[7] && w < 16; w++) fprintf(stderr, "  w%d %lld / %lld / %lld", w, st[8 + w], st[24 + w], st[40 + w]);
         fprintf(stderr, "\n");
     }
-    se3_to_Tcw_f32(Tout, r->Tcw);
-    r->n_inliers = n + M - res[0];
-    r->lm_iterations = res[1];
     for (int k = 0; k < res[2] && k < 64; k++) {
-        g_trace.lambda.push_back(trace[k]); g_trace.chi2.push_back(trace[64 + k]); g_trace.trials.push_back((int)trace[128 + k]);
+        g_trace.lambda.push_back(o.trace[k]); g_trace.chi2.push_back(o.trace[64 + k]); g_trace.trials.push_back((int)o.trace[128 + k]);
     }
     g_trace.linearizations = res[1];
     EAO_HIP(hipEventElapsedTime(&g_trace.deviceMs, c.ev0, c.ev1));
@@ -1094,11 +1122,6 @@ eao_status eao_pose_optimization(const eao_pose_problem* p, eao_pose_result* r) 
 // ONE launch per register variant, ONE synchronisation; each frame's result is what eao_pose_optimization returns for it
 // (same kernel body, same reduction order).  Frames the one-workgroup register kernels do not take (more than
 // 4 * kPoseThreads correspondences) go through eao_pose_optimization one by one.
-// float -> double over one contiguous array (restrict-qualified and on its own, so that the host compiler vectorises it: the
-// interleaved per-correspondence loop it replaces ran scalar and was half of a 256-frame call's host time)
-static inline void widen(double* __restrict dst, const float* __restrict src, size_t n) {
-    for (size_t i = 0; i < n; i++) dst[i] = (double)src[i];
-}
 eao_status eao_pose_optimization_batch(const eao_pose_problem* ps, int32_t nb, eao_pose_result* rs) {
     EAO_REQUIRE(nb >= 0 && (nb == 0 || (ps && rs)), "bad batch");
     if (nb == 0) return EAO_OK;
@@ -1125,125 +1148,54 @@ eao_status eao_pose_optimization_batch(const eao_pose_problem* ps, int32_t nb, e
     for (int g = 0; g < 8; g++) nk += (int)grp[g].size();
     if (nk) {
         // arena: [records | per frame: Xw, obs, info, flags, planes] uploaded, then the per-frame residual scratch
-        struct Slot { int b; double *Xw, *obs, *info, *planes, *err; unsigned char* flags; size_t out; };
+        struct Slot { int b; PoseIn in; double* err; size_t out; };
         std::vector<Slot> slots;
         size_t need = (size_t)nk * sizeof(PoseDev) + 512, outBytes = 0;
-        const size_t outFixed = ((sizeof(SE3) + 15) & ~(size_t)15) + 192 * 8 + 16 + kPoseMaxPlanes;
         for (int g = 0; g < 8; g++)
             for (int b : grp[g]) {
                 need += (size_t)ps[b].n * (3 + 3 + 1 + 3) * 8 + (size_t)ps[b].n + (size_t)kPoseMaxPlanes * 80 + 6 * 256;
-                outBytes += (outFixed + (size_t)ps[b].n + 63) & ~(size_t)63;
+                outBytes += PoseOut::bytes(ps[b].n);
             }
         if ((st = c.bytes.reserve(need))) return st;
         Arena a{c.bytes.p, c.bytes.n};
         const size_t off0 = a.off;
         PoseDev* dW = a.take<PoseDev>(nk);
         for (int g = 0; g < 8; g++)
-            for (int b : grp[g]) {
-                Slot s{};
-                const int n = ps[b].n;
-                s.b = b;
-                s.Xw = a.take<double>((size_t)n * 3); s.obs = a.take<double>((size_t)n * 3); s.info = a.take<double>(n);
-                s.flags = a.take<unsigned char>(n); s.planes = a.take<double>((size_t)kPoseMaxPlanes * 10);
-                slots.push_back(s);
-            }
-        const size_t off1 = (a.off + 255) & ~(size_t)255;
+            for (int b : grp[g]) slots.push_back(Slot{b, PoseIn::take(a, ps[b].n), nullptr, 0});
+        const size_t off1 = eao::align256(a.off);
         for (Slot& s : slots) s.err = a.take<double>((size_t)ps[s.b].n * 3);
-        if (c.pinCap < off1) {
-            if (c.pin) (void)hipHostFree(c.pin);
-            c.pin = nullptr; c.pinCap = 0;
-            EAO_HIP(hipHostMalloc((void**)&c.pin, off1 + (off1 >> 2), hipHostMallocDefault));
-            c.pinCap = off1 + (off1 >> 2);
-        }
-        if (c.pinOutCap < outBytes) {
-            if (c.pinOut) (void)hipHostFree(c.pinOut);
-            c.pinOut = nullptr; c.pinOutCap = 0;
-            EAO_HIP(hipHostMalloc((void**)&c.pinOut, outBytes + (outBytes >> 2), hipHostMallocMapped));
-            c.pinOutCap = outBytes + (outBytes >> 2);
-        }
-        auto hostp = [&](const void* dev) { return c.pin + ((const unsigned char*)dev - a.base); };
-        PoseDev* hW = (PoseDev*)hostp(dW);
-        const bool zeroCopy = false;       // (the single call reads its inputs from the pinned mirror; for a batch it was measured and makes no difference)
+        if ((st = c.pin.reserve(off1)) || (st = c.pinOut.reserve(outBytes))) return st;
+        PoseDev* hW = (PoseDev*)(c.pin.p + ((unsigned char*)dW - a.base));
         size_t oo = 0;
-        const double angleInfo = refc::PLANE_ANGLE_INFO / (1.0 * 1.0), disInfo = refc::PLANE_DIST_INFO_ROOT * refc::PLANE_DIST_INFO_ROOT;     // src/Optimizer.cc:464-465
         for (size_t k = 0; k < slots.size(); k++) {
             Slot& s = slots[k];
             const eao_pose_problem* p = &ps[s.b];
-            const int n = p->n, M = p->n_planes;
             s.out = oo;
-            oo += (outFixed + (size_t)n + 63) & ~(size_t)63;
-            unsigned char* o = c.pinOut + s.out;
-            double* otrace = (double*)(o + ((sizeof(SE3) + 15) & ~(size_t)15));
-            int* ores = (int*)(otrace + 192);
-            unsigned char* opl = (unsigned char*)(ores + 4);
-            std::memset(opl, 0, kPoseMaxPlanes + (size_t)n);
-            ores[0] = ores[1] = ores[2] = ores[3] = 0;
-            double* hX = (double*)hostp(s.Xw); double* hO = (double*)hostp(s.obs); double* hI = (double*)hostp(s.info);
-            unsigned char* hF = (unsigned char*)hostp(s.flags);
-            widen(hX, p->Xw, (size_t)n * 3); widen(hO, p->obs, (size_t)n * 3); widen(hI, p->inv_sigma2, n);
-            for (int i = 0; i < n; i++) hF[i] = (unsigned char)((!(p->obs[3 * i + 2] < 0) ? 1 : 0) | 4);
-            double* hP = (double*)hostp(s.planes);
-            for (int i = 0; i < M; i++) {
-                plane_from_f32(p->plane_world + 4 * i, hP + 10 * i);
-                plane_from_f32(p->plane_obs + 4 * i, hP + 10 * i + 4);
-                const double f = p->plane_seen[i] ? 1.0 : 2.0;
-                hP[10 * i + 8] = f * angleInfo; hP[10 * i + 9] = f * disInfo;
-            }
-            PoseDev& P = hW[k];
-            std::memset((void*)&P, 0, sizeof(PoseDev));
-            P.nDev = nullptr;
-            P.n = n; P.Xw = s.Xw; P.obs = s.obs; P.info = s.info; P.err = s.err; P.flags = s.flags; P.outlier = opl + kPoseMaxPlanes;
-            if (zeroCopy) {     // (read once by the register kernels: straight from the pinned mirror, the transfer overlaps other frames' LM)
-                P.Xw = (const double*)hostp(s.Xw); P.obs = (const double*)hostp(s.obs); P.info = (const double*)hostp(s.info); P.flags = (unsigned char*)hostp(s.flags);
-            }
-            P.T0 = se3_from_Tcw_f32(p->Tcw);
-            P.cam.fx = p->fx; P.cam.fy = p->fy; P.cam.cx = p->cx; P.cam.cy = p->cy; P.cam.bf = p->bf; P.cam.bf_f = p->bf;
-            P.cam.deltaMono = (float)std::sqrt(refc::POSE_HUBER2_MONO); P.cam.deltaStereo = (float)std::sqrt(refc::POSE_HUBER2_STEREO);
-            P.Tout = (SE3*)o; P.result = ores; P.trace = otrace;
-            P.nPlanes = M; P.planes = s.planes; P.planeOutlier = opl; P.deltaPlane = (float)std::sqrt(refc::PLANE_CHI2);
-            P.dbg = nullptr;
+            oo += PoseOut::bytes(p->n);
+            const PoseOut o(c.pinOut.p + s.out);
+            o.clear(p->n);
+            pose_pack(p, s.in.mirror(a.base, c.pin.p));
+            pose_bind(hW[k], p, s.in, s.err, o);
         }
         g_trace.clear();
         EAO_HIP(hipEventRecord(c.ev0, c.stream));
-        const PoseDev* kW = dW;
-        if (zeroCopy) kW = hW;          // (the records too)
-        else EAO_HIP(hipMemcpyAsync(a.base + off0, c.pin + off0, off1 - off0, hipMemcpyHostToDevice, c.stream));
+        EAO_HIP(hipMemcpyAsync(a.base + off0, c.pin.p + off0, off1 - off0, hipMemcpyHostToDevice, c.stream));
         {   // one launch per (geometry class, planes) group; the records lie group after group
             size_t first = 0;
             for (int g = 0; g < 8; g++) {
                 if (grp[g].empty()) continue;
                 const dim3 gr((unsigned)grp[g].size()), bl(g % 4 == 3 ? kPoseThreads : kPoseWaves4);
-                const PoseDev* w = kW + first;
-                switch (g) {
-                    case 0: hipLaunchKernelGGL((k_pose_optimization_batch<1, false, kPoseWaves4>), gr, bl, 0, c.stream, w); break;
-                    case 1: hipLaunchKernelGGL((k_pose_optimization_batch<2, false, kPoseWaves4>), gr, bl, 0, c.stream, w); break;
-                    case 2: hipLaunchKernelGGL((k_pose_optimization_batch<4, false, kPoseWaves4>), gr, bl, 0, c.stream, w); break;
-                    case 3: hipLaunchKernelGGL((k_pose_optimization_batch<4, false, kPoseThreads>), gr, bl, 0, c.stream, w); break;
-                    case 4: hipLaunchKernelGGL((k_pose_optimization_batch<1, true, kPoseWaves4>), gr, bl, 0, c.stream, w); break;
-                    case 5: hipLaunchKernelGGL((k_pose_optimization_batch<2, true, kPoseWaves4>), gr, bl, 0, c.stream, w); break;
-                    case 6: hipLaunchKernelGGL((k_pose_optimization_batch<4, true, kPoseWaves4>), gr, bl, 0, c.stream, w); break;
-                    default: hipLaunchKernelGGL((k_pose_optimization_batch<4, true, kPoseThreads>), gr, bl, 0, c.stream, w); break;
-                }
+                const PoseDev* w = dW + first;
+                pose_variant(g % 4, g >= 4, [&](auto ept, auto pl, auto maxt) {
+                    hipLaunchKernelGGL((k_pose_optimization_batch<decltype(ept)::value, decltype(pl)::value, decltype(maxt)::value>), gr, bl, 0, c.stream, w);
+                });
                 first += grp[g].size();
             }
         }
         EAO_HIP(hipEventRecord(c.ev1, c.stream));
         EAO_HIP(eao::wait_latency(c.stream));
         EAO_HIP(hipGetLastError());
-        for (const Slot& s : slots) {
-            const eao_pose_problem* p = &ps[s.b];
-            eao_pose_result* r = &rs[s.b];
-            const unsigned char* o = c.pinOut + s.out;
-            const SE3 Tout = *(const SE3*)o;
-            const double* otrace = (const double*)(o + ((sizeof(SE3) + 15) & ~(size_t)15));
-            const int* ores = (const int*)(otrace + 192);
-            const unsigned char* opl = (const unsigned char*)(ores + 4);
-            std::memcpy(r->outlier, opl + kPoseMaxPlanes, p->n);
-            if (p->n_planes) std::memcpy(r->plane_outlier, opl, p->n_planes);
-            se3_to_Tcw_f32(Tout, r->Tcw);
-            r->n_inliers = p->n + p->n_planes - ores[0];
-            r->lm_iterations = ores[1];
-        }
+        for (const Slot& s : slots) PoseOut(c.pinOut.p + s.out).read(&ps[s.b], &rs[s.b]);
         EAO_HIP(hipEventElapsedTime(&g_trace.deviceMs, c.ev0, c.ev1));
     }
     for (int b : single)
@@ -1256,11 +1208,11 @@ eao_status eao_pose_optimization_batch(const eao_pose_problem* ps, int32_t nb, e
 // ---------------------------------------------------------------------------------------------------------------------
 // Hooks for the device-resident tracking chain (csrc/track.hip): PoseOptimization over edges that a previous kernel left
 // on the device, their count included.
-#include "chain_internal.h"
 namespace eao {
 namespace lm {
 size_t pose_se3_bytes() { return sizeof(SE3); }
 void pose_se3_to_Tcw(const void* se3, float* T) { se3_to_Tcw_f32(*(const SE3*)se3, T); }
+// normalised world / measured coefficients and the two information values (src/Optimizer.cc:464-465, 503-516)
 void pose_plane_records(int n, const float* plane_world, const float* plane_obs, const unsigned char* plane_seen, double* rec) {
     const double angleInfo = refc::PLANE_ANGLE_INFO / (1.0 * 1.0), disInfo = refc::PLANE_DIST_INFO_ROOT * refc::PLANE_DIST_INFO_ROOT;      // src/Optimizer.cc:464-465
     for (int i = 0; i < n; i++) {
@@ -1275,18 +1227,13 @@ eao_status enqueue_pose_device(const PoseChainArgs& a, hipStream_t s) {
     static_assert(kPoseChainMaxPlanes == kPoseMaxPlanes, "one limit");
     EAO_REQUIRE(a.nPlanes >= 0 && a.nPlanes <= kPoseMaxPlanes && (a.nPlanes == 0 || (a.planes && a.planeOutlier)), "at most %d plane edges", kPoseMaxPlanes);
     PoseDev P;
-    std::memset(&P, 0, sizeof(P));
+    pose_record(P, a.fx, a.fy, a.cx, a.cy, a.bf, a.Tcw0);
     P.n = a.cap; P.nDev = a.nEdges;
     P.Xw = a.Xw; P.obs = a.obs; P.info = a.info; P.err = a.err; P.flags = a.flags; P.outlier = a.outlier;
-    P.T0 = se3_from_Tcw_f32(a.Tcw0);
-    P.cam.fx = a.fx; P.cam.fy = a.fy; P.cam.cx = a.cx; P.cam.cy = a.cy; P.cam.bf = a.bf; P.cam.bf_f = a.bf;
-    P.cam.deltaMono = (float)std::sqrt(refc::POSE_HUBER2_MONO); P.cam.deltaStereo = (float)std::sqrt(refc::POSE_HUBER2_STEREO);
     P.Tout = (SE3*)a.outSE3; P.result = a.outResult; P.trace = a.outTrace;
     P.scatterIdx = a.scatterIdx; P.scatterOut = a.scatterOut;
-    P.done = nullptr; P.doneSeq = 0;
     P.pubSrc = (const uint4*)a.pubSrc; P.pubDst = (uint4*)a.pubDst; P.pubN16 = a.pubN16;
-    P.nPlanes = a.nPlanes; P.planes = a.planes; P.planeOutlier = a.planeOutlier; P.deltaPlane = (float)std::sqrt(refc::PLANE_CHI2);
-    P.dbg = nullptr;
+    P.nPlanes = a.nPlanes; P.planes = a.planes; P.planeOutlier = a.planeOutlier;
     const bool pl = a.nPlanes > 0;
     // The edge count lives on the device: one launch per geometry class the capacity admits (four waves up to 1024 edges, eight
     // beyond); each returns at its first instruction unless the frame's count falls in its range (a ~3 us launch, against running every

@@ -347,24 +347,12 @@ __global__ __launch_bounds__(kSim3Threads) void k_optimize_sim3(const Sim3Rec* _
 }
 
 // ---------------------------------------------------------------------- host side
-struct Sim3Ctx {
-    hipStream_t stream = nullptr;
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;
+struct Sim3Ctx : ThreadStream {
     DevBuf<unsigned char> dev;
     std::vector<unsigned char> host;
     float lastMs = 0;
 };
 thread_local Sim3Ctx g_sim3;
-
-eao_status sim3_ctx_init(Sim3Ctx& c) {
-    if (c.stream) return EAO_OK;
-    eao_status st = require_device();
-    if (st) return st;
-    EAO_HIP(create_stream(&c.stream, StreamClass::Latency));
-    EAO_HIP(hipEventCreate(&c.ev0));
-    EAO_HIP(hipEventCreate(&c.ev1));
-    return EAO_OK;
-}
 
 // R * X accumulated in double, rounded once to float; + t in float (cv::Mat float gemm then add); then promoted
 void camera_point(const float* T, const float* X, double out[3]) {
@@ -384,15 +372,14 @@ eao_status check_problem(const eao_sim3_problem* p, const eao_sim3_result* r) {
     return EAO_OK;
 }
 
-inline size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
-
 eao_status run_sim3(const eao_sim3_problem* ps, int nb, eao_sim3_result* rs) {
     for (int b = 0; b < nb; b++) {
         eao_status st = check_problem(&ps[b], &rs[b]);
         if (st) return st;
     }
     Sim3Ctx& c = g_sim3;
-    eao_status st = sim3_ctx_init(c);
+    eao_status st = c.ready(StreamClass::Latency);
+    if (!st) st = c.timing();
     if (st) return st;
     // layout: [records][per problem: 12 n doubles] | [outputs][per problem: removed n] | [per problem: lastbad n]
     size_t off = align256(sizeof(Sim3Rec) * nb);

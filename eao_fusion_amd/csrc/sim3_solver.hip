@@ -326,22 +326,11 @@ __global__ __launch_bounds__(kWave) void k_sim3_solver_scan(const SolverRec* __r
 }
 
 // ---------------------------------------------------------------------- host side
-struct SolverCtx {
-    hipStream_t stream = nullptr;
+struct SolverCtx : ThreadStream {
     DevBuf<unsigned char> dev;
     std::vector<unsigned char> host;
 };
 thread_local SolverCtx g_solver;
-
-eao_status solver_ctx_init(SolverCtx& c) {
-    if (c.stream) return EAO_OK;
-    eao_status st = require_device();
-    if (st) return st;
-    EAO_HIP(create_stream(&c.stream, StreamClass::Latency));     // LoopClosing's thread waits for the call, as for eao_optimize_sim3
-    return EAO_OK;
-}
-
-inline size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
 
 struct Call {
     const eao_sim3_solver_problem* p;
@@ -382,7 +371,7 @@ eao_status run_solver(std::vector<Call>& calls) {
         if (st) return st;
     }
     SolverCtx& ctx = g_solver;
-    eao_status st = solver_ctx_init(ctx);
+    eao_status st = ctx.ready(StreamClass::Latency);     // LoopClosing's thread waits for the call, as for eao_optimize_sim3
     if (st) return st;
     // layout: [records][per problem: 12 n floats, 3 n_eval ints] | [outputs][per problem: inlier n] | [per problem: HypOut n_eval, masks]
     size_t off = align256(sizeof(SolverRec) * nb);

@@ -706,7 +706,7 @@ __global__ __launch_bounds__(kAssignThreads) void k_track_assign_edges(int nMp, 
 
 // everything the host needs, in one block: [SE3 | result ints | counts | kpMp | kpOutlier | uRight | depth]
 
-inline size_t al256(size_t v) { return (v + 255) & ~(size_t)255; }
+using eao::align256;
 
 }  // namespace
 
@@ -730,7 +730,7 @@ eao_status eao_tracker_create(const eao_tracker_cfg* cfg, eao_tracker** out) {
     h->capQ = (int)Q;
     h->listCap = std::min<size_t>(C * Q, (size_t)1 << 24);
     size_t off = 0;
-    auto take = [&](size_t bytes) { const size_t o = off; off = al256(off + bytes); return o; };
+    auto take = [&](size_t bytes) { const size_t o = off; off = align256(off + bytes); return o; };
     const size_t oKx = take(4 * C), oKy = take(4 * C), oAng = take(4 * C), oUr = take(4 * C), oDz = take(4 * C), oOct = take(4 * C), oOrd = take(4 * C),
                  oCx = take(2 * C), oCy = take(2 * C), oCnt = take(64), oPrior = take(4 * C), oPriorX = take(12 * C), oKpMp = take(4 * C), oOcc = take(C), oKpOut = take(C),
                  oMX = take(12 * M), oMN = take(12 * M), oMMin = take(4 * M), oMMax = take(4 * M), oMNum = take(4 * M), oMD = take(32 * M), oMA = take(M),
@@ -739,8 +739,8 @@ eao_status eao_tracker_create(const eao_tracker_cfg* cfg, eao_tracker** out) {
                  oLQ = take(sizeof(Query) * C), oLX = take(12 * C), oLD = take(32 * C), oLA = take(4 * C), oLS = take(Q),
                  oEX = take(24 * C), oEO = take(24 * C), oEI = take(8 * C), oEE = take(24 * C), oEF = take(C), oEOu = take(C), oEK = take(4 * C),
                  oSc = take(4 * 64), oIs = take(4 * 64), oCol = take(4 * ((size_t)cfg->grid_cols + 1));
-    const size_t se3 = al256(eao::lm::pose_se3_bytes());
-    h->resBytes = se3 + al256(16) + al256(192 * 8) + al256(32) + al256(eao::lm::kPoseChainMaxPlanes) + al256(4 * C) + al256(C) + al256(4 * C) + al256(4 * C) + al256(Q) + 256;      // (+ the done word)
+    const size_t se3 = align256(eao::lm::pose_se3_bytes());
+    h->resBytes = se3 + align256(16) + align256(192 * 8) + align256(32) + align256(eao::lm::kPoseChainMaxPlanes) + align256(4 * C) + align256(C) + align256(4 * C) + align256(4 * C) + align256(Q) + 256;      // (+ the done word)
     const size_t oRes = take(h->resBytes);
     if ((st = h->dev.reserve(off))) { delete h; return st; }
     unsigned char* b = h->dev.p;
@@ -767,8 +767,8 @@ eao_status eao_tracker_create(const eao_tracker_cfg* cfg, eao_tracker** out) {
     if (hipHostGetDevicePointer((void**)&h->res, h->resPin, 0) != hipSuccess) { delete h; eao::set_error("hipHostGetDevicePointer failed"); return EAO_ERR_NO_DEVICE; }
     if (eao::create_stream(&h->stream, eao::StreamClass::Latency) != hipSuccess || hipEventCreateWithFlags(&h->evIn, hipEventDisableTiming) != hipSuccess ||
         hipEventCreateWithFlags(&h->evOut, hipEventDisableTiming) != hipSuccess) { delete h; eao::set_error("stream / event creation failed"); return EAO_ERR_NO_DEVICE; }
-    h->pinCap = std::max(h->resBytes, al256(12 * M) * 2 + al256(4 * M) * 3 + al256(32 * M) + al256(M) + al256(4 * C) + al256(12 * C) +
-                                      al256(sizeof(Query) * C) + al256(32 * C) + al256(4 * C)) + 4096;
+    h->pinCap = std::max(h->resBytes, align256(12 * M) * 2 + align256(4 * M) * 3 + align256(32 * M) + align256(M) + align256(4 * C) + align256(12 * C) +
+                                      align256(sizeof(Query) * C) + align256(32 * C) + align256(4 * C)) + 4096;
     if (hipHostMalloc((void**)&h->pin, h->pinCap, hipHostMallocDefault) != hipSuccess) { delete h; eao::set_error("pinned allocation failed"); return EAO_ERR_NO_DEVICE; }
     // the assignment workgroup's LDS: claims / occupancy / octaves by keypoint, then the staged candidate lists (beyond the default 64 KB)
     if (getenv("EAO_DEBUG_STAMPS")) { EAO_HIP(hipMalloc((void**)&h->dbg, 256)); EAO_HIP(hipMemset(h->dbg, 0, 256)); }
@@ -802,7 +802,7 @@ eao_status eao_tracker_set_local_map(eao_tracker* h, const eao_map_points* pts) 
     auto put = [&](void* dst, const void* src, size_t bytes) -> eao_status {
         std::memcpy(h->pin + off, src, bytes);
         EAO_HIP(hipMemcpyAsync(dst, h->pin + off, bytes, hipMemcpyHostToDevice, h->stream));
-        off = al256(off + bytes);
+        off = align256(off + bytes);
         return EAO_OK;
     };
     eao_status st;
@@ -881,7 +881,7 @@ eao_status track_chain(eao_tracker* h, const eao_keypoint* d_kps, const uint8_t*
         EAO_REQUIRE(!outside || prior_kp_Xw, "prior_kp_map_point holds -2 but prior_kp_Xw is NULL");
         EAO_HIP(hipMemcpyAsync(h->prior, h->pin, 4 * (size_t)C, hipMemcpyHostToDevice, s));
         if (outside) {
-            unsigned char* px = h->pin + al256(4 * (size_t)C);
+            unsigned char* px = h->pin + align256(4 * (size_t)C);
             std::memcpy(px, prior_kp_Xw, 12 * (size_t)C);
             EAO_HIP(hipMemcpyAsync(h->priorXw, px, 12 * (size_t)C, hipMemcpyHostToDevice, s));
         }
@@ -899,7 +899,7 @@ eao_status track_chain(eao_tracker* h, const eao_keypoint* d_kps, const uint8_t*
             eao_status qs = eao::match::build_frame_queries(QA, hq);
             if (qs) return qs;
             // the staging block mirrors the device block lQ | lXw | lDesc | lAng (offsets by CAPACITY, as eao_tracker_create laid them out): one copy
-            const size_t C2 = (size_t)C, oX = al256(sizeof(Query) * C2), oD = oX + al256(12 * C2), oA = oD + al256(32 * C2);
+            const size_t C2 = (size_t)C, oX = align256(sizeof(Query) * C2), oD = oX + align256(12 * C2), oA = oD + align256(32 * C2);
             std::memcpy(h->pin + oX, mm->Xw, 12 * (size_t)nMp); std::memcpy(h->pin + oD, mm->mp_desc, 32 * (size_t)nMp); std::memcpy(h->pin + oA, mm->angle, 4 * (size_t)nMp);
             EAO_HIP(hipMemcpyAsync(h->lQ, h->pin, oA + 4 * (size_t)nMp, hipMemcpyHostToDevice, (hipStream_t)stream));
         }
@@ -947,7 +947,7 @@ eao_status track_chain(eao_tracker* h, const eao_keypoint* d_kps, const uint8_t*
                 } else if (K.node_id[a] < F.node_id[b]) a++; else b++;
             }
             std::memcpy(h->pin + oV, bw->valid, (size_t)nMp);
-            const size_t C2 = (size_t)C, oX = al256(sizeof(Query) * C2), oD = oX + al256(12 * C2), oA = oD + al256(32 * C2);
+            const size_t C2 = (size_t)C, oX = align256(sizeof(Query) * C2), oD = oX + align256(12 * C2), oA = oD + align256(32 * C2);
             std::memcpy(h->pin + oX, bw->Xw, 12 * (size_t)nMp); std::memcpy(h->pin + oD, bw->kf_desc, 32 * (size_t)nMp); std::memcpy(h->pin + oA, bw->kf_angle, 4 * (size_t)nMp);
             EAO_HIP(hipMemcpyAsync(h->lQ, h->pin, oA + 4 * (size_t)nMp, hipMemcpyHostToDevice, s));
             unsigned char* dq = reinterpret_cast<unsigned char*>(h->lQ);
@@ -1000,21 +1000,21 @@ eao_status track_chain(eao_tracker* h, const eao_keypoint* d_kps, const uint8_t*
     const int edgeCap = std::min(C, 2048);
     // result block layout
     // (kernels write the DEVICE twin; the chain's last launch publishes it: see PoseDev::pubSrc, csrc/lm.hip)
-    const size_t se3 = al256(eao::lm::pose_se3_bytes());
+    const size_t se3 = align256(eao::lm::pose_se3_bytes());
     unsigned char* r = h->resDev;
     size_t ro = 0;
     void* rSE3 = r + ro; ro += se3;
-    int* rRes = (int*)(r + ro); ro += al256(16);
-    double* rTrace = (double*)(r + ro); ro += al256(192 * 8);
-    int* rCounts = (int*)(r + ro); ro += al256(32);
-    unsigned char* rPlOut = r + ro; ro += al256(eao::lm::kPoseChainMaxPlanes);      // mvbPlaneOutlier of the frame's plane edges (eao_tracker_set_options)
-    int* rKpMp = (int*)(r + ro); ro += al256(4 * (size_t)C);
-    unsigned char* rOutl = r + ro; ro += al256(C);
-    float* rUr = (float*)(r + ro); ro += al256(4 * (size_t)C);
-    float* rDz = (float*)(r + ro); ro += al256(4 * (size_t)C);
+    int* rRes = (int*)(r + ro); ro += align256(16);
+    double* rTrace = (double*)(r + ro); ro += align256(192 * 8);
+    int* rCounts = (int*)(r + ro); ro += align256(32);
+    unsigned char* rPlOut = r + ro; ro += align256(eao::lm::kPoseChainMaxPlanes);      // mvbPlaneOutlier of the frame's plane edges (eao_tracker_set_options)
+    int* rKpMp = (int*)(r + ro); ro += align256(4 * (size_t)C);
+    unsigned char* rOutl = r + ro; ro += align256(C);
+    float* rUr = (float*)(r + ro); ro += align256(4 * (size_t)C);
+    float* rDz = (float*)(r + ro); ro += align256(4 * (size_t)C);
     unsigned char* rInView = r + ro;
     const size_t pubBytes = (ro + (size_t)std::max(nMp, 0) + 15) & ~(size_t)15;      // everything up to the last in-view flag
-    ro += al256((size_t)h->capQ);
+    ro += align256((size_t)h->capQ);
     const size_t oDone = ro; ro += 256;
     int* rDone = (int*)(h->res + oDone);                                            // the done word itself only exists in host memory
     ResultBlock RB{rCounts, rKpMp, rOutl, rUr, rDz, rInView};

@@ -250,15 +250,12 @@ __global__ __launch_bounds__(256) void k_triangulate(TriArgs A) {
 }
 
 using PinBuf = eao::PinBuf<hipHostMallocDefault>;   // staging of the asynchronous copies
-struct Ctx {   // per host thread, grow-only
-    hipStream_t stream = nullptr;
+struct Ctx : eao::ThreadStream {   // per host thread, grow-only
     PinBuf in, out;
     eao::DevBuf<unsigned char> din, dout;
-    ~Ctx() { if (stream) (void)hipStreamDestroy(stream); }
 };
 thread_local Ctx g_tctx;
-
-inline size_t al256(size_t v) { return (v + 255) & ~(size_t)255; }
+using eao::align256;
 
 // nullptr: the view serves; else what is wrong with it
 const char* view_problem(const eao_frame_view* V, const float* depth) {
@@ -306,26 +303,25 @@ eao_status eao_triangulate_matches_batch(const eao_frame_view* K1, const eao_tri
         for (int i = 0; i < n1; i++) EAO_REQUIRE(row[i] >= -1 && row[i] < K2s[k]->n, "neighbour %d: match12[%d] = %d is no keypoint of its %d", k, i, row[i], K2s[k]->n);
     }
     if (n1 == 0) return EAO_OK;
-    eao_status st = eao::require_device();
-    if (st) return st;
     Ctx& c = g_tctx;
-    if (!c.stream) EAO_HIP(eao::create_stream(&c.stream, eao::StreamClass::Background));      // LocalMapping waits for this call, Tracking does not
+    eao_status st = c.ready(eao::StreamClass::Background);      // LocalMapping waits for this call, Tracking does not
+    if (st) return st;
     // one staging block: per keyframe [kx | ky | ur | depth | rawx | rawy | oct | sf | s2], then the table
     struct Off { size_t kx, ky, ur, dp, rx, ry, oc, sf, s2; };
     size_t off = 0;
     auto lay = [&](const eao_frame_view* V) {
         Off o;
         const size_t n = (size_t)std::max(V->n, 1), nl = (size_t)V->nlevels;
-        o.kx = off; off = al256(off + 4 * n); o.ky = off; off = al256(off + 4 * n); o.ur = off; off = al256(off + 4 * n); o.dp = off; off = al256(off + 4 * n);
-        o.rx = off; off = al256(off + 4 * n); o.ry = off; off = al256(off + 4 * n); o.oc = off; off = al256(off + 4 * n);
-        o.sf = off; off = al256(off + 4 * nl); o.s2 = off; off = al256(off + 4 * nl);
+        o.kx = off; off = align256(off + 4 * n); o.ky = off; off = align256(off + 4 * n); o.ur = off; off = align256(off + 4 * n); o.dp = off; off = align256(off + 4 * n);
+        o.rx = off; off = align256(off + 4 * n); o.ry = off; off = align256(off + 4 * n); o.oc = off; off = align256(off + 4 * n);
+        o.sf = off; off = align256(off + 4 * nl); o.s2 = off; off = align256(off + 4 * nl);
         return o;
     };
     std::vector<Off> offs(n_nb + 1);
     offs[0] = lay(K1);
     for (int k = 0; k < n_nb; k++) offs[k + 1] = lay(K2s[k]);
-    const size_t cells = (size_t)n_nb * n1, oTab = off, inBytes = al256(oTab + 4 * cells);
-    const size_t oX = al256(4 * cells), outBytes = oX + 12 * cells;
+    const size_t cells = (size_t)n_nb * n1, oTab = off, inBytes = align256(oTab + 4 * cells);
+    const size_t oX = align256(4 * cells), outBytes = oX + 12 * cells;
     if ((st = c.in.reserve(inBytes)) || (st = c.out.reserve(outBytes)) || (st = c.din.reserve(inBytes)) || (st = c.dout.reserve(outBytes))) return st;
     auto fill = [&](const Off& o, const eao_frame_view* V, const float* depth, const float* rx, const float* ry) {
         const size_t b = 4 * (size_t)V->n, bl = 4 * (size_t)V->nlevels;
