@@ -101,6 +101,24 @@ class Sim3SolverResult(C.Structure):   # eao_sim3_solver_result
                 ("hyp_inliers", C.c_void_p), ("hyp_T12", C.c_void_p), ("hyp_T21", C.c_void_p), ("hyp_inlier", C.c_void_p)]
 
 
+class InitializerProblem(C.Structure):   # eao_initializer_problem
+    _fields_ = [("n1", C.c_int32), ("n2", C.c_int32), ("keys1_xy", C.c_void_p), ("keys2_xy", C.c_void_p), ("n_matches", C.c_int32), ("matches12", C.c_void_p),
+                ("fx", C.c_float), ("fy", C.c_float), ("cx", C.c_float), ("cy", C.c_float), ("sigma", C.c_float), ("min_parallax", C.c_float),
+                ("min_triangulated", C.c_int32)]
+
+
+class InitializerResult(C.Structure):   # eao_initializer_result
+    _fields_ = [("returned", C.c_int32), ("branch", C.c_int32), ("no_model", C.c_int32), ("degenerate", C.c_int32),
+                ("SH", C.c_float), ("SF", C.c_float), ("RH", C.c_float), ("best_h", C.c_int32), ("best_f", C.c_int32),
+                ("H21", C.c_float * 9), ("F21", C.c_float * 9), ("R21", C.c_float * 9), ("t21", C.c_float * 3),
+                ("parallax", C.c_float), ("cos_parallax", C.c_float), ("n_good", C.c_int32), ("motion", C.c_int32), ("n_motions", C.c_int32),
+                ("n_inliers", C.c_int32), ("p3d", C.c_void_p), ("triangulated", C.c_void_p),
+                ("hyp_H21", C.c_void_p), ("hyp_H12", C.c_void_p), ("hyp_F21", C.c_void_p), ("hyp_SH", C.c_void_p), ("hyp_SF", C.c_void_p),
+                ("hyp_inlier_H", C.c_void_p), ("hyp_inlier_F", C.c_void_p), ("inlier", C.c_void_p),
+                ("mot_R", C.c_void_p), ("mot_t", C.c_void_p), ("mot_n_good", C.c_void_p), ("mot_cos", C.c_void_p), ("mot_good", C.c_void_p),
+                ("mot_p3d", C.c_void_p)]
+
+
 class EssentialGraphProblem(C.Structure):   # eao_essential_graph_problem
     _fields_ = [("n", C.c_int32), ("fixed", C.c_int32), ("fix_scale", C.c_int32), ("Scw", C.c_void_p), ("has_nc", C.c_void_p), ("Snc", C.c_void_p),
                 ("n_edges", C.c_int32), ("edges", C.c_void_p), ("n_points", C.c_int32), ("Xw", C.c_void_p), ("ref", C.c_void_p)]
@@ -175,6 +193,8 @@ SYMBOLS = {
     "eao_optimize_sim3_batch": (_I, [C.POINTER(Sim3Problem), _I, C.POINTER(Sim3Result)]),
     "eao_sim3_solver_iterate": (_I, [C.POINTER(Sim3SolverProblem), _I, _I, C.POINTER(Sim3SolverState), _P, _I, C.POINTER(Sim3SolverResult)]),
     "eao_sim3_solver_iterate_batch": (_I, [_I, C.POINTER(Sim3SolverProblem), _P, _P, C.POINTER(Sim3SolverState), _P, _P, C.POINTER(Sim3SolverResult)]),
+    "eao_initializer_initialize": (_I, [C.POINTER(InitializerProblem), _P, _I, C.POINTER(InitializerResult)]),
+    "eao_initializer_last_kernel_ms": (_I, [_P]),
     "eao_optimize_essential_graph": (_I, [C.POINTER(EssentialGraphProblem), C.POINTER(EssentialGraphResult)]),
     "eao_essential_graph_plan": (_I, [C.POINTER(EssentialGraphProblem), _P, _P, _P, _I]),
     "eao_bundle_adjustment_plan": (_I, [_I, _I, _P, _P, _I, _P, _P, _P, _I, _P, _I, _P, _I, _P, _I, _P, _I, _P, _I]),

@@ -9,12 +9,13 @@
 //   * The neighbour is blockIdx.y: both camera records and the array addresses sit in the kernel arguments and come through scalar loads.
 //   * Arithmetic (tests/triangulation_reference.py is the same text in numpy): a cv::Mat product, Mat::dot and cv::norm accumulate in double in
 //     storage order and round once; A's rows are float expressions; the right singular vector of the smallest singular value is the eigenvector of the smallest
-//     eigenvalue of A^T A (double, from the float A) after kSweeps cyclic Jacobi sweeps -- a fixed count, no data-dependent loop -- rounded to float before the
+//     eigenvalue of A^T A (double, from the float A) after kSweeps4 cyclic Jacobi sweeps -- a fixed count, no data-dependent loop -- rounded to float before the
 //     w == 0 test; x3D / w multiplies by 1. / w in double and rounds once; the comparisons are written as upstream writes them (a NaN falls through the same gates).
 #include <algorithm>
 #include <cstring>
 #include <vector>
 
+#include "small_dense.h"
 #include "triangulate_internal.h"
 
 namespace {
@@ -28,7 +29,7 @@ constexpr double kChi2Stereo = 7.8;             // :389, :415  > 7.8*sigmaSquare
 // ----
 
 constexpr int kSeg = 256;        // match-table slots per wavefront
-constexpr int kSweeps = 8;       // cyclic Jacobi sweeps over the 4 x 4 A^T A (quadratic convergence: a 4 x 4 symmetric matrix is diagonal to double precision after 5 or 6)
+using eao::dense::smallest_eigenvector;      // small_dense.h: kSweeps4 cyclic Jacobi sweeps over the 4 x 4 A^T A
 
 struct TriArgs {
     eao::tri::Side K1;
@@ -45,47 +46,6 @@ __device__ __forceinline__ double ddot3(float a0, float a1, float a2, float b0, 
     s += (double)a1 * (double)b1;
     s += (double)a2 * (double)b2;
     return s;
-}
-
-// eigenvector of the smallest eigenvalue of the symmetric S = A^T A, by kSweeps cyclic Jacobi sweeps; every index below is a compile-time constant after unrolling
-__device__ __forceinline__ void smallest_eigenvector(double (&S)[4][4], double (&v)[4]) {
-    double V[4][4];
-#pragma unroll
-    for (int i = 0; i < 4; i++)
-#pragma unroll
-        for (int j = 0; j < 4; j++) V[i][j] = i == j ? 1.0 : 0.0;
-#pragma unroll 1
-    for (int sweep = 0; sweep < kSweeps; sweep++) {
-#pragma unroll
-        for (int p = 0; p < 3; p++)
-#pragma unroll
-            for (int q = p + 1; q < 4; q++) {
-                const double apq = S[p][q];
-                double c = 1.0, s = 0.0;
-                if (apq != 0.0) {
-                    const double theta = (S[q][q] - S[p][p]) / (2.0 * apq);
-                    const double t = (theta < 0.0 ? -1.0 : 1.0) / (fabs(theta) + sqrt(theta * theta + 1.0));
-                    c = 1.0 / sqrt(t * t + 1.0);
-                    s = t * c;
-                }
-#pragma unroll
-                for (int k = 0; k < 4; k++) { const double a = S[k][p], b = S[k][q]; S[k][p] = c * a - s * b; S[k][q] = s * a + c * b; }
-#pragma unroll
-                for (int k = 0; k < 4; k++) { const double a = S[p][k], b = S[q][k]; S[p][k] = c * a - s * b; S[q][k] = s * a + c * b; }
-#pragma unroll
-                for (int k = 0; k < 4; k++) { const double a = V[k][p], b = V[k][q]; V[k][p] = c * a - s * b; V[k][q] = s * a + c * b; }
-            }
-    }
-    double best = S[0][0];
-#pragma unroll
-    for (int k = 0; k < 4; k++) v[k] = V[k][0];
-#pragma unroll
-    for (int j = 1; j < 4; j++) {
-        const bool less = S[j][j] < best;      // the first of equal eigenvalues
-        best = less ? S[j][j] : best;
-#pragma unroll
-        for (int k = 0; k < 4; k++) v[k] = less ? V[k][j] : v[k];
-    }
 }
 
 // KeyFrame::UnprojectStereo (src/KeyFrame.cc:654-670); false: !(z > 0), upstream returns an empty Mat

@@ -898,6 +898,81 @@ eao_status eao_sim3_solver_iterate_batch(int32_t n_problems, const eao_sim3_solv
                                          eao_sim3_solver_state* states, const int32_t* const* triples, const int32_t* n_hyp,
                                          eao_sim3_solver_result* results);
 
+/* ------------------------------------------------------------------------------------------------
+ * Initializer (reference include/Initializer.h, src/Initializer.cc): the homography / fundamental RANSAC and the two-view reconstruction of
+ * Tracking::MonocularInitialization (src/Tracking.cc:1374-1392).  One call is Initializer::Initialize after its draws (:99-121): FindHomography
+ * (:124-172) and FindFundamental (:175-223) over all sets at once, the choice of the model (:112-118), ReconstructH (:572-732) or ReconstructF
+ * (:470-570) with CheckRT (:798-907) per motion hypothesis.
+ * ------------------------------------------------------------------------------------------------ */
+enum { EAO_INIT_BRANCH_H = 0, EAO_INIT_BRANCH_F = 1 };
+
+typedef struct {
+    int32_t n1, n2;             /* keypoints of the reference / the current frame (mvKeys1, mvKeys2: Frame::mvKeysUn) */
+    const float* keys1_xy;      /* n1*2: pt.x, pt.y */
+    const float* keys2_xy;      /* n2*2 */
+    int32_t n_matches;          /* N = mvMatches12.size() (:49-63) */
+    const int32_t* matches12;   /* N*2: (first, second), strictly ascending in `first` as the loop of :54-63 leaves them */
+    float fx, fy, cx, cy;       /* mK */
+    float sigma;                /* mSigma (> 0) */
+    float min_parallax;         /* minParallax of ReconstructH / ReconstructF (upstream passes 1.0) */
+    int32_t min_triangulated;   /* minTriangulated (upstream passes 50) */
+} eao_initializer_problem;
+
+typedef struct {
+    int32_t returned;           /* what Initialize returns */
+    int32_t branch;             /* EAO_INIT_BRANCH_H when RH > 0.40, else EAO_INIT_BRANCH_F */
+    int32_t no_model;           /* the model of that branch has no hypothesis with a score above 0: returned = 0, nothing reconstructed */
+    int32_t degenerate;         /* ReconstructH left through d1/d2 < 1.00001 || d2/d3 < 1.00001 (:597) */
+    float SH, SF, RH;           /* the scores FindHomography / FindFundamental end with (0 without a winner) and SH/(SH+SF) */
+    int32_t best_h, best_f;     /* the set whose hypothesis won (the first of equal scores), or -1 */
+    float H21[9], F21[9];       /* the winners, row-major (zeros without one) */
+    float R21[9], t21[3];       /* written when returned (zeros otherwise) */
+    float parallax;             /* of the best motion hypothesis, degrees: acos(cos_parallax)*180/CV_PI formed on the host (0 without one) */
+    float cos_parallax;         /* the sorted cosines' entry min(50, nGood-1) the device selected (1 when nGood = 0) */
+    int32_t n_good;             /* nGood of the best motion hypothesis */
+    int32_t motion;             /* its index among the 4 (F: (R1,t1) (R2,t1) (R1,t2) (R2,t2)) or 8 (H: vR / vt order), or -1 */
+    int32_t n_motions;          /* 4, 8 or 0 (no_model, degenerate) */
+    int32_t n_inliers;          /* N of ReconstructH / ReconstructF: set flags of the winner of the branch taken */
+    float* p3d;                 /* n1*3 vP3D, caller-allocated; written only when returned (upstream leaves it alone otherwise) */
+    uint8_t* triangulated;      /* n1 vbTriangulated, likewise */
+    /* inspection, each written when non-NULL */
+    float* hyp_H21;             /* iterations*9: H21i */
+    float* hyp_H12;             /* iterations*9: H12i */
+    float* hyp_F21;             /* iterations*9: F21i */
+    float* hyp_SH;              /* iterations: currentScore of CheckHomography */
+    float* hyp_SF;              /* iterations: currentScore of CheckFundamental */
+    uint8_t* hyp_inlier_H;      /* iterations*N: vbCurrentInliers of CheckHomography (the only path that stores 2*iterations*N flags) */
+    uint8_t* hyp_inlier_F;      /* iterations*N */
+    uint8_t* inlier;            /* N: vbMatchesInliers of the branch taken */
+    float* mot_R;               /* 8*9: the motion hypotheses (rows past n_motions are zero) */
+    float* mot_t;               /* 8*3 */
+    int32_t* mot_n_good;        /* 8: CheckRT's return */
+    float* mot_cos;             /* 8: the selected cosine */
+    uint8_t* mot_good;          /* 8*n1: vbGood */
+    float* mot_p3d;             /* 8*n1*3: vP3D */
+} eao_initializer_result;
+
+/* sets: iterations*8 indices into 0 .. N-1, mvSets (:78-97) in draw order.  N >= 8, 1 <= iterations <= 65535, any n1, n2 >= 1 that fit the device.
+ * EAO_ERR_INVALID before anything is written: N < 8, a set index >= N, a match index out of range or `first` not ascending, a non-finite keypoint
+ * or intrinsic, sigma <= 0.
+ * Arithmetic: upstream's float expressions op for op; OpenCV's by the conventions of eao_sim3_solver_iterate (small products accumulate in double
+ * and round once, cv::norm / Mat::dot / cv::determinant in double, the 3 x 3 inverse by cofactors over a double determinant -- zero when singular);
+ * every singular vector (the 16 x 9 and 8 x 9 systems of ComputeH21 :226-266 / ComputeF21 :268-303, the 3 x 3 SVDs, Triangulate's 4 x 4 :734-747)
+ * is an eigenvector of A^T A in double from the float A, cyclic Jacobi with a fixed sweep count, rounded to float; its sign is not cv::SVD's, so the
+ * 4 / 8 motion hypotheses agree with upstream's as a set, not by index.
+ * Three deviations from upstream:
+ *  1. A score (CheckHomography :305-388, CheckFundamental :390-468) is the sum of its terms in double, rounded once to float.  Every term is a float
+ *     below 8 and a multiple of 2^-23, so that sum is exact: the same for every order, launch layout and run.  Upstream's float sum, term by term,
+ *     differs from it by at most N * 2^-24 relative.
+ *  2. no_model: upstream would throw from K.t()*F*K (or invK*H21*K) on the empty Mat.
+ *  3. Normalize (:749-795) runs on the host inside this call, op for op, with upstream's sequential float sums over ALL keypoints of each frame.
+ * Two calls on the same arguments return the same bytes. */
+eao_status eao_initializer_initialize(const eao_initializer_problem* problem, const int32_t* sets, int32_t iterations, eao_initializer_result* result);
+
+/* Diagnostic (tools/bench_initializer.py): with EAO_INIT_EVENTS=1 in the environment, the device time in ms of each of the five kernels of this thread's last
+ * eao_initializer_initialize (hypotheses, scores, selection, CheckRT, final rule), from HIP events on its stream.  EAO_ERR_INVALID when there is no measurement. */
+eao_status eao_initializer_last_kernel_ms(float* kernel_ms /* 5 */);
+
 /* The value of EAO_ABI_VERSION the library was built with. Bumped whenever an entry point's parameter list or a struct's layout changes (round 3
  * changed eao_tracker_track_local_map and eao_track_result in place); a caller compiled against another version must not call into the library.
  * Result structs are zero-initialised by the caller (`eao_track_result R = {0};`) before their array pointers are set: a pointer member the

@@ -2,7 +2,7 @@
 //
 // In a real EAO-Fusion checkout OpenCV is present and this header only forwards to it.  This build image has no
 // OpenCV, so for compile- and run-testing the adapters a minimal stand-in with the same member names is provided
-// (cv::Mat for CV_8UC1 / CV_32FC1, cv::KeyPoint, cv::Point2f, InputArray/OutputArray as Mat references).  It is NOT
+// (cv::Mat for CV_8UC1 / CV_32FC1, cv::KeyPoint, cv::Point2f, cv::Point3f, InputArray/OutputArray as Mat references).  It is NOT
 // used to build any reference source -- only this repository's own adapters and tests.
 #pragma once
 
@@ -34,6 +34,12 @@ struct Point2f {
     float x = 0, y = 0;
     Point2f() {}
     Point2f(float x_, float y_) : x(x_), y(y_) {}
+};
+
+struct Point3f {
+    float x = 0, y = 0, z = 0;
+    Point3f() {}
+    Point3f(float x_, float y_, float z_) : x(x_), y(y_), z(z_) {}
 };
 
 struct KeyPoint {  // same field order and size (28 bytes) as OpenCV's
