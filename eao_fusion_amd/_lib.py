@@ -119,6 +119,23 @@ class InitializerResult(C.Structure):   # eao_initializer_result
                 ("mot_p3d", C.c_void_p)]
 
 
+class PnpSolverProblem(C.Structure):   # eao_pnp_solver_problem
+    _fields_ = [("n", C.c_int32), ("p3d_w", C.c_void_p), ("p2d", C.c_void_p), ("sigma2", C.c_void_p),
+                ("fx", C.c_float), ("fy", C.c_float), ("cx", C.c_float), ("cy", C.c_float), ("th2", C.c_float)]
+
+
+class PnpSolverState(C.Structure):   # eao_pnp_solver_state
+    _fields_ = [("iterations", C.c_int32), ("best_inliers", C.c_int32), ("best_Tcw", C.c_float * 16), ("best_inlier", C.c_void_p)]
+
+
+class PnpSolverResult(C.Structure):   # eao_pnp_solver_result
+    _fields_ = [("returned", C.c_int32), ("refined", C.c_int32), ("n_inliers", C.c_int32), ("Tcw", C.c_float * 16), ("inlier", C.c_void_p),
+                ("no_more", C.c_int32), ("n_records", C.c_int32),
+                ("hyp_R", C.c_void_p), ("hyp_t", C.c_void_p), ("hyp_rep_err", C.c_void_p), ("hyp_choice", C.c_void_p), ("hyp_inliers", C.c_void_p),
+                ("hyp_inlier", C.c_void_p),
+                ("rec_hyp", C.c_void_p), ("rec_R", C.c_void_p), ("rec_t", C.c_void_p), ("rec_inliers", C.c_void_p), ("rec_inlier", C.c_void_p)]
+
+
 class EssentialGraphProblem(C.Structure):   # eao_essential_graph_problem
     _fields_ = [("n", C.c_int32), ("fixed", C.c_int32), ("fix_scale", C.c_int32), ("Scw", C.c_void_p), ("has_nc", C.c_void_p), ("Snc", C.c_void_p),
                 ("n_edges", C.c_int32), ("edges", C.c_void_p), ("n_points", C.c_int32), ("Xw", C.c_void_p), ("ref", C.c_void_p)]
@@ -195,6 +212,9 @@ SYMBOLS = {
     "eao_sim3_solver_iterate_batch": (_I, [_I, C.POINTER(Sim3SolverProblem), _P, _P, C.POINTER(Sim3SolverState), _P, _P, C.POINTER(Sim3SolverResult)]),
     "eao_initializer_initialize": (_I, [C.POINTER(InitializerProblem), _P, _I, C.POINTER(InitializerResult)]),
     "eao_initializer_last_kernel_ms": (_I, [_P]),
+    "eao_pnp_solver_iterate": (_I, [C.POINTER(PnpSolverProblem), _I, _I, _I, C.POINTER(PnpSolverState), _P, _I, C.POINTER(PnpSolverResult)]),
+    "eao_pnp_solver_iterate_batch": (_I, [_I, C.POINTER(PnpSolverProblem), _P, _P, _P, C.POINTER(PnpSolverState), _P, _P, C.POINTER(PnpSolverResult)]),
+    "eao_pnp_solver_last_kernel_ms": (_I, [_P]),
     "eao_optimize_essential_graph": (_I, [C.POINTER(EssentialGraphProblem), C.POINTER(EssentialGraphResult)]),
     "eao_essential_graph_plan": (_I, [C.POINTER(EssentialGraphProblem), _P, _P, _P, _I]),
     "eao_bundle_adjustment_plan": (_I, [_I, _I, _P, _P, _I, _P, _P, _P, _I, _P, _I, _P, _I, _P, _I, _P, _I, _P, _I]),

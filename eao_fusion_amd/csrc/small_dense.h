@@ -1,5 +1,6 @@
 // small_dense.h -- the small dense helpers the geometric solvers share (device code; include from a .hip).
 //   smallest_eigenvector   4 x 4 symmetric, per lane in registers (triangulate.hip, initializer.hip: the vt.row(3) of a 4 x 4 cv::SVD)
+//   jacobi_sym<N>          symmetric N x N eigenproblem, one wavefront, S and V in LDS (null_vector9; pnp_internal.h: cvSVD of the symmetric 3 x 3 and 12 x 12)
 //   null_vector9           right singular vector of the smallest singular value of a k x 9 float system, one wavefront, S and V in LDS
 //   svd3                   full 3 x 3 SVD of a float matrix (U, w, Vt as cv::SVD::compute with FULL_UV holds them: CV_32F, w descending)
 //   inv3 / mul3 / det3     OpenCV's 3 x 3 float inverse, product and determinant
@@ -59,7 +60,7 @@ __device__ __forceinline__ void smallest_eigenvector(double (&S)[4][4], double (
 }
 
 // the Jacobi rotation that annihilates S[p][q] (c = 1, s = 0 when it is exactly zero: nothing to annihilate)
-__device__ __forceinline__ void jacobi_cs(double app, double aqq, double apq, double& c, double& s) {
+__host__ __device__ __forceinline__ void jacobi_cs(double app, double aqq, double apq, double& c, double& s) {
     c = 1.0; s = 0.0;
     if (apq != 0.0) {
         const double theta = (aqq - app) / (2.0 * apq);
@@ -69,9 +70,51 @@ __device__ __forceinline__ void jacobi_cs(double app, double aqq, double apq, do
     }
 }
 
+// One wavefront, N <= 64.  `sweeps` cyclic Jacobi sweeps over the symmetric N x N S (row-major doubles in LDS); V (N x N, the identity on entry) leaves with the
+// eigenvectors in its columns, S with the eigenvalues on its diagonal, in no particular order.  Lane k < N owns row / column k of a rotation; the pair (p, q) is
+// uniform over the wave, so the runtime indices are LDS addresses, never register indices.  The sweep count is fixed: a NaN ends like any other input.  The host
+// pass of the compiler sees the same rotations with the lanes as a loop (a rotation's two phases touch disjoint entries per k), for CPU checks of the callers.
+template <int N>
+__host__ __device__ inline void jacobi_sym(double* S, double* V, int sweeps, int lane) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    const bool own = lane < N;
+    const int k = own ? lane : 0;
+#pragma unroll 1
+    for (int sweep = 0; sweep < sweeps; sweep++) {
+#pragma unroll 1
+        for (int p = 0; p < N - 1; p++)
+#pragma unroll 1
+            for (int q = p + 1; q < N; q++) {
+                double c, s;
+                jacobi_cs(S[N * p + p], S[N * q + q], S[N * p + q], c, s);
+                wave_sync();
+                if (own) { const double a = S[N * k + p], b = S[N * k + q]; S[N * k + p] = c * a - s * b; S[N * k + q] = s * a + c * b; }
+                wave_sync();
+                if (own) {
+                    const double a = S[N * p + k], b = S[N * q + k]; S[N * p + k] = c * a - s * b; S[N * q + k] = s * a + c * b;
+                    const double va = V[N * k + p], vb = V[N * k + q]; V[N * k + p] = c * va - s * vb; V[N * k + q] = s * va + c * vb;
+                }
+                wave_sync();
+            }
+    }
+#else
+    (void)lane;
+    for (int sweep = 0; sweep < sweeps; sweep++)
+        for (int p = 0; p < N - 1; p++)
+            for (int q = p + 1; q < N; q++) {
+                double c, s;
+                jacobi_cs(S[N * p + p], S[N * q + q], S[N * p + q], c, s);
+                for (int k = 0; k < N; k++) { const double a = S[N * k + p], b = S[N * k + q]; S[N * k + p] = c * a - s * b; S[N * k + q] = s * a + c * b; }
+                for (int k = 0; k < N; k++) {
+                    const double a = S[N * p + k], b = S[N * q + k]; S[N * p + k] = c * a - s * b; S[N * q + k] = s * a + c * b;
+                    const double va = V[N * k + p], vb = V[N * k + q]; V[N * k + p] = c * va - s * vb; V[N * k + q] = s * va + c * vb;
+                }
+            }
+#endif
+}
+
 // One wavefront.  A: rows x 9 floats in LDS (row-major, rows <= 16); S, V: 81 doubles each in LDS (scratch).  Every lane leaves with the same h: the eigenvector of
-// the smallest eigenvalue (the first of equal ones) of A^T A, rounded to float -- vt.row(8) of cv::SVDecomp(A, FULL_UV) up to its sign.  Lane k < 9 owns row / column k
-// of a rotation; the pair (p, q) is uniform over the wave, so the runtime indices are LDS addresses, never register indices.
+// the smallest eigenvalue (the first of equal ones) of A^T A, rounded to float -- vt.row(8) of cv::SVDecomp(A, FULL_UV) up to its sign (jacobi_sym<9>).
 __device__ __forceinline__ void null_vector9(const float* A, int rows, double* S, double* V, int lane, float (&h)[9]) {
     for (int e = lane; e < 81; e += 64) {
         const int i = e / 9, j = e - 9 * i;
@@ -81,26 +124,7 @@ __device__ __forceinline__ void null_vector9(const float* A, int rows, double* S
         V[e] = i == j ? 1.0 : 0.0;
     }
     wave_sync();
-    const bool own = lane < 9;
-    const int k = own ? lane : 0;
-#pragma unroll 1
-    for (int sweep = 0; sweep < kSweeps9; sweep++) {
-#pragma unroll 1
-        for (int p = 0; p < 8; p++)
-#pragma unroll 1
-            for (int q = p + 1; q < 9; q++) {
-                double c, s;
-                jacobi_cs(S[9 * p + p], S[9 * q + q], S[9 * p + q], c, s);
-                wave_sync();
-                if (own) { const double a = S[9 * k + p], b = S[9 * k + q]; S[9 * k + p] = c * a - s * b; S[9 * k + q] = s * a + c * b; }
-                wave_sync();
-                if (own) {
-                    const double a = S[9 * p + k], b = S[9 * q + k]; S[9 * p + k] = c * a - s * b; S[9 * q + k] = s * a + c * b;
-                    const double va = V[9 * k + p], vb = V[9 * k + q]; V[9 * k + p] = c * va - s * vb; V[9 * k + q] = s * va + c * vb;
-                }
-                wave_sync();
-            }
-    }
+    jacobi_sym<9>(S, V, kSweeps9, lane);
     int jmin = 0;
     double best = S[0];
 #pragma unroll 1

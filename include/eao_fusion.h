@@ -973,6 +973,87 @@ eao_status eao_initializer_initialize(const eao_initializer_problem* problem, co
  * eao_initializer_initialize (hypotheses, scores, selection, CheckRT, final rule), from HIP events on its stream.  EAO_ERR_INVALID when there is no measurement. */
 eao_status eao_initializer_last_kernel_ms(float* kernel_ms /* 5 */);
 
+/* ------------------------------------------------------------------------------------------------
+ * PnPsolver (reference include/PnPsolver.h, src/PnPsolver.cc): the EPnP RANSAC of Tracking::Relocalization (src/Tracking.cc:2786-2940), the step before
+ * PoseOptimization.  One call is one PnPsolver::iterate (:165-258): compute_pose (:477-525) and CheckInliers (:308-339) of all its hypotheses together (one
+ * wavefront each), the records among their counts, Refine (:260-305) of each record, then the sequential rule of the loop replayed on the device.
+ * ------------------------------------------------------------------------------------------------ */
+typedef struct {
+    int32_t n;                  /* N: the correspondences the constructor keeps (:67-110), in index order */
+    const float* p3d_w;         /* n*3: mvP3Dw */
+    const float* p2d;           /* n*2: mvP2D */
+    const float* sigma2;        /* n: mvSigma2 */
+    float fx, fy, cx, cy;       /* F.fx .. F.cy; held in double from there on, as fu, fv, uc, vc are */
+    float th2;                  /* the gate of correspondence i is the float sigma2[i] * th2 (:154-156) */
+} eao_pnp_solver_problem;
+
+/* What survives between iterate calls (in/out).  A new solver starts from all zeros (best_inlier: n zero bytes). */
+typedef struct {
+    int32_t iterations;         /* mnIterations */
+    int32_t best_inliers;       /* mnBestInliers */
+    float best_Tcw[16];         /* mBestTcw, row-major 4x4 */
+    uint8_t* best_inlier;       /* n, caller-allocated: mvbBestInliers (Refine reads it across calls); exactly best_inliers of them are set */
+} eao_pnp_solver_state;
+
+typedef struct {
+    int32_t returned;           /* -1: iterate returns an empty Mat.  refined = 1: the position in the chunk of the hypothesis whose Refine succeeded (:226-236).
+                                 * refined = 0: the position of the best hypothesis (:241-254), or n_hyp when the state carried it in */
+    int32_t refined;            /* which of the two return paths was taken (0 when nothing returns) */
+    int32_t n_inliers;          /* nInliers (0 unless returned >= 0) */
+    float Tcw[16];              /* the returned pose: the float rounding of the doubles (zeros unless returned >= 0) */
+    uint8_t* inlier;            /* n flags over the correspondences (caller-allocated), written only when returned >= 0 */
+    int32_t no_more;            /* bNoMore */
+    int32_t n_records;          /* entries of the rec_* arrays */
+    /* inspection, each written when non-NULL */
+    double* hyp_R;              /* n_hyp*9: mRi of compute_pose over the sampled set */
+    double* hyp_t;              /* n_hyp*3: mti */
+    double* hyp_rep_err;        /* n_hyp*3: rep_errors[1..3] */
+    int32_t* hyp_choice;        /* n_hyp: N of :518-520 */
+    int32_t* hyp_inliers;       /* n_hyp: mnInliersi */
+    uint8_t* hyp_inlier;        /* n_hyp*n: mvbInliersi */
+    /* the sets Refine ran on, (n_hyp+1) entries each of which n_records are live: first the state's best_inlier set when best_inliers > 0 (rec_hyp = -1), then each
+     * record up to the hypothesis that ended the call (records past it leave no trace; entries past n_records are zero) */
+    int32_t* rec_hyp;           /* position of the record in the chunk, -1 for the carried set */
+    double* rec_R;              /* *9: mRi of Refine's compute_pose */
+    double* rec_t;              /* *3 */
+    int32_t* rec_inliers;       /* mnRefinedInliers; Refine succeeded when it is > min_inliers */
+    uint8_t* rec_inlier;        /* *n: mvbRefinedInliers */
+} eao_pnp_solver_result;
+
+/* PnPsolver::iterate with mRansacMinInliers = min_inliers, mRansacMaxIts = max_its (the values SetRansacParameters :121-157 leaves; the adapter computes them)
+ * and mRansacMinSet = min_set (4 .. 64).  sets: n_hyp*min_set indices into 0 .. n-1 in draw order; an index may repeat inside a set (the sampling loop of
+ * :191-201 can produce that).  n_hyp is the number of passes the loop `while(mnIterations<mRansacMaxIts || nCurrentIterations<nIterations)` (:182) makes: note
+ * the ||, it is max(nIterations, max_its - iterations), so the first iterate(5) of Relocalization runs all of its max_its.  All n_hyp hypotheses are evaluated.
+ * In order: a hypothesis with inliers >= min_inliers and inliers > best_inliers (strict) is a record and becomes the best; at every hypothesis that passes the
+ * >= gate upstream runs Refine on the best set, which is deterministic, so it is computed once per record (and once for the set the state carries in); the first
+ * gate-passing hypothesis whose best set refines to more than min_inliers (strict) inliers ends the call: iterations advances up to and including it.  Otherwise
+ * no_more = iterations >= max_its, and with it the best pose returns when best_inliers >= min_inliers.  n < min_inliers: no_more, nothing evaluated, state untouched.
+ * EAO_ERR_INVALID before anything is written: an index out of range, min_set < 4 or > 64, a non-finite input, n < min_set, a best_inlier set whose size is not
+ * best_inliers.
+ * Arithmetic: EPnP in double, op for op (-ffp-contract=off); CheckInliers with upstream's mixed widths.  OpenCV's parts: cvSVD of the symmetric 3 x 3 and 12 x 12
+ * is a cyclic Jacobi eigen-solve in double with a fixed sweep count, singular values |lambda| descending (the lower index first among equals); the 3 x 3 SVD of ABt
+ * by the scheme of the Initializer's (eigenvectors of A^T A, u = A v normalised); cvInvert / cvSolve(CV_SVD) are the minimum-norm least-squares solution through
+ * a one-sided Jacobi SVD, a singular value counting when it exceeds 2 * DBL_EPSILON * (the sum of all of them).  Two deviations from upstream:
+ *  1. The PCA axes of choose_control_points (the rows of UCt) are signed so that the component of largest magnitude is positive (the lowest index wins a tie);
+ *     upstream's sign is cvSVD's, and the pose depends on it at the noise level.
+ *  2. gauss_newton's X starts at zero; upstream's is uninitialised when qr_solve leaves through its `eta == 0` return in the first iteration.
+ * Nothing is repaired: coplanar or repeated points, a zero depth and a NaN flow through; a NaN error2 is an outlier.  With min_set = 4 the null space of M^T M has
+ * four dimensions and a hypothesis' pose depends on the basis the eigen-solver returns: it is this library's, not upstream's.  Two calls on the same arguments
+ * return the same bytes. */
+eao_status eao_pnp_solver_iterate(const eao_pnp_solver_problem* problem, int32_t min_inliers, int32_t max_its, int32_t min_set, eao_pnp_solver_state* state,
+                                  const int32_t* sets, int32_t n_hyp, eao_pnp_solver_result* result);
+
+/* One round of Relocalization's loop over its candidates (src/Tracking.cc:2847-2870) in one launch chain: problem b with min_inliers[b], max_its[b], min_set[b],
+ * states[b], sets[b] (n_hyp[b]*min_set[b] indices) and results[b].  Each result and state is bit-identical to what eao_pnp_solver_iterate returns for it.  Any
+ * invalid problem fails the call before anything is written. */
+eao_status eao_pnp_solver_iterate_batch(int32_t n_problems, const eao_pnp_solver_problem* problems, const int32_t* min_inliers, const int32_t* max_its,
+                                        const int32_t* min_set, eao_pnp_solver_state* states, const int32_t* const* sets, const int32_t* n_hyp,
+                                        eao_pnp_solver_result* results);
+
+/* Diagnostic (tools/bench_pnp_solver.py): with EAO_PNP_EVENTS=1 in the environment, the device time in ms of each of the four kernels of this thread's last
+ * eao_pnp_solver_iterate / _batch (hypotheses, scan, refine, finish), from HIP events on its stream.  EAO_ERR_INVALID when there is no measurement. */
+eao_status eao_pnp_solver_last_kernel_ms(float* kernel_ms /* 4 */);
+
 /* The value of EAO_ABI_VERSION the library was built with. Bumped whenever an entry point's parameter list or a struct's layout changes (round 3
  * changed eao_tracker_track_local_map and eao_track_result in place); a caller compiled against another version must not call into the library.
  * Result structs are zero-initialised by the caller (`eao_track_result R = {0};`) before their array pointers are set: a pointer member the
