@@ -1,8 +1,9 @@
-// lm_host.hip -- host side of the Levenberg-Marquardt engine: per-thread contexts, BAJob (validation, arena, pinned mirror, active structure, the map-scale path's
-// covisibility / tile structure, host-stepped trials), eao_local_ba / eao_local_ba_batch / eao_bundle_adjustment(_planes) and the traces.  Kernels: lba.hip, gba.hip
-// (launched through BALaunch).  Shared pieces: lm_internal.h.  (Round 6: split out of csrc/lm.hip.)
+// lm_host.hip -- host side of the Levenberg-Marquardt engine: per-thread contexts, BAJob (arena, pinned mirror, uploads, tile structure, host-stepped trials; its set-up
+// stages that need no device -- validation, the map-scale path's covisibility structure, the active structure, the launch order -- are ba_setup.h, plain C++),
+// eao_local_ba / eao_local_ba_batch / eao_bundle_adjustment(_planes) and the traces.  Kernels: lba.hip, gba.hip (launched through BALaunch).  Shared pieces:
+// lm_internal.h.  (Round 6: split out of csrc/lm.hip.)
 #include "lm_internal.h"
-#include "host_crew.h"
+#include "ba_setup.h"
 
 namespace eao {
 namespace lm {
@@ -67,358 +68,100 @@ struct BAJob {
     }
     bool batchable() const { return !trivial && chained && L.d.usePairs && L.d.solveTiles && !hasPl && !L.d.bigPath && D.nFree > 0 && D.nL > 0 && mode == 0; }
 
-    // validation, arena, pinned mirror, upload (two copies on `s`), active structure.  No kernel is launched here.
+    // ---- prepare(): validation, arena, pinned mirror, upload (two copies on `s`), active structure.  No kernel is launched here.  The stages that need no device
+    //      (counts, covisibility lists and pairs, active structure, launch order) are the free functions of ba_setup.h; the members below are the ones that need
+    //      the window record, the arena, the context and the HIP runtime.
     // deferUpload (batches): NO call into the HIP runtime at all -- the pinned mirror is filled and [upSrc, upSrc + upBytes) is left
     // for the group's leader, which moves every window of its group with ONE launch of k_ba_upload (the copies' enqueue calls
     // serialise inside the runtime: 50 of them were most of a batch's 0.55 ms of set-up, and more host threads made it worse).
     const unsigned char* upSrc = nullptr; unsigned char* upDst = nullptr; size_t upBytes = 0;
-    eao_status prepare(hipStream_t s, bool deferUpload = false) {
-        eao::Range rg("lm: window set-up + upload");
+    bool bigPath = false;      // the map-scale path: dense system in HBM factorised by the whole chip (k_bal_*)
+    int nFreeIn = 0;           // free keyframes of the problem (with or without edges)
+    bool pair_path() const { return !bigPath && nFreeIn > 0 && nFreeIn <= kTileMaxFree; }
+
+    // The uploaded part of the window's arena, slice by slice: device addresses, and host() = the same slice in the pinned mirror (filled in place, sent with two copies).
+    struct Carve {
+        unsigned char* base = nullptr; unsigned char* pin = nullptr;
+        size_t off0 = 0, off1 = 0;      // the uploaded part is [off0, off1)
+        float* obs; float* info; int* ecam; int* ept; SE3* cams; double* pts; unsigned char* flag;
+        int* camIdx; int* ptIdx; int* actCam; int* actPt; int* ptStart; int* ptEdges; int* camStart; int* camEdges;
+        int* ctl;      // two control blocks: see BADecision
+        int* lpStart; int* lpPair; int* lpOrder; size_t lpOrderCap;
+        size_t nObs;      // (observer list entries + 1)
+        int* lmOff; int* lmCam; int* lmEdge; int* cmOff; int* cmLm; int* cmU;
+        int* bigTile; int4* bigWork; int* bigRow; int* bigRowCam; int4* bigSB; int* bigDiagList;
+        double* pl0; double* pmeas;
+        template <typename T> T* host(T* dev) const { return reinterpret_cast<T*>(pin + (reinterpret_cast<unsigned char*>(dev) - base)); }
+    };
+
+    eao_status check_arguments() {
         EAO_REQUIRE(p && r && r->cam_Tcw && r->points && (p->n_edges == 0 || r->edge_outlier || mode == 1), "null argument");
         EAO_REQUIRE(p->n_cams > 0 && p->n_points >= 0 && p->n_edges >= 0, "bad sizes");
         if (pl && pl->n_planes <= 0) pl = nullptr;
         EAO_REQUIRE(!pl || (mode == 1 && pl->plane_world && planes_out && pl->n_pedges >= 0 && (pl->n_pedges == 0 || (pl->pedge_plane && pl->pedge_cam && pl->pedge_obs))),
                     "bad plane arguments");
-        LMContext& c = *this->c;
-        eao_status st;
-        tr->clear();
-        static const bool hostStamps = getenv("EAO_DEBUG_STAMPS") != nullptr;      // host phases of the set-up, in ms on stderr
-        const auto hs0 = std::chrono::steady_clock::now();
-        double hsT[12] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
-        auto hs_lap = [&](int k) { if (hostStamps) hsT[k] = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - hs0).count(); };
         nPo = p->n_points; nPl = pl ? pl->n_planes : 0; Ept = p->n_edges; Epl = pl ? pl->n_pedges : 0;
         nC = p->n_cams; nP = nPo + nPl; E = Ept + Epl;          // landmarks = points then planes, edges = point edges then plane edges
         hasPl = nPl > 0;
-        const eao_ba_problem* p = this->p; const eao_ba_planes* pl = this->pl;
-        const int nPo = this->nPo, Ept = this->Ept;
-        auto edge_cam = [=](int e) { return e < Ept ? p->edge_cam[e] : pl->pedge_cam[e - Ept]; };
-        auto edge_lm = [=](int e) { return e < Ept ? p->edge_point[e] : nPo + pl->pedge_plane[e - Ept]; };
-        r->iters[0] = r->iters[1] = 0; r->aborted = 0; r->chi2[0] = r->chi2[1] = 0;
-        if (stop && *stop) {  // src/Optimizer.cc:961-963: nothing is optimised; poses go through the same SE3 round trip
-            r->aborted = 1;
-            for (int i = 0; i < nC; i++) se3_to_Tcw_f32(se3_from_Tcw_f32(p->cam_Tcw + 16 * i), r->cam_Tcw + 16 * i);
-            for (size_t i = 0; i < (size_t)nPo * 3; i++) r->points[i] = p->points[i];
-            for (int i = 0; i < nPl; i++) { double c4[4]; plane_from_f32(pl->plane_world + 4 * i, c4); for (int k = 0; k < 4; k++) planes_out[4 * i + k] = (float)c4[k]; }
-            if (Ept && r->edge_outlier) std::memset(r->edge_outlier, 0, Ept);
-            trivial = true;
-            return EAO_OK;
+        return EAO_OK;
+    }
+    EdgeView edge_view() const {
+        EdgeView v;
+        v.nC = nC; v.nPo = nPo; v.nPl = nPl; v.Ept = Ept; v.Epl = Epl;
+        v.edge_cam = p->edge_cam; v.edge_point = p->edge_point; v.cam_fixed = p->cam_fixed;
+        v.pedge_cam = pl ? pl->pedge_cam : nullptr; v.pedge_plane = pl ? pl->pedge_plane : nullptr;
+        return v;
+    }
+    void abort_shortcut() {  // src/Optimizer.cc:961-963: nothing is optimised; poses go through the same SE3 round trip
+        r->aborted = 1;
+        for (int i = 0; i < nC; i++) se3_to_Tcw_f32(se3_from_Tcw_f32(p->cam_Tcw + 16 * i), r->cam_Tcw + 16 * i);
+        for (size_t i = 0; i < (size_t)nPo * 3; i++) r->points[i] = p->points[i];
+        for (int i = 0; i < nPl; i++) { double c4[4]; plane_from_f32(pl->plane_world + 4 * i, c4); for (int k = 0; k < 4; k++) planes_out[4 * i + k] = (float)c4[k]; }
+        if (Ept && r->edge_outlier) std::memset(r->edge_outlier, 0, Ept);
+        trivial = true;
+    }
+
+    // ---- the ORDER, TILE structure and launch SCHEDULE of the map-scale system (GbaPlan, gba.hip; round 5 built the tile structure here in natural keyframe order):
+    //      which 64 x 64 tiles of the lower triangle can ever be non-zero -- the tiles a covisible camera pair's 6 x 6 block touches in the elimination order, the
+    //      diagonal, the tile row of the right-hand side, and the fill-in of the elimination worked out at tile level (the block form of the symbolic factorisation a
+    //      sparse LDL^T starts with, solvers/linear_solver_eigen.h:95-112).  Memory and the launches' grids follow this structure.  The plan is a pure function of
+    //      the pair list; the context keeps it while the list's hash stays the same (it is read by the launches of this window, long after prepare has returned).
+    eao_status update_plan(const SetupScratch& S, bool hostStamps) {
+        GbaPlan& plan = c->plan;
+        const int nFa = S.nFa;
+        const int forceP = getenv("EAO_BA_ND") ? atoi(getenv("EAO_BA_ND")) : 0;      // (read per call: A/B runs and the tests -- 1 = natural order, p > 1 = p segments)
+        const uint64_t key = gba_pattern_hash(nFa, S.prA, S.prB) ^ ((uint64_t)(unsigned)forceP << 48);
+        if (!plan.valid || plan.key != key || plan.nFa != nFa) {
+            gba_build_plan(nFa, S.prA, S.prB, forceP, plan);
+            plan.key = key; plan.valid = true;
+            if (hostStamps) fprintf(stderr, "[eao map-scale plan] %d free keyframes (bandwidth %d%s): %d segment(s), %d separator keyframes, %d rows in %d tiles; %zu factorisation launches "
+                                    "(natural order: %d), %zu back-substitution launches, %zu work records\n", nFa, plan.bandwidth, plan.rcm ? ", reverse Cuthill-McKee line" : "", plan.P,
+                                    plan.nSep, plan.N, plan.bigTiles, plan.launches.size(), plan.chainNatural, plan.sbLaunches.size(), plan.work.size() / 2);
         }
-        bool edgesByLandmark = true;      // the edge list is grouped landmark by landmark, ascending (what the adapters and every generator produce): ptEdges is then the identity
-        int nFreeIn = 0;
-        for (int i = 0; i < nC; i++) nFreeIn += p->cam_fixed[i] ? 0 : 1;
-        EAO_REQUIRE(nFreeIn <= kBigMaxFree, "at most %d free keyframes in this build (got %d)", kBigMaxFree, nFreeIn);
-        // more free keyframes than the single-workgroup solvers take (or EAO_BA_SOLVER=big, the harness's A/B switch): the
-        // map-scale path, dense system in HBM factorised by the whole chip (k_bal_*)
-        const char* const solverEnv0 = getenv("EAO_BA_SOLVER");      // (read per call, like the switches below: a test sets it after the process's first call)
-        // (measured, LocalBundleAdjustment wall time, tools/dbg_ba_sizes.py: the LDS / global-scratch single-workgroup solver with
-        //  the slab assembly takes 5.8 ms at 31 free keyframes and 29 ms at 64, the map-scale path 3.6 and 6.9 ms -- so everything
-        //  beyond the register-tile solver goes there; that older path was removed in round 5)
-        const bool bigPath = nFreeIn > kTileMaxFree || (nFreeIn > 0 && solverEnv0 && !strcmp(solverEnv0, "big"));
-        // ---- round 6: the set-up of a map-scale call runs as a SESSION of the host crew (HostCrew: one wake-up, then passes handed over through one polled word):
-        //      validation + counts, the observer / camera lists, the pair counts, the problem pack and the pair lists are each a pass over landmark or camera ranges.
-        //      EAO_BA_SETUP_THREADS: 1 = the serial walks, n > 1 = a session of n threads on any map (the tests), unset = a session from 20 000 edges on.
-        const int envSetupT = getenv("EAO_BA_SETUP_THREADS") ? atoi(getenv("EAO_BA_SETUP_THREADS")) : 0;      // (read per call)
-        struct SessionGuard {
-            bool open = false;
-            ~SessionGuard() { if (open) host_crew().session_end(); }
-        } session;
-        if (bigPath && !t_inCrew && envSetupT != 1 && (Ept >= 20000 || envSetupT > 1)) {
-            const int hw = (int)std::thread::hardware_concurrency();
-            const int nT = envSetupT > 1 ? envSetupT : std::max(2, std::min(12, hw / 2));
-            session.open = host_crew().session_begin(nT - 1);
-        }
-        // ... and, in the same pass over the edges, the edge counts per camera and per landmark the active structure starts from
-        std::vector<int>& cnt = c.scratch;
-        cnt.assign((size_t)nC + nP, 0);
-        int* const camCnt = cnt.data(); int* const ptCnt = camCnt + nC;
-        // ---- the parallel form of that pass (sessions; no plane edges): chunks of the edge list cut at landmark boundaries.  Every chunk validates its edges, checks that
-        //      the landmarks ascend, counts each landmark's edges (a landmark's run belongs to one chunk) and its own edges per camera, looks for a camera that appears
-        //      twice in a landmark, and counts what the covisibility structure needs (free observers, pair entries).  Anything unexpected -- an index out of range, a
-        //      landmark out of order -- and the serial pass below runs instead (and words the error).
-        constexpr int kQ = 48;
-        static thread_local std::vector<int> cb, cl, chunkFree, camCntQ, camLastQ, chunkBad, cmE;
-        static thread_local std::vector<long long> chunkEnt;
-        bool countedInChunks = false;
-        if (session.open && Epl == 0 && Ept > 0) {
-            const int* const ecam = p->edge_cam; const int* const ept = p->edge_point; const uint8_t* const fixedp = p->cam_fixed;
-            cb.assign(kQ + 1, Ept);
-            for (int q = 0; q < kQ; q++) {      // chunk q = edges [cb[q], cb[q + 1]); boundaries moved forward to the end of a run of equal landmarks
-                int e = (int)((long long)Ept * q / kQ);
-                while (e > 0 && e < Ept && ept[e] == ept[e - 1]) e++;
-                cb[q] = std::min(e, Ept);
-            }
-            cb[0] = 0;
-            for (int q = 1; q <= kQ; q++) cb[q] = std::max(cb[q], cb[q - 1]);      // (monotone; an empty chunk is harmless)
-            chunkFree.assign(kQ, 0); chunkEnt.assign(kQ, 0); chunkBad.assign(2 * kQ, -1);
-            camCntQ.assign((size_t)kQ * nC, 0); camLastQ.assign((size_t)kQ * nC, -1);
-            {
-                int* const cfp = chunkFree.data(); long long* const cep = chunkEnt.data(); int* const ccq = camCntQ.data(); int* const clq = camLastQ.data();
-                const int* const cbp = cb.data(); int* const bad = chunkBad.data();
-                const int nC_ = nC, nPo_ = nPo;
-                host_crew().session_pass(kQ, [=](int q) {
-                    int* const cc = ccq + (size_t)q * nC_; int* const last = clq + (size_t)q * nC_;
-                    int freeN = 0; long long ent = 0;
-                    const int e1 = cbp[q + 1];
-                    int prev = cbp[q] > 0 ? ept[cbp[q] - 1] : -1;
-                    for (int e = cbp[q]; e < e1;) {
-                        const int lmk = ept[e];
-                        // (unsigned: `prev` of a chunk q > 0 is the caller's own, unvalidated entry in front of the chunk -- a negative landmark behind a more negative one ascends too)
-                        if ((unsigned)lmk >= (unsigned)nPo_ || lmk <= prev) { bad[2 * q] = -2; return; }
-                        int m = 0, run = 0;
-                        for (; e < e1 && ept[e] == lmk; e++, run++) {
-                            const int ec = ecam[e];
-                            if ((unsigned)ec >= (unsigned)nC_) { bad[2 * q] = -2; return; }
-                            if (last[ec] == lmk && bad[2 * q] == -1) { bad[2 * q] = ec; bad[2 * q + 1] = lmk; }
-                            last[ec] = lmk;
-                            cc[ec]++;
-                            m += fixedp[ec] ? 0 : 1;
-                        }
-                        __atomic_store_n(&ptCnt[lmk], run, __ATOMIC_RELAXED);      // (a landmark out of order could be written by two chunks: the serial pass then starts over)
-                        freeN += m; ent += (long long)m * (m + 1) / 2;
-                        prev = lmk;
-                    }
-                    cfp[q] = freeN; cep[q] = ent;
-                });
-            }
-            countedInChunks = true;
-            for (int q = 0; q < kQ; q++) countedInChunks = countedInChunks && chunkBad[2 * q] != -2;
-            if (countedInChunks) {
-                for (int q = 0; q < kQ; q++)
-                    if (chunkBad[2 * q] >= 0) { eao::set_error("two edges join camera %d and point %d", chunkBad[2 * q], chunkBad[2 * q + 1]); return EAO_ERR_INVALID; }
-                for (int i = 0; i < nC; i++) {      // a camera's count; per chunk: where the chunk's edges go inside the camera's list
-                    int run = 0;
-                    for (int q = 0; q < kQ; q++) { const int c0 = camCntQ[(size_t)q * nC + i]; camCntQ[(size_t)q * nC + i] = run; run += c0; }
-                    camCnt[i] = run;
-                }
-            } else std::fill(cnt.begin(), cnt.end(), 0);
-        }
-        if (!countedInChunks) {
-            for (int e = 0, prev = 0; e < Ept; e++) {
-                const int ec = p->edge_cam[e], ep = p->edge_point[e];
-                EAO_REQUIRE(ec >= 0 && ec < nC && ep >= 0 && ep < nPo, "edge %d out of range", e);
-                edgesByLandmark = edgesByLandmark && ep >= prev; prev = ep;
-                camCnt[ec]++; ptCnt[ep]++;
-            }
-            for (int e = 0, prev = 0; e < Epl; e++) {
-                const int ec = pl->pedge_cam[e], ep = pl->pedge_plane[e];
-                EAO_REQUIRE(ec >= 0 && ec < nC && ep >= 0 && ep < nPl, "plane edge %d out of range", e);
-                edgesByLandmark = edgesByLandmark && ep >= prev; prev = ep;
-                camCnt[ec]++; ptCnt[nPo + ep]++;
-            }
-        }
-        size_t lpEntries = 0, lpPairsMax = 0;
-        // ---- round 5: the covisibility structure of the map-scale path, CAMERA-MAJOR.  For every free camera i1 (ascending) the landmarks it observes in ascending
-        //      order, and for each of them its observers i2 >= i1: the pairs (i1, i2) of camera i1 are counted in a counter array of nF entries that stays in the
-        //      cache, come out sorted, and their entries are later written into ONE contiguous range per camera -- in ascending landmark order, which is the order the
-        //      assembly's fixed-order sums need.  (Rounds 3-5 walked the landmarks and scattered every (pair, landmark) entry through a counter per pair of the
-        //      whole nF (nF + 1) / 2 triangle, three times -- once into a byte matrix for the tile structure, once to count, once to fill: 9.8 + 2.4 ms of host time in
-        //      front of 26.7 ms of device time on the banded 1000-keyframe map.)  Same arrays as before, bit for bit.
-        //      Every landmark's observer list is sorted by camera, so a camera's partners i2 >= i1 in a landmark are the SUFFIX behind its own entry: no test per
-        //      observer (it failed half the time and mispredicted).  Both walks -- counting and filling -- are split over the host crew by camera ranges of equal
-        //      size taken from a shared counter (a camera's pairs and entries are its own: no two workers write the same word).
-        static thread_local std::vector<int> fidx, lmOff, lmCam, lmEdge, cmOff, cmLm, cmU, prA, prB, prStart, cmPairStart, pcur;
-        // workers for the two walks: the crew unless this thread is one of its own (a map-scale window inside a batch call), or the map is small
-        auto crew_for = [&](size_t work, int nChunks, const std::function<void(int)>& chunk) {
-            if (session.open) { host_crew().session_pass(nChunks, chunk); return; }
-            const int hw = (int)std::thread::hardware_concurrency();
-            const int nT = t_inCrew || envSetupT == 1 || (work < 200000 && envSetupT <= 0) ? 1 : std::max(1, std::min(envSetupT > 0 ? envSetupT : std::min(12, hw / 2), nChunks));
-            if (nT == 1) { for (int q = 0; q < nChunks; q++) chunk(q); return; }
-            std::atomic<int> next(0);
-            auto body = [&]() { for (int q; (q = next.fetch_add(1)) < nChunks;) chunk(q); };
-            host_crew().run(nT - 1, [&](int) { body(); }, body);
-        };
-        // ---- the ORDER, TILE structure and launch SCHEDULE of the map-scale system (GbaPlan, gba.hip; round 5 built the tile structure here in natural keyframe order):
-        //      which 64 x 64 tiles of the lower triangle can ever be non-zero -- the tiles a covisible camera pair's 6 x 6 block touches in the elimination order, the
-        //      diagonal, the tile row of the right-hand side, and the fill-in of the elimination worked out at tile level (the block form of the symbolic factorisation a
-        //      sparse LDL^T starts with, solvers/linear_solver_eigen.h:95-112).  Memory and the launches' grids follow this structure.  The plan is a pure function of
-        //      the pair list; the context keeps it while the list's hash stays the same.
-        GbaPlan& plan = c.plan;             // (read by the launches of this window, long after this function has returned: the context's)
-        int bigT = 0, bigTiles = 0;
-        if (bigPath) {
-            // free cameras with at least one edge, in ascending order (the numbering the active structure below gives them: camIdx)
-            fidx.assign((size_t)nC, -1);
-            lmOff.assign((size_t)nP + 1, 0);
-            int nFa = 0;
-            for (int i = 0; i < nC; i++) if (camCnt[i] && !p->cam_fixed[i]) fidx[i] = nFa++;      // (camCnt: the validation pass)
-            // per landmark: its free observers and their edges, in edge order (the order of the active structure's ptEdges)
-            // ---- round 6: the observer lists and the camera lists in PARALLEL PASSES over landmark ranges (the serial walks below took 2.3 of the 4.8 ms of host
-            //      set-up in front of the 1000-keyframe map's 7.5 ms of device time).  With the edges listed landmark by landmark (what the adapters and every
-            //      generator produce; no plane edges) a landmark's edges are contiguous, so a chunk of the edge list cut at landmark boundaries owns its landmarks:
-            //      the validation pass above has counted every chunk's free observers, pair entries and edges per camera; the pass here writes the observer lists
-            //      (sorted by camera) and files every entry under its camera at the position the chunks before it left -- a camera's list comes out in ascending
-            //      landmark order, the same arrays as the serial walk, element for element (tests/test_gpu_lm.py::test_map_scale_set_up_on_the_host_crew), and the
-            //      camera's edge list of the active structure (camEdges) with it.
-            const bool parallelLists = countedInChunks;
-            if (parallelLists) {
-                const int Q = kQ;
-                const int* const ecam = p->edge_cam; const int* const ept = p->edge_point;
-                cl.assign(Q + 1, nP);
-                cl[0] = 0;
-                for (int q = 1; q < Q; q++) cl[q] = cb[q] < Ept ? ept[cb[q]] : nP;
-                // chunk bases; per camera the start of its list and, per chunk, where the chunk's entries go
-                static thread_local std::vector<int> chunkBase;
-                chunkBase.assign(Q + 1, 0);
-                for (int q = 0; q < Q; q++) { chunkBase[q + 1] = chunkBase[q] + chunkFree[q]; lpEntries += (size_t)chunkEnt[q]; }
-                EAO_REQUIRE(lpEntries < ((size_t)1 << 31), "covisibility structure too large (%zu pair entries)", lpEntries);
-                hs_lap(8);
-                const int total = chunkBase[Q];
-                lmCam.resize((size_t)total + 1); lmEdge.resize((size_t)total + 1);
-                cmOff.assign((size_t)nFa + 1, 0);
-                for (int i = 0; i < nC; i++) if (fidx[i] >= 0) cmOff[fidx[i] + 1] = camCnt[i];
-                for (int f = 0; f < nFa; f++) cmOff[f + 1] += cmOff[f];
-                cmLm.resize(cmOff[nFa]); cmU.resize(cmOff[nFa]); cmE.resize(cmOff[nFa]);
-                hs_lap(9);
-                {
-                    int* const lmOffp = lmOff.data(); int* const lc = lmCam.data(); int* const le = lmEdge.data(); const int* const fi = fidx.data();
-                    int* const ccq = camCntQ.data(); const int* const cbp = cb.data(); const int* const clp = cl.data(); const int* const basep = chunkBase.data();
-                    const int* const cmOffp = cmOff.data(); int* const cmLmp = cmLm.data(); int* const cmUp = cmU.data(); int* const cmEp = cmE.data();
-                    const int nFa_ = nFa;
-                    static thread_local std::vector<int> ccF;      // per chunk and free camera: where the chunk's entries go inside the camera's list (camCntQ, renumbered)
-                    ccF.resize((size_t)Q * nFa);
-                    for (int q = 0; q < Q; q++)
-                        for (int i = 0; i < nC; i++) if (fidx[i] >= 0) ccF[(size_t)q * nFa + fidx[i]] = ccq[(size_t)q * nC + i];
-                    int* const ccFp = ccF.data();
-                    crew_for((size_t)Ept * 8, Q, [=](int q) {
-                        int* const cc = ccFp + (size_t)q * nFa_;
-                        int at = basep[q], e = cbp[q];
-                        const int lEnd = clp[q + 1];
-                        for (int lmk = clp[q]; lmk < lEnd; lmk++) {
-                            lmOffp[lmk] = at;      // (a landmark without edges: an empty list)
-                            const int first = at;
-                            for (; e < cbp[q + 1] && ept[e] == lmk; e++) { const int f = fi[ecam[e]]; if (f >= 0) { lc[at] = f; le[at] = e; at++; } }
-                            for (int u = first + 1; u < at; u++) {      // observers by camera (insertion sort: a handful per landmark, mostly in order already)
-                                const int cf = lc[u], ce = le[u];
-                                int v = u;
-                                for (; v > first && lc[v - 1] > cf; v--) { lc[v] = lc[v - 1]; le[v] = le[v - 1]; }
-                                lc[v] = cf; le[v] = ce;
-                            }
-                            for (int u = first; u < at; u++) { const int f = lc[u], pos = cmOffp[f] + cc[f]++; cmLmp[pos] = lmk; cmUp[pos] = u; cmEp[pos] = le[u]; }
-                        }
-                    });
-                    lmOff[nP] = total;
-                }
-                hs_lap(10);
-            } else {
-                bool byLandmark = true;        // the edges come landmark by landmark (the adapters and every generator list them so): the observer lists are then a filtered copy
-                for (int e = 0, prev = 0; e < E; e++) { const int lmk = edge_lm(e); byLandmark = byLandmark && lmk >= prev; prev = lmk; if (fidx[edge_cam(e)] >= 0) lmOff[lmk + 1]++; }
-                for (int i = 0; i < nP; i++) {
-                    const int m = lmOff[i + 1];
-                    lpEntries += (size_t)m * (m + 1) / 2;
-                    lmOff[i + 1] += lmOff[i];
-                }
-                EAO_REQUIRE(lpEntries < ((size_t)1 << 31), "covisibility structure too large (%zu pair entries)", lpEntries);
-                hs_lap(8);
-                lmCam.resize((size_t)lmOff[nP] + 1); lmEdge.resize((size_t)lmOff[nP] + 1);      // (+ 1: the branch-free append writes one slot ahead)
-                cmOff.assign((size_t)nFa + 1, 0);
-                if (byLandmark) {
-                    // (plain pointers and a branch-free append: the loop is a stream of 2 E loads and at most 2 E stores)
-                    int* const lc = lmCam.data(); int* const le = lmEdge.data(); int* const co = cmOff.data() + 1; const int* const fi = fidx.data();
-                    const int* const ecam = p->edge_cam; const int* const pcam = pl ? pl->pedge_cam : nullptr;
-                    int at = 0;
-                    for (int e = 0; e < Ept; e++) { const int f = fi[ecam[e]]; lc[at] = f; le[at] = e; const int ok = f >= 0; at += ok; if (ok) co[f]++; }
-                    for (int e = Ept; e < E; e++) { const int f = fi[pcam[e - Ept]]; lc[at] = f; le[at] = e; const int ok = f >= 0; at += ok; if (ok) co[f]++; }
-                } else {
-                    pcur.assign(lmOff.begin(), lmOff.end() - 1);
-                    for (int e = 0; e < E; e++) {
-                        const int f = fidx[edge_cam(e)];
-                        if (f < 0) continue;
-                        const int at = pcur[edge_lm(e)]++;
-                        lmCam[at] = f; lmEdge[at] = e; cmOff[f + 1]++;
-                    }
-                }
-                hs_lap(9);
-                for (int i = 0; i < nP; i++)           // observers by camera (insertion sort: a handful per landmark, mostly in order already)
-                    for (int u = lmOff[i] + 1; u < lmOff[i + 1]; u++) {
-                        const int cf = lmCam[u], ce = lmEdge[u];
-                        int v = u;
-                        for (; v > lmOff[i] && lmCam[v - 1] > cf; v--) { lmCam[v] = lmCam[v - 1]; lmEdge[v] = lmEdge[v - 1]; }
-                        lmCam[v] = cf; lmEdge[v] = ce;
-                    }
-                hs_lap(10);
-                // per free camera: its landmarks in ascending order (a counting sort over the landmarks, walked in ascending order), each with the position of the
-                // camera's own entry in that landmark's list
-                for (int f = 0; f < nFa; f++) cmOff[f + 1] += cmOff[f];
-                cmLm.resize(cmOff[nFa]); cmU.resize(cmOff[nFa]);
-                {   // (camera ranges on the crew: every worker walks all observer lists and files the entries of ITS cameras -- a camera's list is written by one worker, in landmark order)
-                    const int nRanges = std::max(1, std::min(16, nFa / 32));
-                    const int* const lmOffp = lmOff.data(); const int* const lmCamp = lmCam.data(); const int* const cmOffp = cmOff.data();
-                    int* const cmLmp = cmLm.data(); int* const cmUp = cmU.data();
-                    const int nPl_ = nP;
-                    crew_for(lpEntries, nRanges, [=](int q) {
-                        const int f0 = (int)((long long)nFa * q / nRanges), f1 = (int)((long long)nFa * (q + 1) / nRanges);
-                        static thread_local std::vector<int> curv;
-                        curv.assign(cmOffp + f0, cmOffp + f1);
-                        int* const cur = curv.data();
-                        for (int i = 0; i < nPl_; i++)
-                            for (int u = lmOffp[i]; u < lmOffp[i + 1]; u++) {
-                                const int f = lmCamp[u];
-                                if (f < f0 || f >= f1) continue;
-                                const int at = cur[f - f0]++;
-                                cmLmp[at] = i; cmUp[at] = u;
-                            }
-                    });
-                }
-            }
-            hs_lap(5);
-            // the pairs of every camera and their entry counts: chunks of cameras, each into lists of its own, joined in camera order
-            constexpr int kChunkCams = 4;
-            const int nChunks = (nFa + kChunkCams - 1) / kChunkCams;
-            static thread_local std::vector<std::vector<int>> chB, chCnt;
-            chB.resize(nChunks); chCnt.resize(nChunks);
-            cmPairStart.assign((size_t)nFa + 1, 0);
-            {
-                int* const pairsOfCam = cmPairStart.data() + 1;
-                const int* const lmOffp = lmOff.data(); const int* const lmCamp = lmCam.data(); const int* const cmOffp = cmOff.data();
-                const int* const cmLmp = cmLm.data(); const int* const cmUp = cmU.data();
-                std::vector<int>* const chBp = chB.data(); std::vector<int>* const chCntp = chCnt.data();
-                crew_for(lpEntries, nChunks, [=](int q) {
-                    // (the per-thread scratch through plain pointers: in a shared library every use of a thread_local object is a call into the TLS runtime,
-                    //  and the two loops below made one per observer -- the pass took 0.57 ms where the walk itself needs 0.15)
-                    static thread_local std::vector<int> cnt2v, touchedv;
-                    cnt2v.assign((size_t)nFa, 0); touchedv.resize((size_t)nFa);
-                    int* const cnt2 = cnt2v.data(); int* const touched = touchedv.data();
-                    std::vector<int>& oB = chBp[q]; std::vector<int>& oC = chCntp[q];
-                    oB.clear(); oC.clear();
-                    for (int i1 = q * kChunkCams; i1 < std::min(nFa, (q + 1) * kChunkCams); i1++) {
-                        int nt = 0;
-                        for (int k = cmOffp[i1]; k < cmOffp[i1 + 1]; k++)
-                            for (int u = cmUp[k], ue = lmOffp[cmLmp[k] + 1]; u < ue; u++) { const int i2 = lmCamp[u]; if (cnt2[i2]++ == 0) touched[nt++] = i2; }
-                        std::sort(touched, touched + nt);
-                        for (int k = 0; k < nt; k++) { const int i2 = touched[k]; oB.push_back(i2); oC.push_back(cnt2[i2]); cnt2[i2] = 0; }
-                        pairsOfCam[i1] = nt;
-                    }
-                });
-            }
-            hs_lap(6);
-            prA.clear(); prB.clear(); prStart.clear();
-            int run = 0;
-            for (int q = 0; q < nChunks; q++) {
-                size_t at = 0;
-                for (int i1 = q * kChunkCams; i1 < std::min(nFa, (q + 1) * kChunkCams); i1++) {
-                    const int np = cmPairStart[i1 + 1];
-                    for (int k = 0; k < np; k++, at++) { prA.push_back(i1); prB.push_back(chB[q][at]); prStart.push_back(run); run += chCnt[q][at]; }
-                    cmPairStart[i1 + 1] = (int)prA.size();
-                }
-            }
-            prStart.push_back(run);
-            EAO_REQUIRE((size_t)run == lpEntries, "internal: covisibility count mismatch (%d entries counted, %zu expected)", run, lpEntries);
-            lpPairsMax = prA.size();
-            hs_lap(7);
-            {
-                const int forceP = getenv("EAO_BA_ND") ? atoi(getenv("EAO_BA_ND")) : 0;      // (read per call: A/B runs and the tests -- 1 = natural order, p > 1 = p segments)
-                const uint64_t key = gba_pattern_hash(nFa, prA, prB) ^ ((uint64_t)(unsigned)forceP << 48);
-                if (!plan.valid || plan.key != key || plan.nFa != nFa) {
-                    gba_build_plan(nFa, prA, prB, forceP, plan);
-                    plan.key = key; plan.valid = true;
-                    if (hostStamps) fprintf(stderr, "[eao map-scale plan] %d free keyframes (bandwidth %d%s): %d segment(s), %d separator keyframes, %d rows in %d tiles; %zu factorisation launches "
-                                            "(natural order: %d), %zu back-substitution launches, %zu work records\n", nFa, plan.bandwidth, plan.rcm ? ", reverse Cuthill-McKee line" : "", plan.P,
-                                            plan.nSep, plan.N, plan.bigTiles, plan.launches.size(), plan.chainNatural, plan.sbLaunches.size(), plan.work.size() / 2);
-                }
-            }
-            bigT = plan.T; bigTiles = plan.bigTiles;
-            EAO_REQUIRE(plan.work.size() < ((size_t)1 << 28), "tile structure too large (%zu work records)", plan.work.size() / 2);
-        }
-        hs_lap(0);
+        EAO_REQUIRE(plan.work.size() < ((size_t)1 << 28), "tile structure too large (%zu work records)", plan.work.size() / 2);
+        return EAO_OK;
+    }
+
+    void start_record() {      // the window record's scalars
+        std::memset(&D, 0, sizeof(D));
+        D.nCams = nC; D.nPts = nP; D.nEdges = E;
+        D.cam.fx = p->fx; D.cam.fy = p->fy; D.cam.cx = p->cx; D.cam.cy = p->cy; D.cam.bf = p->bf; D.cam.bf_f = p->bf;
+        D.cam.deltaMono = (float)std::sqrt(mode == 1 ? refc::GBA_HUBER2_MONO : refc::LBA_HUBER2_MONO);
+        D.cam.deltaStereo = (float)std::sqrt(mode == 1 ? refc::GBA_HUBER2_STEREO : refc::LBA_HUBER2_STEREO);
+        D.nPtsOnly = nPo; D.nEdgesPt = Ept;
+        D.deltaPlane = (float)std::sqrt(refc::PLANE_CHI2); D.infoAngle = refc::PLANE_ANGLE_INFO / (1.0 * 1.0); D.infoDist = refc::PLANE_DIST_INFO_ROOT * refc::PLANE_DIST_INFO_ROOT;   // src/Optimizer.cc:203-208
+        D.status = c->status;
+    }
+
+    // Sizes the context's arena for this problem and cuts it up: the size formula and the carve it must cover, one after the other (a.off <= a.cap is checked at
+    // the end).  First the uploaded part (problem, initial state, adjacency, zeroed control block, the window record itself: into `k`, mirrored in pinned host
+    // memory), then the device-only part (straight into the window record D).
+    eao_status carve_arena(const SetupScratch& S, Carve& k) {
+        LMContext& c = *this->c;
+        const GbaPlan& plan = c.plan;
+        const size_t lpEntries = bigPath ? S.lpEntries : 0, lpPairsMax = bigPath ? S.prA.size() : 0;
+        const int bigT = bigPath ? plan.T : 0, bigTiles = bigPath ? plan.bigTiles : 0;
+        eao_status st;
         size_t need = 0;
         need += (size_t)E * (3 * 4 + 4 + 4 + 4 + 1 + 4 + 4 + 4 + 1 + 24 + 18 * 8);
         need += (size_t)nP * (3 + 3 + 9 + 3 + 3 + 1 + 1) * 8 + (size_t)nP * 16 + (bigPath ? 64 : (size_t)nP * nC * 4);
@@ -428,7 +171,7 @@ struct BAJob {
         need += 128 * 256 + (size_t)nPl * 4 * 8 * 2 + (size_t)Epl * 4 * 8 + 2 * sizeof(BADev) + (size_t)nP + 1024;     // (+ k_ba_backsub's workgroup sums)
         if (bigPath) {
             need += (2 * ((size_t)bigTiles << 12) + 2 * (size_t)plan.N * kBigNB) * 8;
-            need += (3 * lpEntries + 5 * lpPairsMax + 72 + 4 * (lmCam.size() + 2) + (size_t)nP + nC + 16) * 4 + (plan.tileMap.size() + plan.rowOf.size() + plan.rowCam.size() + plan.diagList.size() + 8) * 4 + (plan.work.size() + plan.sb.size()) * sizeof(int4) + 4096;
+            need += (3 * lpEntries + 5 * lpPairsMax + 72 + 4 * (S.lmCam.size() + 2) + (size_t)nP + nC + 16) * 4 + (plan.tileMap.size() + plan.rowOf.size() + plan.rowCam.size() + plan.diagList.size() + 8) * 4 + (plan.work.size() + plan.sb.size()) * sizeof(int4) + 4096;
         } else {
             need += 2 * ((size_t)(nC * 6 + 6) * (nC * 6 + 34) + 8) * 8;
             need += (size_t)nC * (nC + 1) / 2 * ((size_t)nP + 64) * (4 + 16);   // landmark lists / item records of the camera pairs
@@ -440,46 +183,41 @@ struct BAJob {
             fprintf(stderr, "[eao map-scale arena] %.1f MB for this problem (%d x %d tile grid, %d live tiles = %.1f MB in the two pools, %zu work records), context arena %.1f MB\n",
                     need / 1e6, bigT, bigT, bigTiles, 2.0 * bigTiles * 32768 / 1e6, plan.work.size() / 2, c.bytes.n / 1e6);
         Arena a{c.bytes.p, c.bytes.n};
-        std::memset(&D, 0, sizeof(D));
-        D.nCams = nC; D.nPts = nP; D.nEdges = E;
-        D.cam.fx = p->fx; D.cam.fy = p->fy; D.cam.cx = p->cx; D.cam.cy = p->cy; D.cam.bf = p->bf; D.cam.bf_f = p->bf;
-        D.cam.deltaMono = (float)std::sqrt(mode == 1 ? refc::GBA_HUBER2_MONO : refc::LBA_HUBER2_MONO);
-        D.cam.deltaStereo = (float)std::sqrt(mode == 1 ? refc::GBA_HUBER2_STEREO : refc::LBA_HUBER2_STEREO);
-        // ---- the uploaded part of the arena (problem, initial state, adjacency, zeroed control block, the window record
-        //      itself) is mirrored in pinned host memory: filled in place, sent with two copies
-        const size_t off0 = a.off;
-        float* dobs = a.take<float>((size_t)E * 3); float* dinfo = a.take<float>(E);
-        int* decam = a.take<int>(E); int* dept = a.take<int>(E);
-        SE3* dcams = a.take<SE3>(nC);
-        double* dpts = a.take<double>((size_t)nP * 3);
-        unsigned char* dflag = a.take<unsigned char>(E);
-        int* dcamIdx = a.take<int>(nC); int* dptIdx = a.take<int>(nP); int* dactCam = a.take<int>(nC); int* dactPt = a.take<int>(nP);
-        int* dptStart = a.take<int>(nP + 1); int* dptEdges = a.take<int>(E); int* dcamStart = a.take<int>(nC + 1); int* dcamEdges = a.take<int>(E);
-        int* dctl = a.take<int>(16);   // two control blocks: see BADecision
-        int* dlpStart = a.take<int>(bigPath ? lpPairsMax + 1 : 1);
-        int* dlpPair = a.take<int>(bigPath ? 2 * lpPairsMax : 1);
-        int* dlpOrder = a.take<int>(bigPath ? 2 * lpPairsMax + 64 : 1);
-        const size_t nObs = bigPath ? lmCam.size() : 1;      // (observer list entries + 1)
-        int* dlmOff = a.take<int>(bigPath ? (size_t)nP + 1 : 1); int* dlmCam = a.take<int>(nObs); int* dlmEdge = a.take<int>(nObs);
-        int* dcmOff = a.take<int>(bigPath ? cmOff.size() : 1); int* dcmLm = a.take<int>(nObs); int* dcmU = a.take<int>(nObs);
-        int* dbigTile = a.take<int>(bigPath ? plan.tileMap.size() : 1);
-        int4* dbigWork = a.take<int4>(bigPath ? std::max<size_t>(plan.work.size(), 1) : 1);
-        int* dbigRow = a.take<int>(bigPath ? std::max<size_t>(plan.rowOf.size(), 1) : 1);
-        int* dbigRowCam = a.take<int>(bigPath ? std::max<size_t>(plan.rowCam.size(), 1) : 1);
-        int4* dbigSB = a.take<int4>(bigPath ? std::max<size_t>(plan.sb.size(), 1) : 1);
-        int* dbigDiagList = a.take<int>(bigPath ? std::max<size_t>(plan.diagList.size(), 1) : 1);
-        double* dpl0 = a.take<double>((size_t)nPl * 4 + 1);
-        double* dpmeas = a.take<double>((size_t)Epl * 4 + 1);
+        // ---- the uploaded part
+        k.base = a.base; k.off0 = a.off;
+        k.obs = a.take<float>((size_t)E * 3); k.info = a.take<float>(E);
+        k.ecam = a.take<int>(E); k.ept = a.take<int>(E);
+        k.cams = a.take<SE3>(nC);
+        k.pts = a.take<double>((size_t)nP * 3);
+        k.flag = a.take<unsigned char>(E);
+        k.camIdx = a.take<int>(nC); k.ptIdx = a.take<int>(nP); k.actCam = a.take<int>(nC); k.actPt = a.take<int>(nP);
+        k.ptStart = a.take<int>(nP + 1); k.ptEdges = a.take<int>(E); k.camStart = a.take<int>(nC + 1); k.camEdges = a.take<int>(E);
+        k.ctl = a.take<int>(16);
+        k.lpOrderCap = 2 * lpPairsMax + 64;
+        k.lpStart = a.take<int>(bigPath ? lpPairsMax + 1 : 1);
+        k.lpPair = a.take<int>(bigPath ? 2 * lpPairsMax : 1);
+        k.lpOrder = a.take<int>(bigPath ? k.lpOrderCap : 1);
+        k.nObs = bigPath ? S.lmCam.size() : 1;
+        k.lmOff = a.take<int>(bigPath ? (size_t)nP + 1 : 1); k.lmCam = a.take<int>(k.nObs); k.lmEdge = a.take<int>(k.nObs);
+        k.cmOff = a.take<int>(bigPath ? S.cmOff.size() : 1); k.cmLm = a.take<int>(k.nObs); k.cmU = a.take<int>(k.nObs);
+        k.bigTile = a.take<int>(bigPath ? plan.tileMap.size() : 1);
+        k.bigWork = a.take<int4>(bigPath ? std::max<size_t>(plan.work.size(), 1) : 1);
+        k.bigRow = a.take<int>(bigPath ? std::max<size_t>(plan.rowOf.size(), 1) : 1);
+        k.bigRowCam = a.take<int>(bigPath ? std::max<size_t>(plan.rowCam.size(), 1) : 1);
+        k.bigSB = a.take<int4>(bigPath ? std::max<size_t>(plan.sb.size(), 1) : 1);
+        k.bigDiagList = a.take<int>(bigPath ? std::max<size_t>(plan.diagList.size(), 1) : 1);
+        k.pl0 = a.take<double>((size_t)nPl * 4 + 1);
+        k.pmeas = a.take<double>((size_t)Epl * 4 + 1);
         dW = a.take<BADev>(2);
-        const size_t off1 = eao::align256(a.off);
+        k.off1 = eao::align256(a.off);
         // ---- device-only part
-        int* dtable = bigPath ? nullptr : a.take<int>((size_t)nP * nC);      // (the map-scale path finds a landmark's edges in its pair lists)
-        int* dlpPts = a.take<int>(bigPath ? lpEntries : 1);                  // (filled by k_bal_pair_fill)
-        int* dlpE1 = a.take<int>(bigPath ? lpEntries : 1);
-        int* dlpE2 = a.take<int>(bigPath ? lpEntries : 1);
+        D.table = bigPath ? nullptr : a.take<int>((size_t)nP * nC);      // (the map-scale path finds a landmark's edges in its pair lists)
+        D.lpPts = a.take<int>(bigPath ? lpEntries : 1);                  // (filled by k_bal_pair_fill)
+        D.lpE1 = a.take<int>(bigPath ? lpEntries : 1);
+        D.lpE2 = a.take<int>(bigPath ? lpEntries : 1);
         D.slot = a.take<int4>((size_t)std::max(nP, 1) * 8);
         D.camEdgeL = a.take<int>(E);
-        const bool pairPath = !bigPath && nFreeIn > 0 && nFreeIn <= kTileMaxFree;
+        const bool pairPath = pair_path();
         const int nPairsMax = nFreeIn * (nFreeIn + 1) / 2;
         D.pairCnt = a.take<int>(bigPath ? 1 : std::max(nPairsMax, 1));
         D.pairPts = a.take<int>(pairPath ? (size_t)nPairsMax * std::max(nP, 1) : 1);
@@ -488,11 +226,9 @@ struct BAJob {
         D.pairItems = a.take<int4>(wmode ? (size_t)nPairsMax * std::max(nP, 1) : 1);
         D.Tl = a.take<double>((size_t)std::max(nP, 1) * 6); D.ul = a.take<double>(((size_t)std::max(nP, 1) + 1) * 3);
         D.cls = a.take<unsigned char>(E);
-        SE3* dcamsT = a.take<SE3>(nC);
-        double* dptsT = a.take<double>((size_t)nP * 3);
-        D.plBuf[0] = dpl0; D.plBuf[1] = a.take<double>((size_t)nPl * 4 + 1); D.pmeas = dpmeas;
-        D.nPtsOnly = nPo; D.nEdgesPt = Ept;
-        D.deltaPlane = (float)std::sqrt(refc::PLANE_CHI2); D.infoAngle = refc::PLANE_ANGLE_INFO / (1.0 * 1.0); D.infoDist = refc::PLANE_DIST_INFO_ROOT * refc::PLANE_DIST_INFO_ROOT;   // src/Optimizer.cc:203-208
+        D.camsBuf[0] = k.cams; D.camsBuf[1] = a.take<SE3>(nC);
+        D.ptsBuf[0] = k.pts; D.ptsBuf[1] = a.take<double>((size_t)nP * 3);
+        D.plBuf[0] = k.pl0; D.plBuf[1] = a.take<double>((size_t)nPl * 4 + 1); D.pmeas = k.pmeas;
         D.err = a.take<double>((size_t)E * 3);
         D.Hpp = a.take<double>((size_t)nC * 36); D.bp = a.take<double>((size_t)nC * 6);
         D.Hll = a.take<double>((size_t)nP * 9); D.bl = a.take<double>((size_t)nP * 3);
@@ -500,13 +236,13 @@ struct BAJob {
         D.sys = a.take<double>(bigPath ? 8 : std::max((size_t)(nFreeIn * 6) * (nFreeIn * 6 + 1), (size_t)tile_geom(std::max(nFreeIn, 1)).nTiles * 256) + 8);
         D.big = a.take<double>(bigPath ? ((size_t)bigTiles << 12) : 8);
         D.bigL = a.take<double>(bigPath ? ((size_t)bigTiles << 12) : 8);
-        D.bigTile = dbigTile; D.bigT = bigT; D.bigTiles = bigTiles; D.bigWork = dbigWork; D.bigDense = bigPath && bigTiles == bigT * (bigT + 1) / 2 ? 1 : 0;
+        D.bigTile = k.bigTile; D.bigT = bigT; D.bigTiles = bigTiles; D.bigWork = k.bigWork; D.bigDense = bigPath && bigTiles == bigT * (bigT + 1) / 2 ? 1 : 0;
         D.bigDiag = a.take<double>(bigPath ? (size_t)plan.N * kBigNB : 8);
         D.bigLinv = a.take<double>(bigPath ? (size_t)plan.N * kBigNB : 8);
-        D.bigN = bigPath ? plan.N : 0; D.bigRow = dbigRow; D.bigRowCam = dbigRowCam; D.bigSB = dbigSB; D.bigDiagList = dbigDiagList;
+        D.bigN = bigPath ? plan.N : 0; D.bigRow = k.bigRow; D.bigRowCam = k.bigRowCam; D.bigSB = k.bigSB; D.bigDiagList = k.bigDiagList;
         D.bigFail = a.take<int>(4);
-        D.lpStart = dlpStart; D.lpPair = dlpPair; D.lpOrder = dlpOrder; D.lpPts = dlpPts; D.lpE1 = dlpE1; D.lpE2 = dlpE2;
-        D.lmOff = dlmOff; D.lmCam = dlmCam; D.lmEdge = dlmEdge; D.cmOff = dcmOff; D.cmLm = dcmLm; D.cmU = dcmU;
+        D.lpStart = k.lpStart; D.lpPair = k.lpPair; D.lpOrder = k.lpOrder;
+        D.lmOff = k.lmOff; D.lmCam = k.lmCam; D.lmEdge = k.lmEdge; D.cmOff = k.cmOff; D.cmLm = k.cmLm; D.cmU = k.cmU;
         D.xp = a.take<double>((size_t)nC * 6); D.xl = a.take<double>((size_t)nP * 3);
         D.partChi = a.take<double>(nP); D.partScale = a.take<double>(nP);
         D.lm0 = a.take<double>(16);
@@ -516,13 +252,17 @@ struct BAJob {
         long long* ddbg = a.take<long long>(32);
         D.dbg = getenv("EAO_DEBUG_STAMPS") ? ddbg : nullptr;
         EAO_REQUIRE(a.off <= a.cap, "internal: arena overflow");
-        D.obs = dobs; D.info = dinfo; D.ecam = decam; D.ept = dept; D.eflag = dflag;
-        D.camIdx = dcamIdx; D.ptIdx = dptIdx; D.actCam = dactCam; D.actPt = dactPt;
-        D.ptStart = dptStart; D.ptEdges = dptEdges; D.camStart = dcamStart; D.camEdges = dcamEdges; D.table = dtable;
-        D.camsBuf[0] = dcams; D.camsBuf[1] = dcamsT; D.ptsBuf[0] = dpts; D.ptsBuf[1] = dptsT;
-        D.ctl0 = dctl; D.ctl = dctl; D.lm = D.lm0;
-        D.status = c.status;
-        if ((st = c.pin.reserve(off1))) return st;
+        D.obs = k.obs; D.info = k.info; D.ecam = k.ecam; D.ept = k.ept; D.eflag = k.flag;
+        D.camIdx = k.camIdx; D.ptIdx = k.ptIdx; D.actCam = k.actCam; D.actPt = k.actPt;
+        D.ptStart = k.ptStart; D.ptEdges = k.ptEdges; D.camStart = k.camStart; D.camEdges = k.camEdges;
+        D.ctl0 = k.ctl; D.ctl = k.ctl; D.lm = D.lm0;
+        if ((st = c.pin.reserve(k.off1))) return st;
+        k.pin = c.pin.p;
+        return EAO_OK;
+    }
+    eao_status reserve_results() {      // pinned results, written by k_ba_finish
+        LMContext& c = *this->c;
+        eao_status st;
         const size_t outBytes = (size_t)nC * sizeof(SE3) + (size_t)nP * 24 + (size_t)nPl * 32 + (((size_t)E + 15) & ~(size_t)15) + 64;
         if ((st = c.pinOut.reserve(outBytes))) return st;
         outCams = (SE3*)c.pinOut.p;
@@ -530,184 +270,91 @@ struct BAJob {
         outPlanes = outPts + (size_t)nP * 3;
         outCls = (unsigned char*)(outPlanes + (size_t)nPl * 4);
         D.outCams = outCams; D.outPts = outPts; D.outPlanes = outPlanes; D.outCls = outCls;
-        auto hostp = [&](const void* dev) { return c.pin.p + ((const unsigned char*)dev - a.base); };
-        size_t offSplit = off0;
+        return EAO_OK;
+    }
+
+    // the problem itself (observations, indices, initial state, flags, zeroed control block) into the pinned mirror
+    void pack_problem(const EdgeView& v, const Carve& k, Workers& crew) {
+        unsigned char* const hf = k.host(k.flag);      // edge flags: bit0 stereo, bit2 robust kernel present (bit1 = level 1 is only ever set on the device)
+        double* const hp = k.host(k.pts);
         {
-            unsigned char* const hf = (unsigned char*)hostp(dflag);      // edge flags: bit0 stereo, bit2 robust kernel present (bit1 = level 1 is only ever set on the device)
-            double* const hp = (double*)hostp(dpts);
-            {
-                unsigned char* const hobs = hostp(dobs); unsigned char* const hinfo = hostp(dinfo); unsigned char* const hecam = hostp(decam); unsigned char* const hept = hostp(dept);
-                const eao_ba_problem* const pp = p;
-                const int Ept_ = Ept, nPo_ = nPo; const unsigned char rb = robust ? 4 : 0;
-                const int nPack = session.open ? 16 : 1;
-                crew_for(0, nPack, [=](int q) {
-                    const size_t e0 = (size_t)Ept_ * q / nPack, e1 = (size_t)Ept_ * (q + 1) / nPack;
-                    std::memcpy(hobs + e0 * 12, pp->edge_obs + e0 * 3, (e1 - e0) * 12);
-                    std::memcpy(hinfo + e0 * 4, pp->edge_inv_sigma2 + e0, (e1 - e0) * 4);
-                    std::memcpy(hecam + e0 * 4, pp->edge_cam + e0, (e1 - e0) * 4);
-                    std::memcpy(hept + e0 * 4, pp->edge_point + e0, (e1 - e0) * 4);
-                    for (size_t e = e0; e < e1; e++) hf[e] = (unsigned char)((!(pp->edge_obs[3 * e + 2] < 0) ? 1 : 0) | rb);
-                    for (size_t i = (size_t)nPo_ * 3 * q / nPack, i1 = (size_t)nPo_ * 3 * (q + 1) / nPack; i < i1; i++) hp[i] = pp->points[i];
-                });
-            }
-            if (hasPl) {
-                std::memset(hostp(dobs) + (size_t)Ept * 12, 0, (size_t)Epl * 12);
-                std::memset(hostp(dinfo) + (size_t)Ept * 4, 0, (size_t)Epl * 4);
-                int* hc2 = (int*)hostp(decam); int* hp2 = (int*)hostp(dept);
-                for (int e = Ept; e < E; e++) { hc2[e] = edge_cam(e); hp2[e] = edge_lm(e); }
-                double* hpl = (double*)hostp(dpl0); double* hpm = (double*)hostp(dpmeas);
-                for (int i = 0; i < nPl; i++) plane_from_f32(pl->plane_world + 4 * i, hpl + 4 * i);          // Converter::toPlane3D (:217)
-                for (int e = 0; e < Epl; e++) plane_from_f32(pl->pedge_obs + 4 * e, hpm + 4 * e);           // (:239)
-            }
-            SE3* hc = (SE3*)hostp(dcams);
-            for (int i = 0; i < nC; i++) hc[i] = se3_from_Tcw_f32(p->cam_Tcw + 16 * i);
-            for (size_t i = (size_t)nPo * 3; i < (size_t)nP * 3; i++) hp[i] = 0;
-            for (int e = Ept; e < E; e++) hf[e] = 8 | 4;      // EdgePlane: always a Huber kernel (:246-248)
-            std::memset(hostp(dctl), 0, 16 * sizeof(int));
-            // The problem itself (observations, indices, initial state, flags) is on its way to the device while the host builds
-            // the active structure below; the structure follows in a second copy.
-            offSplit = (size_t)((unsigned char*)dcamIdx - a.base) & ~(size_t)255;
-            hs_lap(1);
-            if (!deferUpload) EAO_HIP(hipMemcpyAsync(a.base + off0, c.pin.p + off0, offSplit - off0, hipMemcpyHostToDevice, s));
-            // ---- active structure: SparseOptimizer::initializeOptimization(level 0) + buildIndexMapping
-            int* camIdx = (int*)hostp(dcamIdx); int* ptIdx = (int*)hostp(dptIdx);
-            int* actCam = (int*)hostp(dactCam); int* actPt = (int*)hostp(dactPt);
-            int* ptStart = (int*)hostp(dptStart); int* ptEdges = (int*)hostp(dptEdges);
-            int* camStart = (int*)hostp(dcamStart); int* camEdges = (int*)hostp(dcamEdges);
-            // (camCnt / ptCnt: counted with the validation pass above)
-            int nF = 0, nL = 0;
-            for (int i = 0; i < nC; i++) { camIdx[i] = -1; if (camCnt[i] && !p->cam_fixed[i]) { actCam[nF] = i; camIdx[i] = nF++; } }
-            ptStart[0] = 0;
-            for (int i = 0; i < nP; i++) { ptIdx[i] = -1; if (ptCnt[i]) { actPt[nL] = i; ptIdx[i] = nL; ptStart[nL + 1] = ptStart[nL] + ptCnt[i]; nL++; } }
-            camStart[0] = 0;
-            for (int i = 0; i < nF; i++) camStart[i + 1] = camStart[i] + camCnt[actCam[i]];
-            for (int i = 0; i < nL; i++) ptCnt[actPt[i]] = ptStart[i];         // counters become fill cursors
-            for (int i = 0; i < nF; i++) camCnt[actCam[i]] = camStart[i];
-            bool dupChecked = false;
-            if (countedInChunks && bigPath) {      // (sessions: the duplicate test rode along with the validation pass, a camera's edges came with its landmark list -- cmE)
-                EAO_REQUIRE((int)cmE.size() == camStart[nF], "internal: camera edge lists built for another set of free keyframes");
-                const int* const cmEp = cmE.data();
-                const int E_ = E, tot = camStart[nF];
-                crew_for((size_t)E, 16, [=](int q) {
-                    for (int e = (int)((long long)E_ * q / 16), e1 = (int)((long long)E_ * (q + 1) / 16); e < e1; e++) ptEdges[e] = e;
-                    const int k0 = (int)((long long)tot * q / 16), k1 = (int)((long long)tot * (q + 1) / 16);
-                    std::memcpy(camEdges + k0, cmEp + k0, (size_t)(k1 - k0) * sizeof(int));
-                });
-                dupChecked = true;
-            } else if (edgesByLandmark) {      // (the landmarks' edge lists, concatenated in landmark order, ARE the edge list; the one-edge-per-pair test rides along)
-                static thread_local std::vector<int> camLast;
-                camLast.assign((size_t)nC, -1);
-                for (int e = 0; e < E; e++) {
-                    const int cam = edge_cam(e), lmk = edge_lm(e);
-                    ptEdges[e] = e;
-                    if (camIdx[cam] >= 0) camEdges[camCnt[cam]++] = e;
-                    if (camLast[cam] == lmk) { eao::set_error("two edges join camera %d and point %d", cam, lmk); return EAO_ERR_INVALID; }
-                    camLast[cam] = lmk;
-                }
-                dupChecked = true;
-            } else {
-                for (int e = 0; e < E; e++) {
-                    const int cam = edge_cam(e);
-                    ptEdges[ptCnt[edge_lm(e)]++] = e;
-                    if (camIdx[cam] >= 0) camEdges[camCnt[cam]++] = e;
-                }
-            }
-            // one edge per (camera, point) pair: the device's edge table has one slot per pair
-            if (!dupChecked) {
-                for (int i = 0; i < nC; i++) camCnt[i] = -1;                        // now: last point seen with this camera
-                for (int l = 0; l < nL; l++)
-                    for (int k = ptStart[l]; k < ptStart[l + 1]; k++) {
-                        const int cam = edge_cam(ptEdges[k]);
-                        if (camCnt[cam] == l) { eao::set_error("two edges join camera %d and point %d", cam, actPt[l]); return EAO_ERR_INVALID; }
-                        camCnt[cam] = l;
-                    }
-            }
-            D.nFree = nF; D.nL = nL;
-            hs_lap(2);
-            if (bigPath && nF > 0) {
-                // covisibility CSR: for every camera pair (i1 <= i2) sharing a landmark, the landmark blocks in ascending order
-                // (counting sort over the landmarks' observer lists; the diagonal pairs carry each camera's own landmarks)
-                int* lpStart = (int*)hostp(dlpStart); int* lpPair = (int*)hostp(dlpPair);
-                EAO_REQUIRE(plan.valid && plan.nFa == nF && plan.T == bigT, "internal: tile structure built for another system size");
-                std::memcpy(hostp(dbigTile), plan.tileMap.data(), plan.tileMap.size() * sizeof(int));
-                if (!plan.work.empty()) std::memcpy(hostp(dbigWork), plan.work.data(), plan.work.size() * sizeof(int4));
-                std::memcpy(hostp(dbigRow), plan.rowOf.data(), plan.rowOf.size() * sizeof(int));
-                std::memcpy(hostp(dbigRowCam), plan.rowCam.data(), plan.rowCam.size() * sizeof(int));
-                if (!plan.sb.empty()) std::memcpy(hostp(dbigSB), plan.sb.data(), plan.sb.size() * sizeof(int4));
-                if (!plan.diagList.empty()) std::memcpy(hostp(dbigDiagList), plan.diagList.data(), plan.diagList.size() * sizeof(int));
-                // (the pairs, their entry counts and every camera's landmark list were worked out above, before the arena was sized)
-                EAO_REQUIRE((int)cmPairStart.size() == nF + 1, "internal: covisibility structure built for another set of free keyframes");
-                const int nz = (int)prA.size();
-                for (int k = 0; k < nz; k++) { lpPair[2 * k] = prA[k]; lpPair[2 * k + 1] = prB[k]; }
-                std::memcpy(lpStart, prStart.data(), ((size_t)nz + 1) * sizeof(int));
-                // the observer lists travel instead of the pairs' entries (k_bal_pair_fill writes those on the device: see there)
-                EAO_REQUIRE((int)lmOff.size() == nP + 1 && (int)cmOff.size() == nF + 1 && lmCam.size() == nObs && cmLm.size() + 1 == nObs, "internal: observer lists built for another problem");
-                {
-                    int* const hLmOff = (int*)hostp(dlmOff); int* const hLmCam = (int*)hostp(dlmCam); int* const hLmEdge = (int*)hostp(dlmEdge);
-                    int* const hCmOff = (int*)hostp(dcmOff); int* const hCmLm = (int*)hostp(dcmLm); int* const hCmU = (int*)hostp(dcmU);
-                    const int* const lmOffp = lmOff.data(); const int* const lmCamp = lmCam.data(); const int* const lmEdgep = lmEdge.data();
-                    const int* const cmOffp = cmOff.data(); const int* const cmLmp = cmLm.data(); const int* const cmUp = cmU.data();
-                    const size_t nO = nObs - 1, nPp = (size_t)nP + 1, nFp = (size_t)nF + 1;
-                    const int nCopy = session.open ? 12 : 1;
-                    crew_for(0, nCopy, [=](int q) {
-                        auto part = [&](int* dst, const int* src, size_t n) { const size_t i0 = n * q / nCopy, i1 = n * (q + 1) / nCopy; std::memcpy(dst + i0, src + i0, (i1 - i0) * sizeof(int)); };
-                        part(hLmOff, lmOffp, nPp); part(hLmCam, lmCamp, nO); part(hLmEdge, lmEdgep, nO);
-                        part(hCmOff, cmOffp, nFp); part(hCmLm, cmLmp, nO); part(hCmU, cmUp, nO);
-                    });
-                }
-                D.nPairsNZ = nz;
-                nPairsLong = 0;
-                {   // launch order: long pairs first; and inside each class the pairs are dealt to the eight XCDs by camera range -- workgroup b runs on XCD b % 8, a pair
-                    // list is sorted by its first camera, and the pairs of neighbouring cameras share their landmarks: dealt round-robin, every landmark's blocks were
-                    // pulled into all eight L2s (the assembly re-reads each block once per pair of its landmark: 570 MB per launch on the banded 1000-keyframe map);
-                    // with one contiguous camera range per XCD (equal shares of the entries) they stay in one or two.  A slot of -1 is an idle workgroup.
-                    int* lpOrder = (int*)hostp(dlpOrder);
-                    const int kLong = getenv("EAO_BA_PAIR_LONG") ? atoi(getenv("EAO_BA_PAIR_LONG")) : kBigPairLong;      // (tests: the four-wave kernel on small maps)
-                    static thread_local std::vector<int> cls, grp[8];
-                    size_t at = 0;
-                    const size_t cap = 2 * (size_t)lpPairsMax + 64;
-                    bool fits = true;
-                    auto deal = [&](bool longOnes) -> int {
-                        cls.clear();
-                        long long tot = 0;
-                        for (int k = 0; k < nz; k++) if ((lpStart[k + 1] - lpStart[k] > kLong) == longOnes) { cls.push_back(k); tot += lpStart[k + 1] - lpStart[k]; }
-                        if (cls.empty()) return 0;
-                        for (auto& g8 : grp) g8.clear();
-                        long long run = 0;
-                        int x = 0, lastCam = -1;
-                        for (int k : cls) {      // a new XCD only at a camera boundary, once the running share of the entries is reached
-                            const int cam = lpPair[2 * k];
-                            if (cam != lastCam && x < 7 && run * 8 >= tot * (x + 1)) x++;
-                            lastCam = cam;
-                            grp[x].push_back(k);
-                            run += lpStart[k + 1] - lpStart[k];
-                        }
-                        size_t len = 0;
-                        for (auto& g8 : grp) len = std::max(len, g8.size());
-                        if (at + 8 * len > cap) { fits = false; return 0; }
-                        for (size_t sl = 0; sl < len; sl++)
-                            for (int q = 0; q < 8; q++) lpOrder[at++] = sl < grp[q].size() ? grp[q][sl] : -1;
-                        return (int)(8 * len);
-                    };
-                    nPairsLong = deal(true);
-                    nPairsSlots = nPairsLong + deal(false);
-                    if (!fits) {      // (one camera holds most of the pairs: plain order)
-                        at = 0;
-                        for (int k = 0; k < nz; k++) if (lpStart[k + 1] - lpStart[k] > kLong) lpOrder[at++] = k;
-                        nPairsLong = (int)at;
-                        for (int k = 0; k < nz; k++) if (lpStart[k + 1] - lpStart[k] <= kLong) lpOrder[at++] = k;
-                        nPairsSlots = (int)at;
-                    }
-                }
-            }
+            unsigned char* const hobs = (unsigned char*)k.host(k.obs); unsigned char* const hinfo = (unsigned char*)k.host(k.info);
+            unsigned char* const hecam = (unsigned char*)k.host(k.ecam); unsigned char* const hept = (unsigned char*)k.host(k.ept);
+            const eao_ba_problem* const pp = p;
+            const int Ept_ = Ept, nPo_ = nPo; const unsigned char rb = robust ? 4 : 0;
+            const int nPack = crew.open ? 16 : 1;
+            crew.pass(0, nPack, [=](int q) {
+                const size_t e0 = (size_t)Ept_ * q / nPack, e1 = (size_t)Ept_ * (q + 1) / nPack;
+                std::memcpy(hobs + e0 * 12, pp->edge_obs + e0 * 3, (e1 - e0) * 12);
+                std::memcpy(hinfo + e0 * 4, pp->edge_inv_sigma2 + e0, (e1 - e0) * 4);
+                std::memcpy(hecam + e0 * 4, pp->edge_cam + e0, (e1 - e0) * 4);
+                std::memcpy(hept + e0 * 4, pp->edge_point + e0, (e1 - e0) * 4);
+                for (size_t e = e0; e < e1; e++) hf[e] = (unsigned char)((!(pp->edge_obs[3 * e + 2] < 0) ? 1 : 0) | rb);
+                for (size_t i = (size_t)nPo_ * 3 * q / nPack, i1 = (size_t)nPo_ * 3 * (q + 1) / nPack; i < i1; i++) hp[i] = pp->points[i];
+            });
         }
-        hs_lap(3);
-        // ---- launch geometry and solver choice of this window
+        if (hasPl) {
+            std::memset(k.host(k.obs) + (size_t)Ept * 3, 0, (size_t)Epl * 12);
+            std::memset(k.host(k.info) + (size_t)Ept, 0, (size_t)Epl * 4);
+            int* hc2 = k.host(k.ecam); int* hp2 = k.host(k.ept);
+            for (int e = Ept; e < E; e++) { hc2[e] = v.cam(e); hp2[e] = v.lm(e); }
+            double* hpl = k.host(k.pl0); double* hpm = k.host(k.pmeas);
+            for (int i = 0; i < nPl; i++) plane_from_f32(pl->plane_world + 4 * i, hpl + 4 * i);          // Converter::toPlane3D (:217)
+            for (int e = 0; e < Epl; e++) plane_from_f32(pl->pedge_obs + 4 * e, hpm + 4 * e);           // (:239)
+        }
+        SE3* hc = k.host(k.cams);
+        for (int i = 0; i < nC; i++) hc[i] = se3_from_Tcw_f32(p->cam_Tcw + 16 * i);
+        for (size_t i = (size_t)nPo * 3; i < (size_t)nP * 3; i++) hp[i] = 0;
+        for (int e = Ept; e < E; e++) hf[e] = 8 | 4;      // EdgePlane: always a Huber kernel (:246-248)
+        std::memset(k.host(k.ctl), 0, 16 * sizeof(int));
+    }
+
+    // map-scale path, into the pinned mirror: the plan's tables, the covisibility CSR (for every camera pair (i1 <= i2) sharing a landmark where its entries start;
+    // the diagonal pairs carry each camera's own landmarks), the observer lists (they travel instead of the pairs' entries: k_bal_pair_fill writes those on the
+    // device) and the launch order of the pair kernels.  All of it was worked out before the arena was sized.
+    eao_status fill_map_scale_mirror(SetupScratch& S, const Carve& k, Workers& crew) {
+        const GbaPlan& plan = c->plan;
+        const int nF = D.nFree;
+        int* lpStart = k.host(k.lpStart); int* lpPair = k.host(k.lpPair);
+        EAO_REQUIRE(plan.valid && plan.nFa == nF && plan.T == D.bigT, "internal: tile structure built for another system size");
+        std::memcpy(k.host(k.bigTile), plan.tileMap.data(), plan.tileMap.size() * sizeof(int));
+        if (!plan.work.empty()) std::memcpy(k.host(k.bigWork), plan.work.data(), plan.work.size() * sizeof(int4));
+        std::memcpy(k.host(k.bigRow), plan.rowOf.data(), plan.rowOf.size() * sizeof(int));
+        std::memcpy(k.host(k.bigRowCam), plan.rowCam.data(), plan.rowCam.size() * sizeof(int));
+        if (!plan.sb.empty()) std::memcpy(k.host(k.bigSB), plan.sb.data(), plan.sb.size() * sizeof(int4));
+        if (!plan.diagList.empty()) std::memcpy(k.host(k.bigDiagList), plan.diagList.data(), plan.diagList.size() * sizeof(int));
+        EAO_REQUIRE((int)S.cmPairStart.size() == nF + 1, "internal: covisibility structure built for another set of free keyframes");
+        const int nz = (int)S.prA.size();
+        for (int i = 0; i < nz; i++) { lpPair[2 * i] = S.prA[i]; lpPair[2 * i + 1] = S.prB[i]; }
+        std::memcpy(lpStart, S.prStart.data(), ((size_t)nz + 1) * sizeof(int));
+        EAO_REQUIRE((int)S.lmOff.size() == nP + 1 && (int)S.cmOff.size() == nF + 1 && S.lmCam.size() == k.nObs && S.cmLm.size() + 1 == k.nObs, "internal: observer lists built for another problem");
+        {
+            int* const hLmOff = k.host(k.lmOff); int* const hLmCam = k.host(k.lmCam); int* const hLmEdge = k.host(k.lmEdge);
+            int* const hCmOff = k.host(k.cmOff); int* const hCmLm = k.host(k.cmLm); int* const hCmU = k.host(k.cmU);
+            const int* const lmOffp = S.lmOff.data(); const int* const lmCamp = S.lmCam.data(); const int* const lmEdgep = S.lmEdge.data();
+            const int* const cmOffp = S.cmOff.data(); const int* const cmLmp = S.cmLm.data(); const int* const cmUp = S.cmU.data();
+            const size_t nO = k.nObs - 1, nPp = (size_t)nP + 1, nFp = (size_t)nF + 1;
+            const int nCopy = crew.open ? 12 : 1;
+            crew.pass(0, nCopy, [=](int q) {
+                auto part = [&](int* dst, const int* src, size_t n) { const size_t i0 = n * q / nCopy, i1 = n * (q + 1) / nCopy; std::memcpy(dst + i0, src + i0, (i1 - i0) * sizeof(int)); };
+                part(hLmOff, lmOffp, nPp); part(hLmCam, lmCamp, nO); part(hLmEdge, lmEdgep, nO);
+                part(hCmOff, cmOffp, nFp); part(hCmLm, cmLmp, nO); part(hCmU, cmUp, nO);
+            });
+        }
+        D.nPairsNZ = nz;
+        const int kLong = getenv("EAO_BA_PAIR_LONG") ? atoi(getenv("EAO_BA_PAIR_LONG")) : kBigPairLong;      // (read per call; tests: the four-wave kernel on small maps)
+        deal_launch_order(lpStart, lpPair, nz, kLong, k.lpOrderCap, S, k.host(k.lpOrder), nPairsLong, nPairsSlots);
+        return EAO_OK;
+    }
+
+    // launch geometry and solver choice of this window; how far optimize() may run ahead of the device
+    void set_launch_geometry() {
+        const GbaPlan& plan = c->plan;
         const int nF = D.nFree, nL = D.nL;
         BADims& d = L.d;
         d = BADims();
         d.nF = nF; d.nL = nL; d.nP = nP; d.nC = nC; d.E = E; d.nPl = nPl; d.hasPl = hasPl; d.bigPath = bigPath;
-        d.usePairs = pairPath && nF > 0 && nL > 0;
+        d.usePairs = pair_path() && nF > 0 && nL > 0;
         d.wmode = D.wmode != 0 && d.usePairs;
         if (!d.wmode) D.wmode = 0;
         // solver choice: register tiles + MFMA up to kTileMaxFree free keyframes, the map-scale path beyond
@@ -716,16 +363,10 @@ struct BAJob {
         d.tiles3 = tile_geom(std::max(nF, 1)).nTiles <= 3 * (kTileThreads / 64);
         d.gB = big_geom(std::max(nF, 1));
         if (bigPath) { d.gB.N = plan.N; d.gB.RP = plan.RP; }
-        d.nPairsNZ = D.nPairsNZ; d.nPairsLong = nPairsLong; d.nPairsSlots = nPairsSlots; d.big = D.big; d.bigTiles = bigTiles;
+        d.nPairsNZ = D.nPairsNZ; d.nPairsLong = nPairsLong; d.nPairsSlots = nPairsSlots; d.big = D.big; d.bigTiles = D.bigTiles;
         d.plan = bigPath ? &plan : nullptr;
         d.bigCtl0 = D.ctl0;
         d.bigArgs = BigStepArgs{D.big, D.bigL, D.bigDiag, D.bigFail, D.bigWork, D.ctl0, D.dbg, d.gB.N, 0, {}};
-        // the window record itself travels with the structure
-        write_records((BADev*)hostp(dW));
-        if (!deferUpload) EAO_HIP(hipMemcpyAsync(a.base + offSplit, c.pin.p + offSplit, off1 - offSplit, hipMemcpyHostToDevice, s));
-        else { upSrc = c.pin.p + off0; upDst = a.base + off0; upBytes = (off1 - off0 + 15) & ~(size_t)15; }
-        L.W = dW; L.nz = 1; L.s = s; L.seq = c.status->seq;
-        c.status->ph[0].touched = c.status->ph[1].touched = 0;
         // map-scale runs (tens of milliseconds) are NOT enqueued speculatively when the caller can abort them: optimize() then
         // submits one LM iteration at a time and reads *stop in between, like g2o's forceStopFlag
         pollStop = bigPath && stop != nullptr;
@@ -734,13 +375,68 @@ struct BAJob {
         // iterations were enqueued up front
         lazy = bigPath && !pollStop;
         chained = E > 0 && (nF + nL) > 0 && !pollStop && !lazy;
-        hs_lap(4);
-        if (hostStamps && bigPath)
-            fprintf(stderr, "[eao map-scale host set-up] observer / camera lists %.3f (counts %.3f, observer scatter %.3f, sort %.3f, camera scatter %.3f), pair counts %.3f, pair list %.3f, order + tiles + symbolic elimination + schedule (GbaPlan; cached per pattern) %.3f ms\n",
-                    hsT[5], hsT[8], hsT[9] - hsT[8], hsT[10] - hsT[9], hsT[5] - hsT[10], hsT[6] - hsT[5], hsT[7] - hsT[6], hsT[0] - hsT[7]);
-        if (hostStamps && bigPath)
-            fprintf(stderr, "[eao map-scale host set-up] covisibility lists + pairs + plan %.3f, arena + problem pack %.3f, active structure %.3f, pair CSR + launch order %.3f, records + upload enqueue %.3f ms (cumulative %.3f)\n",
-                    hsT[0], hsT[1] - hsT[0], hsT[2] - hsT[1], hsT[3] - hsT[2], hsT[4] - hsT[3], hsT[4]);
+    }
+    static void print_laps(const Laps& l) {      // (EAO_DEBUG_STAMPS: host phases of a map-scale set-up, in ms on stderr)
+        const double* const t = l.t;
+        fprintf(stderr, "[eao map-scale host set-up] observer / camera lists %.3f (counts %.3f, observer scatter %.3f, sort %.3f, camera scatter %.3f), pair counts %.3f, pair list %.3f, order + tiles + symbolic elimination + schedule (GbaPlan; cached per pattern) %.3f ms\n",
+                t[5], t[8], t[9] - t[8], t[10] - t[9], t[5] - t[10], t[6] - t[5], t[7] - t[6], t[0] - t[7]);
+        fprintf(stderr, "[eao map-scale host set-up] covisibility lists + pairs + plan %.3f, arena + problem pack %.3f, active structure %.3f, pair CSR + launch order %.3f, records + upload enqueue %.3f ms (cumulative %.3f)\n",
+                t[0], t[1] - t[0], t[2] - t[1], t[3] - t[2], t[4] - t[3], t[4]);
+    }
+
+    eao_status prepare(hipStream_t s, bool deferUpload = false) {
+        eao::Range rg("lm: window set-up + upload");
+        eao_status st;
+        if ((st = check_arguments())) return st;                                                 // 1. arguments
+        LMContext& c = *this->c;
+        tr->clear();
+        static const bool hostStamps = getenv("EAO_DEBUG_STAMPS") != nullptr;      // host phases of the set-up, in ms on stderr (once per process)
+        Laps laps;
+        laps.on = hostStamps;
+        r->iters[0] = r->iters[1] = 0; r->aborted = 0; r->chi2[0] = r->chi2[1] = 0;
+        if (stop && *stop) { abort_shortcut(); return EAO_OK; }                                  // 2. abort shortcut
+        nFreeIn = 0;
+        for (int i = 0; i < nC; i++) nFreeIn += p->cam_fixed[i] ? 0 : 1;
+        EAO_REQUIRE(nFreeIn <= kBigMaxFree, "at most %d free keyframes in this build (got %d)", kBigMaxFree, nFreeIn);
+        // more free keyframes than the single-workgroup solvers take (or EAO_BA_SOLVER=big, the harness's A/B switch): the map-scale path
+        // (measured, LocalBundleAdjustment wall time, tools/dbg_ba_sizes.py: the LDS / global-scratch single-workgroup solver with
+        //  the slab assembly takes 5.8 ms at 31 free keyframes and 29 ms at 64, the map-scale path 3.6 and 6.9 ms -- so everything
+        //  beyond the register-tile solver goes there; that older path was removed in round 5)
+        const char* const solverEnv = getenv("EAO_BA_SOLVER");      // (read per call, like the other switches: a test sets it after the process's first call)
+        bigPath = nFreeIn > kTileMaxFree || (nFreeIn > 0 && solverEnv && !strcmp(solverEnv, "big"));
+        static thread_local SetupScratch t_setup;
+        SetupScratch& S = t_setup;           // (one look-up per call: see SetupScratch)
+        Workers crew(bigPath, Ept);          // (a map-scale set-up is a session of the host crew, open until this function returns)
+        const EdgeView v = edge_view();
+        std::vector<int>& cnt = c.scratch;
+        if (!count_edges(v, crew, S, cnt)) return EAO_ERR_INVALID;                               // 3. validation + counts
+        if (bigPath) {                                                                           // 4. map-scale: covisibility lists, pairs, plan
+            if (!build_observer_lists(v, crew, S, cnt.data(), laps) || !build_pairs(crew, S, laps)) return EAO_ERR_INVALID;
+            if ((st = update_plan(S, hostStamps))) return st;
+        }
+        laps.lap(0);
+        Carve k;                                                                                 // 5. arena
+        start_record();
+        if ((st = carve_arena(S, k)) || (st = reserve_results())) return st;
+        pack_problem(v, k, crew);                                                                // 6. problem pack + first upload
+        // The problem itself is on its way to the device while the host builds the active structure below; the structure follows in a second copy.
+        const size_t offSplit = (size_t)((unsigned char*)k.camIdx - k.base) & ~(size_t)255;
+        laps.lap(1);
+        if (!deferUpload) EAO_HIP(hipMemcpyAsync(k.base + k.off0, k.pin + k.off0, offSplit - k.off0, hipMemcpyHostToDevice, s));
+        ActiveStructure A{k.host(k.camIdx), k.host(k.ptIdx), k.host(k.actCam), k.host(k.actPt), k.host(k.ptStart), k.host(k.ptEdges), k.host(k.camStart), k.host(k.camEdges)};
+        if (!build_active_structure(v, crew, S, bigPath, cnt, A)) return EAO_ERR_INVALID;        // 7. active structure
+        D.nFree = A.nF; D.nL = A.nL;
+        laps.lap(2);
+        if (bigPath && A.nF > 0 && (st = fill_map_scale_mirror(S, k, crew))) return st;          // 8. map-scale: tables, observer lists, launch order
+        laps.lap(3);
+        set_launch_geometry();                                                                   // 9. launch geometry
+        write_records(k.host(dW));                                                               // 10. records (they travel with the structure) + second upload
+        if (!deferUpload) EAO_HIP(hipMemcpyAsync(k.base + offSplit, k.pin + offSplit, k.off1 - offSplit, hipMemcpyHostToDevice, s));
+        else { upSrc = k.pin + k.off0; upDst = k.base + k.off0; upBytes = (k.off1 - k.off0 + 15) & ~(size_t)15; }
+        L.W = dW; L.nz = 1; L.s = s; L.seq = c.status->seq;
+        c.status->ph[0].touched = c.status->ph[1].touched = 0;
+        laps.lap(4);
+        if (hostStamps && bigPath) print_laps(laps);
         return EAO_OK;
     }
 

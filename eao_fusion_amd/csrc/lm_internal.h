@@ -4,7 +4,8 @@
 //   lba.hip      Optimizer::LocalBundleAdjustment (src/Optimizer.cc:675-1138): linearisation, pair assembly, register-tile solver, back substitution, the LM decision,
 //                and BALaunch -- every launch of the engine, the window as grid.z
 //   gba.hip      the map-scale path of Optimizer::BundleAdjustment (src/Optimizer.cc:47-323; more than 30 free keyframes): block-sparse tiles, panel LDL^T, back substitution
-//   lm_host.hip  host side: per-thread contexts, BAJob (validation, arena, active structure, host-stepped trials), the batch call and its crew, the C-ABI entry points
+//   lm_host.hip  host side: per-thread contexts, BAJob (arena, pinned mirror, uploads, host-stepped trials), the batch call and its crew, the C-ABI entry points
+//   ba_setup.h   (included by lm_host.hip only; plain C++17 without HIP) the stages of BAJob::prepare that need no device: validation, covisibility structure, active structure
 // The arithmetic follows the reference's vendored g2o (Thirdparty/g2o/g2o/core/optimization_algorithm_levenberg.cpp:61-189, core/block_solver.hpp:354-604,
 // types/types_six_dof_expmap.cpp, types/se3quat.h); g2o's object graph is not reproduced.  TYPES live in eao::lm (one definition for all units); the device helper
 // FUNCTIONS are internal to each unit (anonymous namespace, all inline) -- the library is built without relocatable device code.

@@ -562,7 +562,8 @@ def test_map_scale_assembly_with_four_wave_pairs(gpu, oracle, kw, monkeypatch):
 def test_map_scale_set_up_on_the_host_crew(gpu, oracle, kw, monkeypatch):
     """Round 5: the covisibility structure of the map-scale path (pairs of every camera, their landmark lists) is counted and filled camera by camera, on the
     process-wide host crew for large maps.  EAO_BA_SETUP_THREADS forces the crew onto a map of test size: the device arrays -- hence the result -- must not depend on
-    how many workers built them, and a map-scale window INSIDE a batch call (whose set-up already runs on a crew thread) builds its structure on that thread alone."""
+    how many workers built them, and a map-scale window INSIDE a batch call (whose set-up already runs on a crew thread) builds its structure on that thread alone.
+    (The stages are csrc/ba_setup.h; tests/cpp/ba_setup_test.cpp compares their serial, crew-run and crew-session forms array by array on the CPU.)"""
     p = synth.synth_ba(**kw)
     monkeypatch.setenv("EAO_BA_SETUP_THREADS", "1")
     one = gpu.Optimizer.BundleAdjustment(p, 6, bRobust=False)
@@ -585,7 +586,8 @@ def test_map_scale_set_up_on_the_host_crew(gpu, oracle, kw, monkeypatch):
 def test_map_scale_set_up_refuses_bad_edge_lists_the_same_way_on_any_crew(gpu, threads, monkeypatch):
     """Round 6: the validation pass of a map-scale call runs in chunks on a crew session.  What it refuses -- an index out of range, two edges between one camera and one
     point -- and the words it refuses them with must not depend on the crew; an edge list that is NOT grouped by landmark falls back to the serial walks and gives the
-    result of its ordered twin (edge order only permutes the sums inside one landmark's and one camera's lists: same bits is not promised, the same LM trace is)."""
+    result of its ordered twin (edge order only permutes the sums inside one landmark's and one camera's lists: same bits is not promised, the same LM trace is).
+    (count_edges of csrc/ba_setup.h; tests/cpp/ba_setup_test.cpp feeds it the same four lists under AddressSanitizer on the CPU.)"""
     monkeypatch.setenv("EAO_BA_SETUP_THREADS", threads)
     p = synth.synth_ba(n_free=45, n_fixed=2, n_points=1800, seed=5750)
     bad = dict(p); ec = p["edge_cam"].copy(); ec[1234] = len(p["poses"]); bad["edge_cam"] = ec
