@@ -146,6 +146,17 @@ class EssentialGraphResult(C.Structure):   # eao_essential_graph_result
                 ("lambda_", C.c_double * 20), ("chi2", C.c_double * 20), ("chi2_initial", C.c_double), ("n_active", C.c_int32)]
 
 
+class VocabularyDesc(C.Structure):   # eao_vocabulary_desc
+    _fields_ = [("n_nodes", C.c_int32), ("parent", C.c_void_p), ("descriptor", C.c_void_p), ("weight", C.c_void_p), ("is_leaf", C.c_void_p),
+                ("weighting", C.c_int32), ("norm", C.c_int32)]
+
+
+class BowResult(C.Structure):   # eao_bow_result
+    _fields_ = [("n_words", C.c_int32), ("word_id", C.c_void_p), ("word_value", C.c_void_p),
+                ("n_fv_nodes", C.c_int32), ("node_id", C.c_void_p), ("node_start", C.c_void_p), ("index", C.c_void_p),
+                ("feat_word", C.c_void_p), ("feat_node", C.c_void_p), ("feat_stopped", C.c_void_p)]
+
+
 # every symbol include/eao_fusion.h declares: (restype, argtypes)
 _P = C.c_void_p
 _I = C.c_int32
@@ -217,6 +228,13 @@ SYMBOLS = {
     "eao_pnp_solver_last_kernel_ms": (_I, [_P]),
     "eao_optimize_essential_graph": (_I, [C.POINTER(EssentialGraphProblem), C.POINTER(EssentialGraphResult)]),
     "eao_essential_graph_plan": (_I, [C.POINTER(EssentialGraphProblem), _P, _P, _P, _I]),
+    "eao_vocabulary_create": (_I, [C.POINTER(VocabularyDesc), C.POINTER(_P)]),
+    "eao_vocabulary_destroy": (None, [_P]),
+    "eao_vocabulary_info": (_I, [_P, C.POINTER(_I), C.POINTER(_I), C.POINTER(_I), C.POINTER(_I)]),
+    "eao_vocabulary_transform": (_I, [_P, _P, _I, _I, C.POINTER(BowResult)]),
+    "eao_vocabulary_transform_batch": (_I, [_P, _I, _P, _P, _I, C.POINTER(BowResult)]),
+    "eao_vocabulary_transform_device": (_I, [_P, _P, _P, _I, _I, C.POINTER(BowResult), _P]),
+    "eao_bow_score_l1": (_I, [_I, _P, _P, _I, _P, _P, _P, _P]),
     "eao_bundle_adjustment_plan": (_I, [_I, _I, _P, _P, _I, _P, _P, _P, _I, _P, _I, _P, _I, _P, _I, _P, _I, _P, _I]),
 }
 

@@ -734,8 +734,9 @@ eao_status eao_tracker_track_with_motion_model(eao_tracker* h, const eao_keypoin
  * 1 / HISTO_LENGTH :171), Optimizer::PoseOptimization from the last frame's pose (:1584-1590), and -- when discard_outliers != 0 -- the "Discard outliers" loop
  * (:1593-1612); one copy back.  The reference keyframe travels as host arrays per keyframe keypoint i (n_kf <= max_keypoints entries): valid[i] != 0 where
  * GetMapPointMatches()[i] != NULL && !isBad(); Xw = GetWorldPos(); kf_desc = pKF->mDescriptors.row(i); kf_angle = pKF->mvKeysUn[i].angle.  fv_kf = pKF->mFeatVec,
- * fv_cur = mCurrentFrame.mFeatVec: the frame's own vector is what Frame::ComputeBoW (:1571) makes of its descriptors on the host -- DBoW2's vocabulary tree is
- * not part of this library, so this stage costs the descriptors one trip to the host before the call.  A keypoint index lies in ONE node (DBoW2 files a feature
+ * fv_cur = mCurrentFrame.mFeatVec: the frame's own vector is what Frame::ComputeBoW (:1571) makes of its descriptors -- this entry point
+ * takes it as host arrays, so this stage still costs one trip to the host before the call (eao_vocabulary_transform_device computes the vector from the
+ * descriptors in HBM; feeding it to this chain without the hop is a later change).  A keypoint index lies in ONE node (DBoW2 files a feature
  * under its single ancestor at levelsup); a vector that lists an index twice, out of range, or whose node ids do not ascend fails with EAO_ERR_INVALID before
  * any kernel runs, an index of fv_cur beyond the *d_n keypoints the extractor left fails after the chain.  Tcw_last: mLastFrame.mTcw, 16 floats row-major, finite.
  * Result as for eao_tracker_track_with_motion_model, with kp_map_point[k] = the KEYFRAME KEYPOINT INDEX whose map point frame keypoint k took, or -1, and n_matches =
@@ -1053,6 +1054,74 @@ eao_status eao_pnp_solver_iterate_batch(int32_t n_problems, const eao_pnp_solver
 /* Diagnostic (tools/bench_pnp_solver.py): with EAO_PNP_EVENTS=1 in the environment, the device time in ms of each of the four kernels of this thread's last
  * eao_pnp_solver_iterate / _batch (hypotheses, scan, refine, finish), from HIP events on its stream.  EAO_ERR_INVALID when there is no measurement. */
 eao_status eao_pnp_solver_last_kernel_ms(float* kernel_ms /* 4 */);
+
+/* ------------------------------------------------------------------------------------------------
+ * ORBVocabulary (reference include/ORBVocabulary.h = DBoW2::TemplatedVocabulary<FORB::TDescriptor, FORB>, Thirdparty/DBoW2/DBoW2/TemplatedVocabulary.h):
+ * the vocabulary tree on the device.  Frame::ComputeBoW (src/Frame.cc:764-771, called at src/Tracking.cc:1571 and :2789), KeyFrame::ComputeBoW
+ * (src/KeyFrame.cc:93-101, called at src/LocalMapping.cc:141 and src/Tracking.cc:1424-1425) and ORBVocabulary::score (src/LoopClosing.cc:134,
+ * src/KeyFrameDatabase.cc:132, 248) stand behind these entry points.  Everything is bit for bit what upstream computes, the doubles included: every double is
+ * the result of single IEEE operations in upstream's order.
+ *
+ * The handle.  The five arrays are what both upstream file formats hold per node (TemplatedVocabulary.h:1350-1480); array entry i is node id i + 1 in file
+ * order, the root (id 0) is implied.  The children of a node are its nodes in ascending id (the loaders' push_back order, the order ties are broken in); word ids
+ * count the leaf-flagged nodes in id order (:1420-1427, :1468-1473).  The descent stops at a node without children (:1266, :340), so eao_vocabulary_create
+ * fails with EAO_ERR_INVALID -- before anything reaches the device -- when is_leaf[i] disagrees with "no node names i + 1 as its parent", when parent[i] is not in
+ * 0 .. i, or on an enum out of range.  n_nodes == 0 is a valid, empty vocabulary (empty(), :1146): every transform over it returns empty vectors and zeroed
+ * feat_* arrays.  depth (upstream's m_L) is DERIVED: the largest depth of a leaf (a child of the root has depth 1); a file whose header names another L than its
+ * tree has differs from upstream in the node ids of the FeatureVector only.  The arrays are copied; the handle is immutable and any number of host threads may
+ * use it at once (each thread has its own stream and scratch).  On the device the children of one node are contiguous; file ids and word ids are what is
+ * reported outward. */
+typedef struct eao_vocabulary eao_vocabulary;
+typedef struct {
+    int32_t n_nodes;            /* nodes WITHOUT the root; array entry i is node id i+1, in file order */
+    const int32_t* parent;      /* parent id, 0 = root; required: 0 <= parent[i] < i+1 */
+    const uint8_t* descriptor;  /* n_nodes*32 */
+    const double*  weight;      /* Node::weight (WordValue is double; the binary file stores float, promoted) */
+    const uint8_t* is_leaf;     /* the file's leaf flag */
+    int32_t weighting;          /* DBoW2 enum order: 0 TF_IDF, 1 TF, 2 IDF, 3 BINARY */
+    int32_t norm;               /* what mustNormalize() yields: 0 none, 1 L1, 2 L2 */
+} eao_vocabulary_desc;
+eao_status eao_vocabulary_create(const eao_vocabulary_desc* desc, eao_vocabulary** out);
+void eao_vocabulary_destroy(eao_vocabulary* voc);
+/* each pointer may be NULL; n_words = size(), depth and max_children as defined above (0 for the empty vocabulary) */
+eao_status eao_vocabulary_info(const eao_vocabulary* voc, int32_t* n_nodes, int32_t* n_words, int32_t* depth, int32_t* max_children);
+
+/* TemplatedVocabulary::transform(features, v, fv, levelsup), :1138-1206, with the per-feature descent of :1229-1271.
+ * Descent: from the root, each level takes the child with the smallest FORB::distance (FORB.cpp:81-101); strict <, so the first child in id order wins a tie;
+ * until a node without children.  nid is the node reached at level depth - levelsup (the first chosen child is level 1); a level <= 0 gives nid = 0.  A leaf
+ * reached ABOVE that level leaves nid uninitialised upstream (:1163, :1263); here nid is then the leaf's own node id and feat_stopped bit 1 is set.
+ * A feature whose word weight is not > 0 enters neither vector (:1169, :1197; feat_stopped bit 0).  TF_IDF / TF: addWeight adds the weight once per feature in
+ * feature order (BowVector.cpp:34-46: c - 1 sequential additions for a word seen c times), and without normalisation every value is divided by v.size()
+ * (:1176-1182).  IDF / BINARY: addIfNotExist, the weight once.  Normalisation (BowVector.cpp:62-84): L1 the sequential sum of fabs(value) in ascending word id,
+ * L2 the sequential sum of squares, then sqrt; each value divided when the norm is > 0.  FeatureVector (FeatureVector.cpp:31-45): node ids ascend, each node's
+ * indices ascend.  n <= EAO_VOCABULARY_MAX_FEATURES per frame; more fails with EAO_ERR_INVALID and nothing is written.  levelsup >= 0.
+ * The result arrays are the caller's: capacities n (word_id, word_value, node_id, index, feat_*) and n + 1 (node_start); entries past the counts are not
+ * written.  EAO_ERR_INVALID leaves every output untouched.  Two calls on the same arguments return the same bytes. */
+#define EAO_VOCABULARY_MAX_FEATURES 8192
+typedef struct {
+    int32_t n_words;   uint32_t* word_id;  double* word_value;                  /* BowVector in std::map order; capacity n */
+    int32_t n_fv_nodes; uint32_t* node_id; int32_t* node_start; uint32_t* index; /* FeatureVector, the layout of eao_feature_vector; capacities n, n+1, n */
+    uint32_t* feat_word; uint32_t* feat_node; uint8_t* feat_stopped;            /* optional (NULL): per feature, for inspection */
+} eao_bow_result;
+eao_status eao_vocabulary_transform(const eao_vocabulary* voc, const uint8_t* desc, int32_t n, int32_t levelsup, eao_bow_result* result);
+/* n_frames frames in one upload, one launch chain and one copy back: frame f owns descriptors frame_start[f] .. frame_start[f+1] - 1 (frame_start[0] = 0,
+ * ascending) and results[f]; equal to n_frames single calls entry for entry. */
+eao_status eao_vocabulary_transform_batch(const eao_vocabulary* voc, int32_t n_frames, const uint8_t* desc, const int32_t* frame_start /* n_frames+1 */,
+                                          int32_t levelsup, eao_bow_result* results);
+/* The same over the descriptors and the count ONE frame's slice of eao_orb_extract_batch_device left in HBM (d_desc: cap*32 bytes, 16-byte aligned; d_n: that
+ * frame's count, read on the device).  Enqueued on `stream` (a hipStream_t; NULL = the null stream) behind whatever wrote them, and waited for: the result
+ * arrays are host arrays of capacity cap (cap + 1).  A count outside 0 .. cap fails with EAO_ERR_INVALID after the chain, outputs untouched.  This is the hook for
+ * keeping TrackReferenceKeyFrame's chain on the device; eao_tracker_track_reference_keyframe itself still takes fv_cur. */
+eao_status eao_vocabulary_transform_device(const eao_vocabulary* voc, const uint8_t* d_desc, const int32_t* d_n, int32_t cap, int32_t levelsup,
+                                           eao_bow_result* result, void* stream);
+
+/* L1Scoring::score (ScoringObject.cpp:23-68) of ONE query vector (v1: q_id / q_val, nq entries) against n_db stored vectors (v2: vector j owns entries
+ * db_start[j] .. db_start[j+1] - 1 of db_id / db_val) -- the loops of src/KeyFrameDatabase.cc:124-138, 243-254 and src/LoopClosing.cc:125-138 in one call.
+ * Per pair, over the common word ids in ascending order: s += fabs(vi - wi) - fabs(vi) - fabs(wi), evaluated left to right and accumulated sequentially from 0;
+ * scores[j] = -s / 2.0 (no common word: -0.0, as upstream).  Ids ascend strictly within each vector and db_start ascends from >= 0, else EAO_ERR_INVALID before
+ * anything is written.  Callers narrow to float themselves, as upstream does. */
+eao_status eao_bow_score_l1(int32_t nq, const uint32_t* q_id, const double* q_val, int32_t n_db, const int32_t* db_start /* n_db+1 */, const uint32_t* db_id,
+                            const double* db_val, double* scores /* n_db */);
 
 /* The value of EAO_ABI_VERSION the library was built with. Bumped whenever an entry point's parameter list or a struct's layout changes (round 3
  * changed eao_tracker_track_local_map and eao_track_result in place); a caller compiled against another version must not call into the library.
