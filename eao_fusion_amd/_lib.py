@@ -157,6 +157,17 @@ class BowResult(C.Structure):   # eao_bow_result
                 ("feat_word", C.c_void_p), ("feat_node", C.c_void_p), ("feat_stopped", C.c_void_p)]
 
 
+class KeyFrameDbQuery(C.Structure):   # eao_keyframe_db_query
+    _fields_ = [("kind", C.c_int32), ("query_id", C.c_uint64), ("nq", C.c_int32), ("q_id", C.c_void_p), ("q_val", C.c_void_p),
+                ("n_connected", C.c_int32), ("connected_id", C.c_void_p), ("min_score", C.c_float)]
+
+
+class KeyFrameDbScored(C.Structure):   # eao_keyframe_db_scored
+    _fields_ = [("n_sharing", C.c_int32), ("sharing_id", C.c_void_p), ("sharing_words", C.c_void_p),
+                ("max_common_words", C.c_int32), ("min_common_words", C.c_int32), ("n_scores", C.c_int32),
+                ("n_scored", C.c_int32), ("scored_id", C.c_void_p), ("scored_score", C.c_void_p)]
+
+
 # every symbol include/eao_fusion.h declares: (restype, argtypes)
 _P = C.c_void_p
 _I = C.c_int32
@@ -235,6 +246,15 @@ SYMBOLS = {
     "eao_vocabulary_transform_batch": (_I, [_P, _I, _P, _P, _I, C.POINTER(BowResult)]),
     "eao_vocabulary_transform_device": (_I, [_P, _P, _P, _I, _I, C.POINTER(BowResult), _P]),
     "eao_bow_score_l1": (_I, [_I, _P, _P, _I, _P, _P, _P, _P]),
+    "eao_keyframe_db_create": (_I, [_I, C.POINTER(_P)]),
+    "eao_keyframe_db_destroy": (None, [_P]),
+    "eao_keyframe_db_clear": (_I, [_P]),
+    "eao_keyframe_db_info": (_I, [_P, C.POINTER(_I), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
+    "eao_keyframe_db_add": (_I, [_P, C.c_uint64, _I, _P, _P]),
+    "eao_keyframe_db_erase": (_I, [_P, C.c_uint64]),
+    "eao_keyframe_db_intersect": (_I, [_P, _I, _P, _P, _I, _P, _P, _P, _P, C.POINTER(_I)]),
+    "eao_keyframe_db_query_scores": (_I, [_P, C.POINTER(KeyFrameDbQuery), _I, C.POINTER(KeyFrameDbScored)]),
+    "eao_keyframe_db_candidates": (_I, [_P, _I, C.c_uint64, _I, C.c_float, _I, _P, _P, _P, _P, _P, C.POINTER(_I), _P, _P, C.POINTER(_I)]),
     "eao_bundle_adjustment_plan": (_I, [_I, _I, _P, _P, _I, _P, _P, _P, _I, _P, _I, _P, _I, _P, _I, _P, _I, _P, _I]),
 }
 

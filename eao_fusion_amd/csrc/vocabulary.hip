@@ -16,6 +16,7 @@
 #include <string>
 #include <vector>
 
+#include "bow_intersect.h"
 #include "common.h"
 #include "vocabulary_internal.h"
 
@@ -271,32 +272,9 @@ __global__ __launch_bounds__(256) void k_bow_score_l1(int nq, const unsigned* qI
     const int j = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
     if (j >= nDb) return;      // (a whole wavefront leaves together)
     const int b = dbStart[j], e = dbStart[j + 1];
-    double s = 0.0;
-    for (int c0 = b; c0 < e; c0 += 64) {
-        const int c = c0 + lane;
-        double term = 0.0;
-        bool hit = false;
-        if (c < e) {
-            const unsigned id = dbId[c];
-            int lo = 0, hi = nq;
-            while (lo < hi) {
-                const int mid = (lo + hi) >> 1;
-                if (qId[mid] < id) lo = mid + 1;
-                else hi = mid;
-            }
-            if (lo < nq && qId[lo] == id) {
-                const double vi = qVal[lo], wi = dbVal[c];
-                term = (fabs(vi - wi) - fabs(vi)) - fabs(wi);      // ScoringObject.cpp:41, left to right
-                hit = true;
-            }
-        }
-        u64 mask = __ballot(hit);
-        while (mask) {      // the common words in ascending id: the same additions in every lane
-            const int l = __ffsll((long long)mask) - 1;
-            mask &= mask - 1;
-            s += __shfl(term, l);
-        }
-    }
+    int common = 0;
+    unsigned firstWord = 0;
+    const double s = eao::bow_l1_pair<false>(nq, qId, qVal, dbId, dbVal, b, e, lane, common, firstWord);
     if (lane == 0) scores[j] = -s / 2.0;      // :65 (no common word: -0.0)
 }
 

@@ -1123,6 +1123,64 @@ eao_status eao_vocabulary_transform_device(const eao_vocabulary* voc, const uint
 eao_status eao_bow_score_l1(int32_t nq, const uint32_t* q_id, const double* q_val, int32_t n_db, const int32_t* db_start /* n_db+1 */, const uint32_t* db_id,
                             const double* db_val, double* scores /* n_db */);
 
+/* ------------------------------------------------------------------------------------------------
+ * KeyFrameDatabase (reference include/KeyFrameDatabase.h, src/KeyFrameDatabase.cc): the recognition database at the head of LoopClosing::DetectLoop
+ * (src/LoopClosing.cc:141) and Tracking::Relocalization.  The BoW vectors of the added keyframes are RESIDENT on the device (one arena of word ids, one of
+ * values); a query uploads the query vector and downloads 16 bytes per live keyframe.  No inverted file is kept: upstream's walk over mvInvertedFile is, per
+ * stored keyframe, the number of the query's words it holds, and the list order of lKFsSharingWords is ascending (first common word, add order)
+ * (csrc/keyframe_db_internal.h says why).  Everything is bit for bit what upstream computes: counts, list orders, the float scores, the candidates.
+ *
+ * Per-keyframe state.  Upstream keeps mnLoopQuery / mnLoopWords / mLoopScore and mnRelocQuery / mnRelocWords / mRelocScore on the KeyFrame
+ * (include/KeyFrame.h:207-212); the handle keeps the same six per held id, initial state (0, 0, unset) as src/KeyFrame.cc:37 leaves them.  An id the handle does
+ * not hold (never added, or erased) reads as the initial state.  A score that was never written reads as 0.0f where upstream reads an uninitialised float, and
+ * stage 2 counts such reads (used_unset).
+ * Deviations: adding an id that is live is EAO_ERR_INVALID (upstream would list it twice); erasing an unknown id is a no-op, as upstream; a re-added id starts with
+ * fresh state; word ids at or above n_words are EAO_ERR_INVALID (upstream indexes past the vector).  A vector, stored or query, has at most
+ * EAO_VOCABULARY_MAX_FEATURES words.
+ * EAO_ERR_INVALID leaves every output and all state untouched.  A handle is serialised by one mutex (upstream's mMutex, widened to the whole call); distinct
+ * handles are independent.  The arenas grow by reallocation (device-to-device copy), and the words of erased keyframes are compacted away once they exceed half
+ * of the words in use. */
+typedef struct eao_keyframe_db eao_keyframe_db;
+/* KeyFrameDatabase::KeyFrameDatabase (:33-37): n_words = voc.size() */
+eao_status eao_keyframe_db_create(int32_t n_words, eao_keyframe_db** out);
+void eao_keyframe_db_destroy(eao_keyframe_db* db);
+/* clear() (:68-72): drops every keyframe and its state */
+eao_status eao_keyframe_db_clear(eao_keyframe_db* db);
+/* each pointer may be NULL: live keyframes, the words in use in the arena (those of erased keyframes included until they are compacted away), the arena's
+ * capacity in words */
+eao_status eao_keyframe_db_info(eao_keyframe_db* db, int32_t* n_live, int64_t* n_stored_words, int64_t* arena_capacity);
+/* add(pKF) (:39-45): pKF->mnId and pKF->mBowVec in std::map order.  Ids ascend strictly, else EAO_ERR_INVALID.  n == 0 is valid; such a keyframe is never listed. */
+eao_status eao_keyframe_db_add(eao_keyframe_db* db, uint64_t kf_id, int32_t n, const uint32_t* word_id, const double* word_val);
+/* erase(pKF) (:47-66) */
+eao_status eao_keyframe_db_erase(eao_keyframe_db* db, uint64_t kf_id);
+/* The kernel's raw result over the *n_live live keyframes in storage (= add) order: the number of common words (what the walks of :85-103 / :206-221 count), the
+ * smallest common word id (unspecified where common == 0) and the double of L1Scoring::score(query, stored) exactly as eao_bow_score_l1 gives it (-0.0 without a
+ * common word).  Pure: no per-keyframe state is touched, two calls return the same bytes.  It also gives src/LoopClosing.cc:125-138 its scores for the connected
+ * keyframes that are resident.  cap: the capacity of the four arrays; below the number of live keyframes is EAO_ERR_INVALID. */
+eao_status eao_keyframe_db_intersect(eao_keyframe_db* db, int32_t nq, const uint32_t* q_id, const double* q_val, int32_t cap, uint64_t* kf_id, int32_t* common,
+                                     uint32_t* first_word, double* score, int32_t* n_live);
+/* Stage 1: DetectLoopCandidates :75-141 (kind 0) / DetectRelocalizationCandidates :198-255 (kind 1) up to lScoreAndMatch; writes the per-keyframe state as upstream
+ * does.  kind 0: connected_id = the ids of pKF->GetConnectedKeyFrames() in any order (ids not held are ignored) and min_score; kind 1 reads neither. */
+typedef struct {
+    int32_t kind;                  /* 0 DetectLoopCandidates, 1 DetectRelocalizationCandidates */
+    uint64_t query_id;             /* pKF->mnId / F->mnId */
+    int32_t nq; const uint32_t* q_id; const double* q_val;     /* mBowVec in std::map order */
+    int32_t n_connected; const uint64_t* connected_id;
+    float min_score;
+} eao_keyframe_db_query;
+typedef struct {
+    int32_t n_sharing; uint64_t* sharing_id; int32_t* sharing_words;   /* lKFsSharingWords in list order with mnLoopWords / mnRelocWords; capacity cap */
+    int32_t max_common_words, min_common_words, n_scores;             /* :112-121, :227-238; all 0 when the list is empty */
+    int32_t n_scored; uint64_t* scored_id; float* scored_score;       /* lScoreAndMatch in list order; capacity cap */
+} eao_keyframe_db_scored;
+eao_status eao_keyframe_db_query_scores(eao_keyframe_db* db, const eao_keyframe_db_query* query, int32_t cap, eao_keyframe_db_scored* out);
+/* Stage 2, host only: :143-195 (kind 0) / :257-307 (kind 1).  nb_start / nb_id: GetBestCovisibilityKeyFrames(10) of every scored keyframe as a CSR; the
+ * neighbours' state is read from the handle.  cand_id (capacity n_scored): vpLoopCandidates / vpRelocCandidates in upstream's order.  acc_score / best_id
+ * (n_scored each, optional): lAccScoreAndMatch.  kind 1 ignores min_common_words and min_score, as upstream. */
+eao_status eao_keyframe_db_candidates(eao_keyframe_db* db, int32_t kind, uint64_t query_id, int32_t min_common_words, float min_score, int32_t n_scored,
+                                      const uint64_t* scored_id, const float* scored_score, const int32_t* nb_start /* n_scored+1 */, const uint64_t* nb_id,
+                                      uint64_t* cand_id, int32_t* n_cand, float* acc_score, uint64_t* best_id, int32_t* used_unset);
+
 /* The value of EAO_ABI_VERSION the library was built with. Bumped whenever an entry point's parameter list or a struct's layout changes (round 3
  * changed eao_tracker_track_local_map and eao_track_result in place); a caller compiled against another version must not call into the library.
  * Result structs are zero-initialised by the caller (`eao_track_result R = {0};`) before their array pointers are set: a pointer member the
