@@ -227,6 +227,7 @@ SYMBOLS = {
     "eao_bundle_adjustment": (_I, [C.POINTER(BAProblem), _I, _P, C.POINTER(BAResult)]),
     "eao_bundle_adjustment_planes": (_I, [C.POINTER(BAProblem), C.POINTER(BAPlanes), _I, _P, C.POINTER(BAResult), _P]),
     "eao_last_lm_trace": (_I, [_P, _P, _P, _I, C.POINTER(_I)]),
+    "eao_last_pose_rounds": (_I, [_I, _P, _P, _P, _I, C.POINTER(_I), _P, C.POINTER(_I)]),
     "eao_last_lm_timing": (_I, [C.POINTER(C.c_float), C.POINTER(_I)]),
     "eao_optimize_sim3": (_I, [C.POINTER(Sim3Problem), C.POINTER(Sim3Result)]),
     "eao_optimize_sim3_batch": (_I, [C.POINTER(Sim3Problem), _I, C.POINTER(Sim3Result)]),

@@ -875,6 +875,22 @@ eao_status eao_last_lm_trace(double* lambda, double* chi2, int32_t* trials, int3
     return EAO_OK;
 }
 
+eao_status eao_last_pose_rounds(int32_t frame, double* lambda, double* chi2, int32_t* trials, int32_t cap, int32_t* n, int32_t* round_start, int32_t* n_rounds) {
+    EAO_REQUIRE(n && n_rounds, "null argument");
+    EAO_REQUIRE(frame >= 0 && frame < (int)g_trace.pose.size(), "frame %d: the last PoseOptimization call of this thread had %d frames", frame, (int)g_trace.pose.size());
+    const PoseRoundsHost& h = g_trace.pose[frame];
+    const int m = std::min(h.n, cap);
+    for (int i = 0; i < m; i++) {
+        if (lambda) lambda[i] = h.lambda[i];
+        if (chi2) chi2[i] = h.chi2[i];
+        if (trials) trials[i] = h.trials[i];
+    }
+    *n = m;
+    if (round_start) for (int k = 0; k < 4; k++) round_start[k] = h.roundStart[k];
+    *n_rounds = h.nRounds;
+    return EAO_OK;
+}
+
 eao_status eao_last_lm_timing(float* device_ms, int32_t* linearizations) {
     if (device_ms) *device_ms = g_trace.deviceMs;
     if (linearizations) *linearizations = g_trace.linearizations;

@@ -235,12 +235,21 @@ struct GbaPlan {
 uint64_t gba_pattern_hash(int nFa, const std::vector<int>& prA, const std::vector<int>& prB);
 void gba_build_plan(int nFa, const std::vector<int>& prA, const std::vector<int>& prB, int forceP, GbaPlan& pl, int bw = 6);
 
+// PoseOptimization's trace of ONE frame with the index at which each of its optimize() calls (rounds) begins; -1 for a round that was not run
+struct PoseRoundsHost {
+    int n, nRounds;
+    int roundStart[4];
+    double lambda[64], chi2[64];
+    int trials[64];
+    PoseRoundsHost() : n(0), nRounds(0) { roundStart[0] = roundStart[1] = roundStart[2] = roundStart[3] = -1; }      // (the arrays are written up to n)
+};
 struct LMTraceHost {
     std::vector<double> lambda, chi2;
     std::vector<int> trials;
+    std::vector<PoseRoundsHost> pose;      // eao_pose_optimization: one entry; eao_pose_optimization_batch: one per frame
     float deviceMs = 0;
     int linearizations = 0;
-    void clear() { lambda.clear(); chi2.clear(); trials.clear(); deviceMs = 0; linearizations = 0; }
+    void clear() { lambda.clear(); chi2.clear(); trials.clear(); pose.clear(); deviceMs = 0; linearizations = 0; }
 };
 extern thread_local LMTraceHost g_trace;      // (defined in lm_host.hip)
 

@@ -21,7 +21,8 @@ struct PoseDev {
     Cam cam;
     // outputs
     GP<SE3> Tout;
-    GP<int> result;         // [0] nBad of the last round, [1] LM iterations, [2] trace count
+    GP<int> result;         // [0] nBad of the last round, [1] LM iterations, [2] trace count, [3] passes (register kernels), [4 .. 8) the trace count at which each
+                            // round (optimize() call) began -- rounds that were not run keep what the host put there
     GP<double> trace;       // 3 * 64: lambda, chi2, trials
     GP<long long> dbg;      // optional phase stamps (diagnostic runs of the harness only)
     // plane edges: nPlanes x { world[4], meas[4], infoAngle, infoDistance } doubles; flags as for the points
@@ -360,6 +361,7 @@ __device__ __forceinline__ void pose_lm_fused(const PoseDev& P) {
         for (int k = 0; k < EPT; k++) any |= !(eF[k] & 2);
         if (PLANES && t < M) any |= !(s_pflag[t] & 2);
         if (lane == 0) s_pose[wv][ei] = P.T0;                                           // every round restarts from the frame's pose (src/Optimizer.cc:547)
+        if (t == 0) P.result[4 + round] = ntrace;                                       // where this optimize() call's part of the trace begins
         ci = ei;
         PoseRt Tm = pose_rt(P.T0);                                                      // rotation matrix + translation of the pose the next heavy pass evaluates
         const int active = __syncthreads_or(any);
@@ -528,9 +530,12 @@ __device__ __forceinline__ void pose_lm_fused(const PoseDev& P) {
                     if (lane < 28) mySys[lane] = tot;
                     curChi = lane_bcast_f64(tot, 27);
                     if (it == 0) {      // lambda_0 = tau * max |diagonal| (:166-180), at the first iteration of every optimize()
+                        // upstream's std::max(fabs(h), maxDiagonal), i.e. h unless h < maxDiagonal: a NaN on the diagonal (a point in the camera's plane z = 0) is
+                        // KEPT unless a later entry replaces it, where fmax would drop it -- lambda_0 is then NaN upstream, and so it is here
                         double md = 0;
-                        md = fmax(md, fabs(lane_bcast_f64(tot, 0))); md = fmax(md, fabs(lane_bcast_f64(tot, 6))); md = fmax(md, fabs(lane_bcast_f64(tot, 11)));
-                        md = fmax(md, fabs(lane_bcast_f64(tot, 15))); md = fmax(md, fabs(lane_bcast_f64(tot, 18))); md = fmax(md, fabs(lane_bcast_f64(tot, 20)));
+                        constexpr int kDiag[6] = {0, 6, 11, 15, 18, 20};
+#pragma unroll
+                        for (int a = 0; a < 6; a++) { const double h = fabs(lane_bcast_f64(tot, kDiag[a])); md = h < md ? md : h; }
                         lambda = refc::LM_TAU * md;
                         ni = 2;
                         nbad = 0;
@@ -750,7 +755,7 @@ __global__ __launch_bounds__(kPoseThreads) void k_pose_optimization_mem(PoseDev 
     };
     __syncthreads();
     for (int round = 0; round < refc::POSE_ROUNDS; round++) {
-        if (t == 0) { s_est = P.T0; s_active = 0; }
+        if (t == 0) { s_est = P.T0; s_active = 0; P.result[4 + round] = s_ntrace; }
         __syncthreads();
         {   // any level-0 edge?  (g2o: optimize() returns -1 when the index mapping is empty)
             int any = 0;
@@ -862,7 +867,7 @@ __global__ __launch_bounds__(kPoseThreads) void k_pose_optimization_mem(PoseDev 
                     if (it == 0) {
                         double md = 0;
                         int q = 0;
-                        for (int a = 0; a < 6; a++) { md = fmax(md, fabs(sums[q])); q += 6 - a; }
+                        for (int a = 0; a < 6; a++) { const double h = fabs(sums[q]); md = h < md ? md : h; q += 6 - a; }      // (std::max(fabs(h), md): keeps a NaN, see pose_lm_fused)
                         s_lambda = refc::LM_TAU * md;
                         s_ni = 2;
                         s_nbad = 0;
@@ -1019,16 +1024,25 @@ void pose_pack(const eao_pose_problem* p, const PoseIn& h) {
     eao::lm::pose_plane_records(p->n_planes, p->plane_world, p->plane_obs, p->plane_seen, h.planes);
 }
 
-// One problem's result block in mapped host memory, as the kernels write it: SE3 | 192 doubles of trace | 4 ints | kPoseMaxPlanes plane flags | n point flags
+// One problem's result block in mapped host memory, as the kernels write it: SE3 | 192 doubles of trace | 8 ints | kPoseMaxPlanes plane flags | n point flags
 struct PoseOut {
     SE3* T; double* trace; int* res; unsigned char* planeOutlier; unsigned char* outlier;
     static constexpr size_t kHead = (sizeof(SE3) + 15) & ~(size_t)15;
-    static size_t bytes(int n) { return (kHead + 192 * 8 + 16 + kPoseMaxPlanes + (size_t)n + 63) & ~(size_t)63; }
+    static_assert(refc::POSE_ROUNDS == 4, "PoseDev::result holds four round starts behind its four counts");
+    static size_t bytes(int n) { return (kHead + 192 * 8 + 32 + kPoseMaxPlanes + (size_t)n + 63) & ~(size_t)63; }
     explicit PoseOut(unsigned char* base)
-        : T((SE3*)base), trace((double*)(base + kHead)), res((int*)(trace + 192)), planeOutlier((unsigned char*)(res + 4)), outlier(planeOutlier + kPoseMaxPlanes) {}
+        : T((SE3*)base), trace((double*)(base + kHead)), res((int*)(trace + 192)), planeOutlier((unsigned char*)(res + 8)), outlier(planeOutlier + kPoseMaxPlanes) {}
     void clear(int n) const {      // (the memory variant of the kernel reads the flags before it first writes them)
         std::memset(planeOutlier, 0, kPoseMaxPlanes + (size_t)n);
         res[0] = res[1] = res[2] = res[3] = 0;
+        res[4] = res[5] = res[6] = res[7] = -1;      // (a round that is not run leaves its entry)
+    }
+    // the LM trace with its round boundaries, for eao_last_pose_rounds
+    void read_rounds(PoseRoundsHost& h) const {
+        h.n = std::min(std::max(res[2], 0), 64);
+        for (int k = 0; k < h.n; k++) { h.lambda[k] = trace[k]; h.chi2[k] = trace[64 + k]; h.trials[k] = (int)trace[128 + k]; }
+        h.nRounds = 0;
+        for (int k = 0; k < 4; k++) { h.roundStart[k] = res[4 + k]; if (res[4 + k] >= 0) h.nRounds = k + 1; }
     }
     void read(const eao_pose_problem* p, eao_pose_result* r) const {
         const SE3 Tout = *T;
@@ -1066,6 +1080,7 @@ eao_status eao_pose_optimization(const eao_pose_problem* p, eao_pose_result* r) 
     for (int i = 0; i < n; i++) r->outlier[i] = 0;
     r->lm_iterations = 0;
     if (n < 3) {  // "if(nInitialCorrespondences<3) return 0" (src/Optimizer.cc:453-454): pose untouched
+        g_trace.pose.resize(1);      // (no round, no trace)
         std::memcpy(r->Tcw, p->Tcw, 16 * sizeof(float));
         r->n_inliers = 0;
         return EAO_OK;
@@ -1113,6 +1128,8 @@ eao_status eao_pose_optimization(const eao_pose_problem* p, eao_pose_result* r) 
         g_trace.lambda.push_back(o.trace[k]); g_trace.chi2.push_back(o.trace[64 + k]); g_trace.trials.push_back((int)o.trace[128 + k]);
     }
     g_trace.linearizations = res[1];
+    g_trace.pose.resize(1);
+    o.read_rounds(g_trace.pose[0]);
     EAO_HIP(hipEventElapsedTime(&g_trace.deviceMs, c.ev0, c.ev1));
     return EAO_OK;
 }
@@ -1146,6 +1163,9 @@ eao_status eao_pose_optimization_batch(const eao_pose_problem* ps, int32_t nb, e
     }
     int nk = 0;
     for (int g = 0; g < 8; g++) nk += (int)grp[g].size();
+    static thread_local std::vector<PoseRoundsHost> rounds;      // every frame's trace, by frame (eao_last_pose_rounds); handed to g_trace at the end: a frame that goes
+    rounds.clear();                                              // through the single call below clears g_trace
+    rounds.resize(nb);
     if (nk) {
         // arena: [records | per frame: Xw, obs, info, flags, planes] uploaded, then the per-frame residual scratch
         struct Slot { int b; PoseIn in; double* err; size_t out; };
@@ -1195,11 +1215,14 @@ eao_status eao_pose_optimization_batch(const eao_pose_problem* ps, int32_t nb, e
         EAO_HIP(hipEventRecord(c.ev1, c.stream));
         EAO_HIP(eao::wait_latency(c.stream));
         EAO_HIP(hipGetLastError());
-        for (const Slot& s : slots) PoseOut(c.pinOut.p + s.out).read(&ps[s.b], &rs[s.b]);
+        for (const Slot& s : slots) { const PoseOut o(c.pinOut.p + s.out); o.read(&ps[s.b], &rs[s.b]); o.read_rounds(rounds[s.b]); }
         EAO_HIP(hipEventElapsedTime(&g_trace.deviceMs, c.ev0, c.ev1));
     }
-    for (int b : single)
+    for (int b : single) {
         if ((st = eao_pose_optimization(&ps[b], &rs[b]))) return st;
+        rounds[b] = g_trace.pose[0];
+    }
+    g_trace.pose.swap(rounds);
     return EAO_OK;
 }
 

@@ -18,6 +18,18 @@ def _trace():
     return dict(lam=lam[:n.value], chi2=chi[:n.value], trials=tr[:n.value])
 
 
+def _pose_trace(frame=0):
+    """the LM trace of one frame of the last PoseOptimization / PoseOptimizationBatch call, with round_start: the trace index at which each
+    of its optimize() calls (rounds) begins, one entry per round that ran"""
+    lam = np.zeros(64)
+    chi = np.zeros(64)
+    tr = np.zeros(64, np.int32)
+    rs = np.zeros(4, np.int32)
+    n, nr = C.c_int32(), C.c_int32()
+    _lib.check(_lib.load().eao_last_pose_rounds(frame, _lib.ptr(lam), _lib.ptr(chi), _lib.ptr(tr), 64, C.byref(n), _lib.ptr(rs), C.byref(nr)))
+    return dict(lam=lam[:n.value], chi2=chi[:n.value], trials=tr[:n.value], round_start=rs[:nr.value])
+
+
 def _timing():
     ms, lin = C.c_float(), C.c_int32()
     if _lib.load().eao_last_lm_timing(C.byref(ms), C.byref(lin)) != 0:
@@ -50,7 +62,7 @@ class Optimizer:
         R.plane_outlier = _lib.ptr(pout)
         _lib.check(_lib.load().eao_pose_optimization(C.byref(P), C.byref(R)))
         out = dict(Tcw=np.array(R.Tcw, np.float32).reshape(4, 4), outlier=outl[:n], n_inliers=R.n_inliers,
-                   lm_iterations=R.lm_iterations, trace=_trace(), timing=_timing())
+                   lm_iterations=R.lm_iterations, trace=_pose_trace(), timing=_timing())
         if m:
             out["plane_outlier"] = pout[:m]
         return out
@@ -83,9 +95,9 @@ class Optimizer:
         return dict(P=Ps, R=Rs, n=nb, keep=keep)
 
     @staticmethod
-    def PoseOptimizationBatch(probs, packed=None):
+    def PoseOptimizationBatch(probs, packed=None, traces=False):
         """One PoseOptimization per element of `probs` (the candidate loop of Tracking::Relocalization, src/Tracking.cc:2786-2940)
-        in a single eao_pose_optimization_batch call.  Returns a list of the dicts PoseOptimization returns."""
+        in a single eao_pose_optimization_batch call.  Returns a list of the dicts PoseOptimization returns (each frame's LM trace on request)."""
         pk = packed or Optimizer.pack_pose_batch(probs)
         nb, Rs, keep = pk["n"], pk["R"], pk["keep"]
         _lib.check(_lib.load().eao_pose_optimization_batch(pk["P"], nb, Rs))
@@ -94,6 +106,8 @@ class Optimizer:
             outl, pout, n, m = keep[b][7:]
             out = dict(Tcw=np.array(Rs[b].Tcw, np.float32).reshape(4, 4), outlier=outl[:n], n_inliers=Rs[b].n_inliers,
                        lm_iterations=Rs[b].lm_iterations)
+            if traces:
+                out["trace"] = _pose_trace(b)
             if m:
                 out["plane_outlier"] = pout[:m]
             outs.append(out)

@@ -624,6 +624,12 @@ eao_status eao_bundle_adjustment_plan(int32_t n_free, int32_t n_pairs, const int
  * up to cap entries of (lambda after the iteration, robust chi2, trials). Returns the count in *n. */
 eao_status eao_last_lm_trace(double* lambda, double* chi2, int32_t* trials, int32_t cap, int32_t* n);
 
+/* PoseOptimization runs up to four optimize() calls (rounds, src/Optimizer.cc:541-660) and lays their traces end to end.  Frame `frame` of the last
+ * eao_pose_optimization (frame 0) / eao_pose_optimization_batch call made by this thread: its trace as eao_last_lm_trace gives it, the number of
+ * rounds it ran in *n_rounds and the trace index at which each began in round_start[0 .. 4) (-1 for a round that was not run; a round without an
+ * iteration begins where the next one does). */
+eao_status eao_last_pose_rounds(int32_t frame, double* lambda, double* chi2, int32_t* trials, int32_t cap, int32_t* n, int32_t* round_start, int32_t* n_rounds);
+
 /* HIP-event time (ms) spent in device work by the last eao_local_ba / eao_pose_optimization on this thread,
  * and the number of linearisations (buildSystem calls) it made. */
 eao_status eao_last_lm_timing(float* device_ms, int32_t* linearizations);

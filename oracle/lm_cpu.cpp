@@ -766,7 +766,9 @@ struct orc_pose_problem {
     const float* inv_sigma2;  // n
     float fx, fy, cx, cy, bf;
 };
-struct orc_trace { int32_t n; double lambda[64]; double chi2[64]; int32_t trials[64]; };
+// n_rounds / round_start / round_active: PoseOptimization only -- the optimize() calls made, the trace index at which each one begins (a call that makes
+// no iteration begins where the next one does) and the number of level-0 edges it finds; entries of calls that were not made are -1
+struct orc_trace { int32_t n; double lambda[64]; double chi2[64]; int32_t trials[64]; int32_t n_rounds; int32_t round_start[4]; int32_t round_active[4]; };
 
 // returns nInitialCorrespondences - nBad; Tcw_out float[16]; outlier[n]; pose_d = final (qx,qy,qz,qw,tx,ty,tz) in fp64.
 // Planes (src/Optimizer.cc:456-535, 626-658): plane_world / plane_obs 4 floats each (MapPlane::GetWorldPos(),
@@ -786,7 +788,7 @@ int orc_pose_optimization_planes(const orc_pose_problem* P, int n_planes, const 
         e.info = P->inv_sigma2[i];
         outlier[i] = 0;
     }
-    if (trace) trace->n = 0;
+    if (trace) { trace->n = 0; trace->n_rounds = 0; for (int k = 0; k < 4; k++) trace->round_start[k] = trace->round_active[k] = -1; }
     if (n < 3) { std::memcpy(Tcw_out, P->Tcw, 16 * sizeof(float)); return 0; }   // checked BEFORE the planes are added (:453-454)
     const double angleInfo = refc::PLANE_ANGLE_INFO / (1.0 * 1.0), disInfo = refc::PLANE_DIST_INFO_ROOT * refc::PLANE_DIST_INFO_ROOT, planeChi = refc::PLANE_CHI2;
     pb.deltaPlane = (float)std::sqrt(planeChi);
@@ -807,6 +809,13 @@ int orc_pose_optimization_planes(const orc_pose_problem* P, int n_planes, const 
         pb.est = se3_from_Tcw_f32(P->Tcw);
         LM lm;
         LMTrace tr;
+        if (trace && it < 4) {
+            trace->round_start[it] = trace->n; trace->n_rounds = it + 1;
+            int act = 0;
+            for (const PoseEdge& e : pb.edges) act += e.level == 0;
+            for (const PlaneEdge& e : pb.planes) act += e.level == 0;
+            trace->round_active[it] = act;
+        }
         lm.optimize(pb, refc::POSE_ITS, nullptr, &tr);
         if (trace) for (size_t k = 0; k < tr.lambda.size() && trace->n < 64; k++) {
             trace->lambda[trace->n] = tr.lambda[k]; trace->chi2[trace->n] = tr.chi2[k]; trace->trials[trace->n] = tr.trials[k]; trace->n++;

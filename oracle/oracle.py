@@ -25,11 +25,16 @@ def build():
 
 
 class Trace(C.Structure):
-    _fields_ = [("n", C.c_int32), ("lam", C.c_double * 64), ("chi2", C.c_double * 64), ("trials", C.c_int32 * 64)]
+    _fields_ = [("n", C.c_int32), ("lam", C.c_double * 64), ("chi2", C.c_double * 64), ("trials", C.c_int32 * 64),
+                ("n_rounds", C.c_int32), ("round_start", C.c_int32 * 4), ("round_active", C.c_int32 * 4)]      # (orc_trace; the last three are written by PoseOptimization only)
 
-    def to_dict(self):
+    def to_dict(self, rounds=False):
         n = self.n
-        return dict(lam=np.array(self.lam[:n]), chi2=np.array(self.chi2[:n]), trials=np.array(self.trials[:n]))
+        d = dict(lam=np.array(self.lam[:n]), chi2=np.array(self.chi2[:n]), trials=np.array(self.trials[:n]))
+        if rounds:      # the trace index at which each optimize() call of PoseOptimization begins, and the level-0 edges it finds
+            d["round_start"] = np.array(self.round_start[:self.n_rounds], np.int32)
+            d["round_active"] = np.array(self.round_active[:self.n_rounds], np.int32)
+        return d
 
 
 class PoseProblem(C.Structure):
@@ -226,7 +231,7 @@ def pose_optimization(prob):
     pw = prob.get("plane_world")
     if pw is None:
         ninl = lib().orc_pose_optimization(C.byref(P), _p(T_out), _p(outl), _p(pose_d), C.byref(tr))
-        return dict(Tcw=T_out, outlier=outl[:n], n_inliers=ninl, pose_d=pose_d, trace=tr.to_dict())
+        return dict(Tcw=T_out, outlier=outl[:n], n_inliers=ninl, pose_d=pose_d, trace=tr.to_dict(rounds=True))
     pw = np.ascontiguousarray(pw, np.float32)
     po = np.ascontiguousarray(prob["plane_obs"], np.float32)
     ps = np.ascontiguousarray(prob["plane_seen"], np.uint8)
@@ -235,7 +240,7 @@ def pose_optimization(prob):
     fn.restype = C.c_int
     ninl = fn(C.byref(P), C.c_int(len(pw)), C.c_void_p(_p(pw)), C.c_void_p(_p(po)), C.c_void_p(_p(ps)), C.c_void_p(_p(T_out)),
               C.c_void_p(_p(outl)), C.c_void_p(_p(pout)), C.c_void_p(_p(pose_d)), C.byref(tr))
-    return dict(Tcw=T_out, outlier=outl[:n], plane_outlier=pout[:len(pw)], n_inliers=ninl, pose_d=pose_d, trace=tr.to_dict())
+    return dict(Tcw=T_out, outlier=outl[:n], plane_outlier=pout[:len(pw)], n_inliers=ninl, pose_d=pose_d, trace=tr.to_dict(rounds=True))
 
 
 def local_ba(prob, its=(5, 10), stop=None):

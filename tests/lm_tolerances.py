@@ -15,6 +15,11 @@ CHI2_REL = 1e-6              # test_local_ba_parity & co.  Observed 8e-10 (six o
 CHI2_REL_FAR_OFF = 1e-4      # the far-off-start families (25 degrees, 0.8 m off; monocular-heavy): round 1
 # lambda per iteration, relative
 LAMBDA_REL = 5e-4            # round 2 (2e-3 in round 1): observed 5.1e-5; the oracle's own one-ulp band is 8e-3 (profiles/r02_lm_trace_sensitivity.txt)
+                             # PoseOptimization with plane edges (test_pose_optimization_with_planes, every round since the trace is compared per round): held to this figure
+                             # on the iterations that are not stalled and on which the oracle's thirteen runs (one-ulp input perturbations) make the same decision, EXCEPT
+                             # where the oracle's own lambda spread at that iteration exceeds LAMBDA_REL / CHAOTIC_BANDS_ALLOWED -- the central-difference Jacobians (1e-7 of
+                             # noise) make the last iterations in front of the stall noise-driven in the oracle already: its own lambda moves by 0.11 - 0.32 there on three
+                             # of the eleven scenes and its own trial counts differ on two.  There lambda is held to CHAOTIC_BANDS_ALLOWED x that spread, measured in the test.
 LAMBDA_REL_FAR_OFF = 4e-3    # round 4 (2e-3 before), the tile-solver path: the pair assembly works on Cholesky-scaled blocks W = Hpl C^-T (csrc/lm.hip, ba_chol3) where the
                              # oracle multiplies by an explicit 3 x 3 inverse as upstream does -- different rounding from the first iteration on.  Seed 3037, iteration 14:
                              # 3.07e-3 off (1.45e-3 with the explicit inverse of round 3) while chi2 agrees to 9e-8 and the points to 8e-6 of the update (profiles/r04_lm_seed3037.txt)
@@ -40,3 +45,15 @@ CHI2_REL_BATCH_VS_SINGLE = 1e-4
 # ---- round 6: tests/test_gpu_lm_conditioning.py -- the five excursions of the round-5 sweeps (profiles/r05_sweeps.txt: one weakly constrained landmark each,
 #      1.1 - 1.9e-4 of the update) + 50 fresh draws.  A problem outside UPDATE_REL must lie inside the oracle's own one-ulp band, measured in the test; at most this many may.
 CONDITIONING_BANDED_MAX = 7
+
+# ---- pose rounds: written by tools/pose_round_bands.py, do not edit (tests/test_lm_tolerances.py compares it with profiles/pose_round_bands.txt)
+# chi2 and lambda of a DECIDED iteration (same trial count in the oracle's thirteen runs) of the scenes of tests/pose_scenes.py, relative; chi2 relative to
+# max(chi2, pose_scenes.CHI2_FLOOR).  Values that are not finite (zero_depth: chi2 is inf in every run) must be the same value.
+# POSE_ROUNDS_CHAOTIC_BAND: scenes whose returned pose moves by more than UPDATE_REL of the update among the oracle's own runs -- held to CHAOTIC_BANDS_ALLOWED x this
+# band instead; at most a quarter of the scenes may be listed (tests/test_pose_scenes_cpu.py)
+POSE_ROUNDS_CHAOTIC_BAND = {}
+POSE_ROUNDS_CHI2_REL = 7.889e-04
+POSE_ROUNDS_LAMBDA_REL = 6.909e-03
+POSE_ROUNDS_CHAOTIC_BAND['boundary n=9 planes=0 seed=4602'] = 3.211e-04
+POSE_ROUNDS_CHAOTIC_BAND['boundary n=7 planes=2 seed=4604'] = 1.669e-04
+# ---- pose rounds: end

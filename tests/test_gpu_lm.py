@@ -4,6 +4,7 @@ Bar (BASELINE.json north_star): <= 1e-4 relative on the pose / point UPDATES; th
 import numpy as np
 import pytest
 
+import pose_scenes
 from eao_fusion_amd import synth
 from lm_tolerances import (CHAOTIC_BAND, CHAOTIC_BANDS_ALLOWED, CHI2_REL, CHI2_REL_BATCH_VS_SINGLE, CHI2_REL_FAR_OFF, CHI2_REL_PLANES, LAMBDA_REL, LAMBDA_REL_FAR_OFF, LAMBDA_REL_FAR_OFF_MAP_SCALE, LEAVES_THE_BAR,
                            SCHEDULE_UNSTABLE, UPDATE_REL)
@@ -19,24 +20,45 @@ def gpu():
     return E
 
 
-def _check_trace(r, o, rel=CHI2_REL, lam_rel=LAMBDA_REL):
+def _rounds(t):
+    """the optimize() calls a trace is made of: PoseOptimization lays four of them end to end and says where each begins (trace["round_start"])"""
+    rs = t.get("round_start")
+    if rs is None:
+        return [(0, len(t["chi2"]))]
+    rs = [int(x) for x in rs]
+    return list(zip(rs, rs[1:] + [len(t["chi2"])]))
+
+
+def _check_trace(r, o, rel=CHI2_REL, lam_rel=LAMBDA_REL, own_runs=None):
     """LM control flow must match wherever it is well-conditioned: once chi2 stalls at the float32 noise floor
     (relative improvement < 1e-6) rho = (chi_old - chi_new)/scale is rounding noise and accept/reject is a coin flip
-    in ANY implementation, so only the well-conditioned prefix of each optimize() call is compared."""
+    in ANY implementation, so only the well-conditioned prefix of each optimize() call is compared -- of EACH: the rule
+    starts afresh where a round begins, both sides must have made the same number of rounds, and a round without
+    iterations must be one on both sides.
+    own_runs (PoseOptimization with plane edges): the oracle's thirteen runs of the problem (pose_scenes.oracle_runs, o first).  The central-difference Jacobians of
+    the plane edges carry 1e-7 of noise, and the last iterations in front of the stall are then coin flips in the ORACLE ALREADY: under one-ulp input perturbations its
+    own trial counts differ there and its own lambda moves by up to 0.3 (tests/lm_tolerances.py, LAMBDA_REL).  A round is then compared up to its first iteration that is
+    stalled OR undecided, and where the oracle's own lambda spread exceeds lam_rel / CHAOTIC_BANDS_ALLOWED, lambda is held to CHAOTIC_BANDS_ALLOWED x that spread."""
+    dec = pose_scenes.decided(own_runs) if own_runs else None
     tg, to = r["trace"], o["trace"]
-    n = min(len(tg["chi2"]), len(to["chi2"]))
-    prev = None
-    for k in range(n):
-        c = to["chi2"][k]
-        stalled = prev is not None and abs(prev - c) <= 1e-6 * max(abs(prev), 1e-12)
-        if stalled or c < 1e-6:
-            break
-        assert tg["trials"][k] == to["trials"][k], "trials differ at LM iteration %d" % k
-        assert tg["chi2"][k] == pytest.approx(c, rel=rel), "chi2 differs at LM iteration %d" % k
-        # (profiles/r02_lm_trace_sensitivity.txt: GPU vs oracle <= 5.1e-5 on these problems, where one float32 ulp on the inputs moves the
-        #  ORACLE's own lambda by up to 8e-3 -- lambda is a function of rho, a ratio of small differences)
-        assert tg["lam"][k] == pytest.approx(to["lam"][k], rel=lam_rel), "lambda differs at LM iteration %d" % k
-        prev = c
+    rg, ro = _rounds(tg), _rounds(to)
+    assert len(rg) == len(ro), "%d optimize() calls, the oracle made %d" % (len(rg), len(ro))
+    for rd, ((sg, eg), (so, eo)) in enumerate(zip(rg, ro)):
+        assert (eg > sg) == (eo > so), "round %d: %d iterations, the oracle %d" % (rd + 1, eg - sg, eo - so)
+        prev = None
+        for k in range(min(eg - sg, eo - so) if dec is None else min(eg - sg, eo - so, dec[rd])):
+            c = to["chi2"][so + k]
+            stalled = prev is not None and abs(prev - c) <= 1e-6 * max(abs(prev), 1e-12)
+            if stalled or c < 1e-6:
+                break
+            at = "LM iteration %d of round %d" % (k, rd + 1)
+            assert tg["trials"][sg + k] == to["trials"][so + k], "trials differ at " + at
+            assert tg["chi2"][sg + k] == pytest.approx(c, rel=rel), "chi2 differs at " + at
+            # (profiles/r02_lm_trace_sensitivity.txt: GPU vs oracle <= 5.1e-5 on these problems, where one float32 ulp on the inputs moves the
+            #  ORACLE's own lambda by up to 8e-3 -- lambda is a function of rho, a ratio of small differences)
+            lam_bound = lam_rel if dec is None else max(lam_rel, CHAOTIC_BANDS_ALLOWED * pose_scenes.lambda_spread_at(own_runs, rd, k))
+            assert tg["lam"][sg + k] == pytest.approx(to["lam"][so + k], rel=lam_bound), "lambda differs at " + at
+            prev = c
 
 
 def _check_updates(new_gpu, new_cpu, old, what):
@@ -202,9 +224,11 @@ def test_pose_optimization_with_planes(gpu, oracle, kw):
     any implementation."""
     p = synth.synth_pose(**kw)
     r = gpu.Optimizer.PoseOptimization(p)
-    o = oracle.pose_optimization(p)
+    own = pose_scenes.oracle_runs(oracle, p)
+    o = own[0]
     assert r["n_inliers"] == o["n_inliers"]
     assert np.array_equal(r["outlier"], o["outlier"]) and np.array_equal(r["plane_outlier"], o["plane_outlier"])
+    _check_trace(r, o, rel=CHI2_REL_PLANES, own_runs=own)
     _check_updates(r["Tcw"], o["Tcw"], p["Tcw"], "Tcw")
     if kw["n_planes"] >= 3:
         assert r["plane_outlier"][-1] == 1 and r["plane_outlier"][:-1].sum() == 0
@@ -220,6 +244,10 @@ def test_pose_optimization_batch_equals_single_calls(gpu):
            dict(n=300, seed=4200, n_planes=6), dict(n=1500, seed=4202, n_planes=32), dict(n=40, seed=4203, n_planes=1, mono_frac=1.0)]
     kws += [dict(n=200 + 37 * k, seed=4300 + k) for k in range(20)]
     probs = [synth.synth_pose(**kw) for kw in kws]
+    # the round scenes (tests/pose_scenes.py): rejected trials in every round, rounds on 0 / 1 / 2 edges, the `< 10` break, a point in the camera's plane
+    scenes = pose_scenes.all_scenes()
+    kws += list(scenes)
+    probs += [fn(*args) for family, fn, args in scenes.values()]
     singles = [gpu.Optimizer.PoseOptimization(p) for p in probs]
     for order in (list(range(len(probs))), list(reversed(range(len(probs))))):
         outs = gpu.Optimizer.PoseOptimizationBatch([probs[i] for i in order])
@@ -236,10 +264,11 @@ def test_pose_optimization_batch_equals_single_calls(gpu):
 def test_pose_optimization_batch_parity(gpu, oracle):
     """The batch against the fp64 oracle directly (same bar as the single call)."""
     probs = [synth.synth_pose(n=150 + 61 * k, seed=4400 + k, mono_frac=0.1 * (k % 5)) for k in range(12)]
-    outs = gpu.Optimizer.PoseOptimizationBatch(probs)
+    outs = gpu.Optimizer.PoseOptimizationBatch(probs, traces=True)
     for p, r in zip(probs, outs):
         o = oracle.pose_optimization(p)
         assert r["n_inliers"] == o["n_inliers"] and np.array_equal(r["outlier"], o["outlier"])
+        _check_trace(r, o)
         _check_updates(r["Tcw"], o["Tcw"], p["Tcw"], "Tcw")
 
 
