@@ -256,6 +256,16 @@ SYMBOLS = {
     "eao_keyframe_db_intersect": (_I, [_P, _I, _P, _P, _I, _P, _P, _P, _P, C.POINTER(_I)]),
     "eao_keyframe_db_query_scores": (_I, [_P, C.POINTER(KeyFrameDbQuery), _I, C.POINTER(KeyFrameDbScored)]),
     "eao_keyframe_db_candidates": (_I, [_P, _I, C.c_uint64, _I, C.c_float, _I, _P, _P, _P, _P, _P, C.POINTER(_I), _P, _P, C.POINTER(_I)]),
+    "eao_plane_map_create": (_I, [C.POINTER(_P)]),
+    "eao_plane_map_destroy": (None, [_P]),
+    "eao_plane_map_clear": (_I, [_P]),
+    "eao_plane_map_info": (_I, [_P, C.POINTER(_I), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
+    "eao_plane_map_add": (_I, [_P, C.c_uint64, _P, _I, _P, _P]),
+    "eao_plane_map_update_boundary": (_I, [_P, C.c_uint64, _I, _P, _P]),
+    "eao_plane_map_set_world_pos": (_I, [_P, C.c_uint64, _P]),
+    "eao_plane_map_erase": (_I, [_P, C.c_uint64]),
+    "eao_plane_map_boundary": (_I, [_P, C.c_uint64, _I, _P, C.POINTER(_I), _P]),
+    "eao_plane_map_associate": (_I, [_P, _I, _P, _P, _P, _I, _P, C.c_float, C.c_float, _P, _P, _P, _P, _P]),
     "eao_bundle_adjustment_plan": (_I, [_I, _I, _P, _P, _I, _P, _P, _P, _I, _P, _I, _P, _I, _P, _I, _P, _I, _P, _I]),
 }
 

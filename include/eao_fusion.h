@@ -693,7 +693,7 @@ eao_status eao_tracker_track_local_map(eao_tracker* h, const eao_keypoint* d_kps
                                        void* stream);
 
 /* One-shot options of the NEXT eao_tracker_track_* call on the handle (round 5; NULL or never called: defaults).
- *  - plane edges: in this fork Map::AssociatePlanesByBoundary runs BEFORE Optimizer::PoseOptimization in all three stages (src/Tracking.cc:1587, before :2181,
+ *  - plane edges (the association itself: eao_plane_map_associate, "MapPlane boundaries" below): in this fork Map::AssociatePlanesByBoundary runs BEFORE Optimizer::PoseOptimization in all three stages (src/Tracking.cc:1587, before :2181,
  *    TrackLocalMap), so the frame's associated planes are edges of the optimisation (src/Optimizer.cc:456-535, 626-658).  A caller whose frame carries them
  *    hands them over exactly as in eao_pose_problem (n_planes <= 32; plane_world = MapPlane::GetWorldPos(), plane_obs = mvPlaneCoefficients[i], plane_seen =
  *    mbSeen) and gets mvbPlaneOutlier back in plane_outlier (caller array, valid until the track call returns); the chained pose optimisation is then the
@@ -1186,6 +1186,64 @@ eao_status eao_keyframe_db_query_scores(eao_keyframe_db* db, const eao_keyframe_
 eao_status eao_keyframe_db_candidates(eao_keyframe_db* db, int32_t kind, uint64_t query_id, int32_t min_common_words, float min_score, int32_t n_scored,
                                       const uint64_t* scored_id, const float* scored_score, const int32_t* nb_start /* n_scored+1 */, const uint64_t* nb_id,
                                       uint64_t* cand_id, int32_t* n_cand, float* acc_score, uint64_t* best_id, int32_t* used_unset);
+
+/* ------------------------------------------------------------------------------------------------
+ * MapPlane boundaries (reference include/MapPlane.h, src/MapPlane.cc; Map::AssociatePlanesByBoundary src/Map.cc:155-215, Map::PointDistanceFromPlane :217-236,
+ * Map::SearchMatchedPlanes :245-292): the plane association that runs in front of Optimizer::PoseOptimization in all three tracking stages
+ * (src/Tracking.cc:1587, :2181, :2243, :2491) and in LoopClosing (src/LoopClosing.cc:395, :620).  The boundary clouds of the map's planes
+ * (MapPlane::mvBoundaryPoints, world frame) are RESIDENT on the device, 16 bytes per point; a query uploads the frame's plane coefficients and 32 bytes per
+ * candidate, and downloads one index and one distance per frame plane.  Everything is bit for bit what upstream's loops compute.
+ *
+ * The handle keeps, per plane id, the cloud and mWorldPos.  The table is in ADD order; update_boundary does not move a plane in it.
+ * Deviations: adding an id that is live is EAO_ERR_INVALID (upstream's ids are unique, src/MapPlane.cc:26); erasing an unknown id is a no-op, as
+ * std::set::erase (src/Map.cc:150); a candidate id the handle does not hold is EAO_ERR_INVALID.
+ * EAO_ERR_INVALID leaves every output and all state untouched.  A handle is serialised by one mutex (upstream's mMutexMap, widened to every call); distinct
+ * handles are independent.  The arena grows by reallocation (device-to-device copy), and replaced and erased clouds are compacted away once they exceed half of
+ * the points in use. */
+#define EAO_PLANE_MAP_MAX_ROWS 2048          /* frame planes (rows of coef) per eao_plane_map_associate call */
+#define EAO_PLANE_MAP_MAX_POINTS 1048576     /* points of one plane's cloud */
+#define EAO_PLANE_MAP_MAX_CANDIDATES 65536   /* candidates per call; rows x candidates <= 2^24 */
+#define EAO_PLANE_MAP_DIS_TH 0.2f            /* Map::mfDisTh, src/Map.cc:22 */
+#define EAO_PLANE_MAP_ANGLE_TH 0.8f          /* Map::mfAngleTh, src/Map.cc:23 */
+typedef struct eao_plane_map eao_plane_map;
+eao_status eao_plane_map_create(eao_plane_map** out);
+void eao_plane_map_destroy(eao_plane_map* pm);
+/* Map::clear (src/Map.cc:131-133): drops every plane; the allocation stays */
+eao_status eao_plane_map_clear(eao_plane_map* pm);
+/* each pointer may be NULL: live planes, the points in use in the arena (those of replaced and erased clouds included until they are compacted away), the
+ * arena's capacity in points */
+eao_status eao_plane_map_info(eao_plane_map* pm, int32_t* n_live, int64_t* n_points_in_use, int64_t* arena_capacity);
+/* MapPlane::MapPlane (src/MapPlane.cc:23-39): world_pos = Pos (4 floats), xyz = pRefKF->mvBoundaryPoints[idx] as n x 3 floats in the camera frame, Tcw =
+ * pRefKF->GetPose() as 16 floats, row-major.  The cloud is stored as pcl::transformPointCloud(cloud, out, T.inverse().matrix()) with Eigen::Isometry3d T =
+ * Converter::toSE3Quat(Tcw) leaves it (:34-36): the isometry in double (unit quaternion of the rotation block, then its rotation matrix), inverted as
+ * R^T, -(R^T t), and per coordinate (float)(m0*x + m1*y + m2*z + m3) in double, left to right.  Non-finite coordinates go through the same arithmetic.
+ * Tcw == NULL: the points are in the world frame already and are stored as they are.  n == 0 is valid.  A live id is EAO_ERR_INVALID. */
+eao_status eao_plane_map_add(eao_plane_map* pm, uint64_t id, const float* world_pos /* 4 */, int32_t n, const float* xyz /* n*3 */, const float* Tcw /* 16 or NULL */);
+/* MapPlane::UpdateBoundary (src/MapPlane.cc:150-153; called at src/Tracking.cc:1112): replaces the plane's cloud, same transform.  An id that is not held is
+ * EAO_ERR_INVALID. */
+eao_status eao_plane_map_update_boundary(eao_plane_map* pm, uint64_t id, int32_t n, const float* xyz, const float* Tcw);
+/* MapPlane::SetWorldPos (src/MapPlane.cc:137-142), also for what the optimisers write back.  An id that is not held is EAO_ERR_INVALID. */
+eao_status eao_plane_map_set_world_pos(eao_plane_map* pm, uint64_t id, const float* world_pos /* 4 */);
+/* Map::EraseMapPlane (src/Map.cc:147-153) and the losing side of MapPlane::Replace (src/MapPlane.cc:161-192).  An unknown id is a no-op. */
+eao_status eao_plane_map_erase(eao_plane_map* pm, uint64_t id);
+/* The resident world-frame cloud of a plane (*n points into xyz, capacity cap points; cap below the count is EAO_ERR_INVALID) and, when world_pos is not NULL, its
+ * mWorldPos.  xyz == NULL: the count (and world_pos) alone. */
+eao_status eao_plane_map_boundary(eao_plane_map* pm, uint64_t id, int32_t cap, float* xyz /* cap*3 */, int32_t* n, float* world_pos /* 4 or NULL */);
+/* Map::AssociatePlanesByBoundary (src/Map.cc:155-215; M = mTcw) and Map::SearchMatchedPlanes (:245-292; M = Scw) for n_sets frames against ONE candidate list
+ * (n_sets > 1: the connected keyframes of LoopClosing::SearchAndFuse, src/LoopClosing.cc:620).  Set s owns M + 16*s (row-major 4x4) and rows set_start[s] ..
+ * set_start[s+1] - 1 of coef (mvPlaneCoefficients, 4 floats per row, camera frame); set_start[0] = 0, ascending.  cand_id: the candidates in the caller's
+ * iteration order -- std::set order of Map::mspMapPlanes, vector order of vpPlanes; an id may appear twice.  cand_id == NULL: every live plane in add order, and
+ * n_cand must be their number (or 0: no candidates).
+ * Per row: pM = M^T c as a cv::Mat product (accumulated in double, rounded once to float; src/Frame.cc:373-379).  Per candidate in list order: angle = pM0*pW0 +
+ * pM1*pW1 + pM2*pW2 in float, left to right; the pair is gated in when angle > angle_th || angle < -angle_th (a NaN is not).  For a gated pair dis starts at
+ * 100 and takes d = |pM0*x + pM1*y + pM2*z + pM3| (float, left to right) of every point with d < dis (a NaN never wins; no points leave 100).  ldTh starts at
+ * dis_th; a gated candidate with dis < ldTh becomes the match and sets ldTh = dis: the first of equal minima wins, a distance equal to dis_th does not associate.
+ * match (rows): the index into the candidate list or -1; match_dis (rows): ldTh as the loop leaves it (dis_th where nothing associated).  Optional (NULL):
+ * world_coef (rows x 4) = pM; dis (rows x n_cand, row-major) with 100 where the pair is gated out; gated (rows x n_cand).
+ * No rows or no candidates are valid calls.  Two calls on the same arguments return the same bytes. */
+eao_status eao_plane_map_associate(eao_plane_map* pm, int32_t n_sets, const float* M /* n_sets*16 */, const int32_t* set_start /* n_sets+1 */,
+                                   const float* coef /* rows*4 */, int32_t n_cand, const uint64_t* cand_id, float dis_th, float angle_th, int32_t* match,
+                                   float* match_dis, float* world_coef, float* dis, uint8_t* gated);
 
 /* The value of EAO_ABI_VERSION the library was built with. Bumped whenever an entry point's parameter list or a struct's layout changes (round 3
  * changed eao_tracker_track_local_map and eao_track_result in place); a caller compiled against another version must not call into the library.

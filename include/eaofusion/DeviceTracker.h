@@ -164,7 +164,8 @@ public:
     // Round 5: (a) a search that returns fewer than minMatches (upstream's 20, :1756 / :1762) is NOT followed by the pose optimisation and the discard -- the call
     // returns the search's count right away and has touched no map point and no pose, exactly as upstream at that point; the caller repeats it with 2 * th or
     // returns false.  (b) The planes the caller associated with the predicted pose (Map::AssociatePlanesByBoundary, :2181 -- it reads the pose, not the matches)
-    // are edges of the chained optimisation; mvbPlaneOutlier comes back, the plane discard loop (:2210-2221) stays with the caller.
+    // are edges of the chained optimisation; mvbPlaneOutlier comes back, the plane discard loop (:2210-2221) stays with the caller.  (The association itself is a
+    // library call too: include/eaofusion/MapPlanes.h over eao_plane_map_*, the boundary clouds resident on the device.)
     template <class FrameT>
     int TrackWithMotionModel(FrameT& Cur, const FrameT& Last, const eao_keypoint* d_kps, const uint8_t* d_desc, const int32_t* d_n, const float* d_depth,
                              int depthPitch, int width, int height, float th, bool bMono, void* stream, int* nmatchesMap = nullptr, int* nSearch = nullptr,
@@ -233,7 +234,8 @@ public:
     // Optimizer::PoseOptimization(&Cur) and the "Discard outliers" loop, one copy back.  The caller has run Cur.ComputeBoW() (:1571: DBoW2 works on the host
     // copy of the descriptors) and passes the last frame's pose.  Returns nmatchesMap (:1630 compares it with 10); nSearch = SearchByBoW's return value (:1580
     // compares it with 10 -- below it the caller takes upstream's "return false" and ignores what this call filled in).  As with TrackWithMotionModel, what this
-    // fork does between the search and the optimisation (AssociatePlanesByBoundary, :1587) sees Cur.mvpMapPoints only after the call.
+    // fork does between the search and the optimisation (AssociatePlanesByBoundary, :1587) sees Cur.mvpMapPoints only after the call.  (It does not read them: it
+    // runs in front of this call, on the host or through include/eaofusion/MapPlanes.h.)
     template <class KeyFrameT, class FrameT>
     int TrackReferenceKeyFrame(FrameT& Cur, KeyFrameT* pRefKF, const cv::Mat& lastTcw, const eao_keypoint* d_kps, const uint8_t* d_desc, const int32_t* d_n,
                                const float* d_depth, int depthPitch, int width, int height, void* stream, int* nSearch = nullptr, float nnratio = 0.7f,
@@ -298,7 +300,8 @@ public:
 private:
     // The one-shot options of the next chain call (eao_tracker_set_options, round 5): the frame's associated map planes -- in this fork
     // Map::AssociatePlanesByBoundary runs BEFORE Optimizer::PoseOptimization in every stage (src/Tracking.cc:1587, :2181, TrackLocalMap), so they are edges of
-    // the optimisation (src/Optimizer.cc:456-535); the caller has associated them with the pose the stage starts from -- and the stage's match threshold.
+    // the optimisation (src/Optimizer.cc:456-535); the caller has associated them with the pose the stage starts from (upstream's loop, or
+    // include/eaofusion/MapPlanes.h: the same association over boundary clouds resident on the device) -- and the stage's match threshold.
     template <class FrameT>
     void set_options(FrameT& F, int minMatches, PlaneEdges& pe, std::vector<uint8_t>& pout) {
         collect_planes(&F, pe);
