@@ -789,6 +789,172 @@ __global__ __launch_bounds__(256) void k_blur7(const Geom* __restrict__ g, ImgSr
     else blur_strip<0>(src, pitch, dst, L.pitch, x4, y0, L.w, L.h);
 }
 
+// ---------------------------------------------------------------------------------------------- blur on the matrix cores
+// The same blur as two exact int8 matrix products per 32 x 32 output tile (v_mfma_i32_32x32x32_i8, i32 accumulation): out = Ty . P . Tx with the banded
+// tap matrices of orb_blur_tables.h, reflect-101 folded into the tables of the edge tiles.  Between the two products nothing leaves the registers:
+//   stage 1   X[source row][out x] = (P ^ 0x80) . Tx.  The pixel rows are the FIRST operand (lane = source row, 16 consecutive bytes of it per K step), Tx the
+//             second, so a lane holds sixteen source rows of ONE output column: register j <-> row (j & 3) + 8 (j >> 2) + 4 (lane >> 5).
+//             Every real column of Tx sums to 257, so X = H - 32896 with H the unsigned 16-bit horizontal sum, and X + 128 is an int16: its high byte is signed as
+//             it stands, its low byte becomes signed with ^ 0x80.  v_perm gathers the two bytes of four registers, packed in register order = fragment byte order.
+//   stage 2   two chains over the source blocks b - 1, b, b + 1: acc_hi = X_hi^T . Ty, acc_lo = X_lo^T . Ty + 257 (32768 + 128) + 32768.  The packed X is
+//             the FIRST operand again (lane = out x), Ty the second (lane = out y), so a lane ends with four consecutive x of one output row per register
+//             group: v = (acc_hi << 8) + acc_lo, out = min(v >> 16, 255); two half-wave exchanges make them one 16-byte store per lane.
+// The constant sits in the C input of the first instruction of the low chain.  A wave owns a 32-pixel column strip and walks up to kBlurMSeg blocks down it: each block's X
+// is computed once and kept packed for the three output blocks that use it.
+// Per 32 x 32 tile, interior of a walk (the gfx950 object, tools/isa_census.py): 8 v_mfma_i32_32x32x32_i8 and 82 VALU instructions (28 v_perm, 17 v_lshl_add, 8 v_xor,
+// 8 v_pk_add_u16, 8 v_pk_min_u16, 2 v_permlane32_swap, 11 of address arithmetic and masks) against 320 of k_blur7; two 16-byte loads, two LDS writes and reads,
+// one 16-byte store.  A walk adds one block of stage 1 (26 VALU, 2 MFMA) at either end.  122 VGPRs, 10 KB of LDS: four waves per SIMD.
+typedef int bm_v4i __attribute__((ext_vector_type(4)));
+typedef int bm_v16i __attribute__((ext_vector_type(16)));
+typedef bm_v4i bm_v4i_a4 __attribute__((aligned(4)));
+struct BlurMPacked { bm_v4i hi, lo; };
+
+// The source rows of a block reach the first operand THROUGH LDS: loaded as the operand wants them (lane = row, 16 bytes of it) a load instruction touches 64
+// separate 16-byte pieces of 32 cache lines, and the blur was bound by that; loaded four lanes to a row (64 contiguous bytes, sixteen rows per instruction) it
+// touches a quarter of them.  The wave parks the block in its own 32 x 64 byte LDS image (80-byte row pitch) and reads its fragments back from there.
+constexpr int kBlurMLdsPitch = 80;
+__device__ __forceinline__ void blur_m_load(const uint8_t* __restrict__ src, int pitch, int h, int blk, unsigned ws, int lane, bm_v4i raw[2]) {
+#pragma unroll
+    for (int k = 0; k < 2; k++) {
+        // (rows beyond the image carry zero weights in Ty: any row that may be read serves)
+        const int y = min(max(kBlurMTile * blk + 16 * k + (lane >> 2), 0), h - 1);
+        raw[k] = *reinterpret_cast<const bm_v4i_a4*>(src + (unsigned)(__umul24(y, pitch) + ws + 16 * (lane & 3)));
+    }
+}
+
+__device__ __forceinline__ BlurMPacked blur_m_stage1(const bm_v4i raw[2], uint8_t* stage, int lane, bm_v4i tx0, bm_v4i tx1) {
+    const bm_v4i bias = {(int)0x80808080u, (int)0x80808080u, (int)0x80808080u, (int)0x80808080u};
+    bm_v16i z;
+#pragma unroll
+    for (int q = 0; q < 16; q++) z[q] = 0;
+    // (one wave, LDS operations in order: the previous block's fragment reads are done before these writes land)
+    eao::wave_sync();
+#pragma unroll
+    for (int k = 0; k < 2; k++) *reinterpret_cast<bm_v4i*>(stage + (16 * k + (lane >> 2)) * kBlurMLdsPitch + 16 * (lane & 3)) = raw[k] ^ bias;
+    eao::wave_sync();
+    const uint8_t* fr = stage + (lane & 31) * kBlurMLdsPitch + 16 * (lane >> 5);
+    const bm_v4i a0 = *reinterpret_cast<const bm_v4i*>(fr), a1 = *reinterpret_cast<const bm_v4i*>(fr + 32);
+    bm_v16i X = __builtin_amdgcn_mfma_i32_32x32x32_i8(a0, tx0, z, 0, 0, 0);
+    X = __builtin_amdgcn_mfma_i32_32x32x32_i8(a1, tx1, X, 0, 0, 0);
+    // X = H - 32896.  X + 128 is an int16 = 256 hi + ul with hi its (signed) high byte; the low operand is ul - 128, whose bit pattern ul ^ 0x80 is the low
+    // byte of X + 256, that is of X itself: the low bytes are taken before the + 128 (two 16-bit lanes at a time), the high bytes after it.
+    BlurMPacked P;
+    const u16x2 k128 = {128, 128};
+#pragma unroll
+    for (int q = 0; q < 4; q++) {
+        const unsigned t = __builtin_amdgcn_perm((unsigned)X[4 * q + 1], (unsigned)X[4 * q], 0x05040100u);       // [a.0 a.1 b.0 b.1]
+        const unsigned w = __builtin_amdgcn_perm((unsigned)X[4 * q + 3], (unsigned)X[4 * q + 2], 0x05040100u);
+        P.lo[q] = (int)__builtin_amdgcn_perm(w, t, 0x06040200u);
+        const unsigned t2 = __builtin_bit_cast(unsigned, __builtin_bit_cast(u16x2, t) + k128), w2 = __builtin_bit_cast(unsigned, __builtin_bit_cast(u16x2, w) + k128);
+        P.hi[q] = (int)__builtin_amdgcn_perm(w2, t2, 0x07050301u);
+    }
+    return P;
+}
+
+__device__ __forceinline__ void blur_m_stage2(const BlurMPacked& Pm, const BlurMPacked& Pc, const BlurMPacked& Pn, const bm_v4i ty[3], int lane,
+                                              uint8_t* __restrict__ dst, int dpitch, int x0, int b, int h, const bm_v16i& c) {
+    bm_v16i z;
+#pragma unroll
+    for (int q = 0; q < 16; q++) z[q] = 0;
+    bm_v16i ah = __builtin_amdgcn_mfma_i32_32x32x32_i8(Pm.hi, ty[0], z, 0, 0, 0);
+    bm_v16i al = __builtin_amdgcn_mfma_i32_32x32x32_i8(Pm.lo, ty[0], c, 0, 0, 0);
+    ah = __builtin_amdgcn_mfma_i32_32x32x32_i8(Pc.hi, ty[1], ah, 0, 0, 0);
+    al = __builtin_amdgcn_mfma_i32_32x32x32_i8(Pc.lo, ty[1], al, 0, 0, 0);
+    ah = __builtin_amdgcn_mfma_i32_32x32x32_i8(Pn.hi, ty[2], ah, 0, 0, 0);
+    al = __builtin_amdgcn_mfma_i32_32x32x32_i8(Pn.lo, ty[2], al, 0, 0, 0);
+    unsigned o[4];      // o[q]: x0 + 8 q + 4 (lane >> 5) .. + 3 of row lane & 31
+#pragma unroll
+    for (int q = 0; q < 4; q++) {
+        unsigned sv[4];
+#pragma unroll
+        for (int e = 0; e < 4; e++) sv[e] = ((unsigned)ah[4 * q + e] << 8) + (unsigned)al[4 * q + e];
+        const u16x2 lim = {255, 255};
+        const u16x2 pa = __builtin_elementwise_min(__builtin_bit_cast(u16x2, __builtin_amdgcn_perm(sv[1], sv[0], 0x07060302u)), lim);
+        const u16x2 pb = __builtin_elementwise_min(__builtin_bit_cast(u16x2, __builtin_amdgcn_perm(sv[3], sv[2], 0x07060302u)), lim);
+        o[q] = __builtin_amdgcn_perm(__builtin_bit_cast(unsigned, pb), __builtin_bit_cast(unsigned, pa), 0x06040200u);
+    }
+    // A row is split over the two halves of the wave in 4-byte pieces.  Two half exchanges (v_permlane32_swap: lanes 32-63 of the first register
+    // <-> lanes 0-31 of the second) give the lower half x0 .. x0 + 15 and the upper half x0 + 16 .. x0 + 31: ONE 16-byte store per lane, 32
+    // contiguous bytes per row, instead of four 4-byte stores.
+    const auto s02 = __builtin_amdgcn_permlane32_swap(o[0], o[2], false, false);
+    const auto s13 = __builtin_amdgcn_permlane32_swap(o[1], o[3], false, false);
+    const int y = kBlurMTile * b + (lane & 31);
+    // (the blur buffer pads its levels to 16 rows, a block has 32: rows below the image are not stored.  Columns beyond the row land in the pitch padding:
+    //  the pitch is a multiple of 64)
+    if (y < h) *reinterpret_cast<uint4*>(dst + (unsigned)(__umul24(y, dpitch) + x0 + 16 * (lane >> 5))) = make_uint4(s02[0], s02[1], s13[0], s13[1]);
+}
+
+// One launch over all levels, like k_blur7; a level that cannot take the matrix path (narrower or lower than the 64-byte source window, or level 0 of a
+// caller whose image is not 4-byte aligned) runs the VALU strips inside the same launch: its share of the grid covers either form.
+__global__ __launch_bounds__(256, 4) void k_blur7_mfma(const Geom* __restrict__ g, ImgSrc s, uint8_t* __restrict__ blur, const uint8_t* __restrict__ tab, int f0,
+                                                    int src0Aligned, int frameAffinity) {
+    int f = blockIdx.y, bxi = blockIdx.x;
+    if (frameAffinity) {
+        const unsigned b = blockIdx.x + gridDim.x * blockIdx.y, xcd = b & 7, slot = b >> 3;
+        f = (int)(xcd + 8 * (slot / gridDim.x)); bxi = (int)(slot % gridDim.x);
+    }
+    f += f0;
+    int l = 0;
+    while (l + 1 < g->nlevels && bxi >= g->L[l + 1].mTileBase) l++;
+    const LevelGeom L = g->L[l];
+    int pitch;
+    const uint8_t* src = level_ptr(g, s, l, f, &pitch);
+    uint8_t* dst = blur + (long long)f * g->pyrFrameBytes + L.off;
+    if (!L.mOk || (l == 0 && !src0Aligned)) {
+        const int lane = threadIdx.x & 31;
+        const int strip = (bxi - L.mTileBase) * kBlurStripsPerWg + (int)(threadIdx.x >> 5);
+        const int x4 = (strip % L.tilesX) * kBlurSegW + lane * 4;
+        const int y0 = (strip / L.tilesX) * kBlurRows;
+        if (x4 >= L.w || y0 >= L.h) return;
+        if (l == 0 && !src0Aligned) blur_strip<2>(src, pitch, dst, L.pitch, x4, y0, L.w, L.h);
+        else if (__any(x4 < 4 || x4 + 7 > L.w)) blur_strip<1>(src, pitch, dst, L.pitch, x4, y0, L.w, L.h);
+        else blur_strip<0>(src, pitch, dst, L.pitch, x4, y0, L.w, L.h);
+        return;
+    }
+    const int lane = threadIdx.x & 63;
+    const int task = __builtin_amdgcn_readfirstlane((bxi - L.mTileBase) * 4 + (int)(threadIdx.x >> 6));
+    int walkLen;
+    blur_m_walks(L.mBlocksY, &walkLen);
+    const int cx = task % L.mTilesX, b0 = (task / L.mTilesX) * walkLen;
+    if (b0 >= L.mBlocksY) return;
+    const int b1 = min(b0 + walkLen, L.mBlocksY);
+    const int2* idx = reinterpret_cast<const int2*>(tab);
+    const uint8_t* frag = tab + g->mFragOff;
+    const int2 xi = idx[L.mXIdx + cx];      // (window start, Tx)
+    const bm_v4i tx0 = *reinterpret_cast<const bm_v4i*>(frag + xi.y + lane * 16), tx1 = *reinterpret_cast<const bm_v4i*>(frag + xi.y + kBlurMFrag + lane * 16);
+    const unsigned ws = (unsigned)xi.x;
+    __shared__ __attribute__((aligned(16))) uint8_t sStage[4][kBlurMTile * kBlurMLdsPitch];
+    uint8_t* stage = sStage[threadIdx.x >> 6];
+    // The constant C input of the low chain lives in registers of its own for the whole walk: the instruction's C input need not be its destination, so no
+    // tile spends sixteen moves on re-creating it.  (The empty asm keeps the compiler from re-materialising the block next to every use.)
+    bm_v16i c2;
+#pragma unroll
+    for (int q = 0; q < 16; q++) c2[q] = 257 * (32768 + 128) + 32768;
+    asm volatile("" : "+v"(c2));
+    bm_v4i raw[2], ty[3];
+    int tyOff = -1;      // (the interior blocks of every level share one Ty: it stays in registers down the walk)
+    BlurMPacked P[3];
+    P[0].hi = P[0].lo = bm_v4i{0, 0, 0, 0};      // (block b0 - 1 of the top segment does not exist: zero weights)
+    if (b0 > 0) { blur_m_load(src, pitch, L.h, b0 - 1, ws, lane, raw); P[0] = blur_m_stage1(raw, stage, lane, tx0, tx1); }
+    blur_m_load(src, pitch, L.h, b0, ws, lane, raw);
+    P[1] = blur_m_stage1(raw, stage, lane, tx0, tx1);
+    blur_m_load(src, pitch, L.h, b0 + 1, ws, lane, raw);
+#pragma unroll
+    for (int i = 0; i < kBlurMSeg; i++) {
+        const int b = b0 + i;
+        if (b >= b1) break;
+        P[(i + 2) % 3] = blur_m_stage1(raw, stage, lane, tx0, tx1);
+        if (b + 1 < b1) blur_m_load(src, pitch, L.h, b + 2, ws, lane, raw);      // (in flight during the second stage)
+        const int yo = idx[L.mYIdx + b].y;
+        if (yo != tyOff) {
+            tyOff = yo;
+#pragma unroll
+            for (int k = 0; k < 3; k++) ty[k] = *reinterpret_cast<const bm_v4i*>(frag + yo + k * kBlurMFrag + lane * 16);
+        }
+        blur_m_stage2(P[i % 3], P[(i + 1) % 3], P[(i + 2) % 3], ty, lane, dst, L.pitch, kBlurMTile * cx, b, L.h, c2);
+    }
+}
+
 // Sum over the 32 lanes of each half-wave on the VALU, both halves at once (DPP: two quad permutes, half-row and row mirrors, then
 // row_bcast15 into rows 1 and 3, whose lanes then hold the sums of their halves); the two totals are read from lanes 31 and 63 into
 // SGPRs and every lane takes the one of its half: five v_add with DPP + two v_readlane + one v_cndmask.
@@ -1161,6 +1327,9 @@ __global__ __launch_bounds__(256) void k_stereo_match(const Geom* __restrict__ g
 namespace eao {
 namespace orb {
 
+// EAO_ORB_BLUR_MFMA: 1 (default) = the blur on the matrix cores wherever a level can take it, 0 = the VALU kernel only (A/B runs; no result changes).  Read once.
+static int blur_mfma_mode() { static const int mode = [] { const char* e = getenv("EAO_ORB_BLUR_MFMA"); return e ? atoi(e) : 1; }(); return mode; }
+
 // Enqueue the whole pipeline for `batch` frames on the caller's stream `st`; level 0 is read from `d_img` (device memory).
 // The main chain runs on `st` itself -- no hand-over to a private stream and back, which put two cross-stream event hops (~25 us on
 // PyTorch's bundled HIP 7.0 runtime) between consecutive calls -- and the handle's side stream takes the work that runs beside it.
@@ -1239,7 +1408,12 @@ eao_status enqueue(eao_orb* h, const uint8_t* d_img, int pitch0, long long fs0, 
     auto blur = [&]() -> eao_status {
         EAO_HIP(hipStreamWaitEvent(ss, h->evFork, 0));
         if (prof) EAO_HIP(hipEventRecord(ev[6], ss));
-        { eao::Range rg("orb: blur"); hipLaunchKernelGGL(k_blur7, dim3(g.totalTiles, batch), dim3(256), 0, ss, h->d_geom.p, s, h->d_blur.p, 0, src0Aligned, aff); }
+        {
+            eao::Range rg("orb: blur");
+            if (g.mTotalTiles && blur_mfma_mode())
+                hipLaunchKernelGGL(k_blur7_mfma, dim3(g.mTotalTiles, batch), dim3(256), 0, ss, h->d_geom.p, s, h->d_blur.p, h->d_blurTab.p, 0, src0Aligned, aff);
+            else hipLaunchKernelGGL(k_blur7, dim3(g.totalTiles, batch), dim3(256), 0, ss, h->d_geom.p, s, h->d_blur.p, 0, src0Aligned, aff);
+        }
         if (prof) EAO_HIP(hipEventRecord(ev[7], ss));
         EAO_HIP(hipEventRecord(h->evJoin, ss));
         return EAO_OK;

@@ -206,6 +206,35 @@ eao_status build_geometry(eao_orb* h, int W, int H) {
         for (int i = 0; i < 7; i++)
             if (cv_round((double)(float)(cf[i] * (1. / sum)) * 256.0) != expect[i]) { eao::set_error("gaussian taps mismatch"); return EAO_ERR_INTERNAL; }
     }
+    // the matrix-core blur: operand tables and tiling of this geometry (orb_blur_tables.h).  Level 0 is the caller's image: rows may be read up to the
+    // next multiple of 4 only (and only when the call's image is 4-byte aligned -- the kernel decides that per call); the pyramid's rows up to their pitch.
+    {
+        std::vector<BlurMLevelIn> in;
+        for (int l = 0; l < c.nlevels; l++) in.push_back({g.L[l].w, g.L[l].h, l == 0 ? (g.L[l].w + 3) & ~3 : g.L[l].pitch});
+        const BlurMTables T = blur_m_build(in);
+        EAO_REQUIRE(T.maxEntry <= 127, "blur table entry %d does not fit int8", T.maxEntry);
+        int mBase = 0, any = 0;
+        for (int l = 0; l < c.nlevels; l++) {
+            LevelGeom& L = g.L[l];
+            const BlurMLevel& M = T.level[l];
+            L.mOk = M.ok; L.mTilesX = M.tilesX; L.mBlocksY = M.blocksY; L.mXIdx = M.xIdx; L.mYIdx = M.yIdx;
+            const int valu = eao::cdiv(L.tilesX * eao::cdiv(L.h, kBlurRows), kBlurStripsPerWg);
+            int walkLen;
+            const int mfma = eao::cdiv(M.tilesX * blur_m_walks(M.blocksY, &walkLen), 4);
+            L.mTileBase = mBase;
+            mBase += !M.ok ? valu : l == 0 ? std::max(valu, mfma) : mfma;      // (level 0 may take either form, call by call)
+            any |= M.ok;
+        }
+        g.mTotalTiles = any ? mBase : 0;
+        g.mFragOff = (int)((T.idx.size() * sizeof(int) + kBlurMFrag - 1) / kBlurMFrag * kBlurMFrag);
+        if (any) {
+            std::vector<uint8_t> blob((size_t)g.mFragOff + T.frag.size(), 0);
+            std::memcpy(blob.data(), T.idx.data(), T.idx.size() * sizeof(int));
+            std::memcpy(blob.data() + g.mFragOff, T.frag.data(), T.frag.size());
+            { eao_status st = h->d_blurTab.reserve(blob.size()); if (st) return st; }
+            EAO_HIP(hipMemcpy(h->d_blurTab.p, blob.data(), blob.size(), hipMemcpyHostToDevice));
+        }
+    }
     { eao_status st = h->d_geom.reserve(1); if (st) return st; }
     EAO_HIP(hipMemcpyAsync(h->d_geom.p, &g, sizeof(Geom), hipMemcpyHostToDevice, h->stream));
     { eao_status st = h->d_cells.reserve(h->cells.size()); if (st) return st; }

@@ -13,6 +13,7 @@
 #include <vector>
 
 #include "common.h"
+#include "orb_blur_tables.h"
 
 
 namespace eao {
@@ -38,6 +39,9 @@ struct LevelGeom {
     int kpBase;                // first keypoint slot of this level inside a frame
     int candBase, candCap;     // candidate scratch of this level inside a frame
     int tileBase, tilesX;      // blur: first workgroup of this level, 128-px strips per row of strips
+    int mOk, mTileBase;        // matrix-core blur (k_blur7_mfma): the level takes it; first workgroup of this level in that launch
+    int mTilesX, mBlocksY;     // ... 32-px column strips, 32-row blocks
+    int mXIdx, mYIdx;          // ... first (window start, Tx offset) / (0, Ty offset) pair of the level in the table index
     long long nodeOff;         // k_quadtree, global node lists: byte offset of this level inside a frame's workspace
     int scaledPatch;
     float scale;
@@ -47,6 +51,7 @@ struct Geom {
     int nlevels, W, H;
     int totalCells, cellCap;
     int totalKpCap, totalCandCap, totalTiles;
+    int mTotalTiles, mFragOff; // k_blur7_mfma: workgroups per frame (0: no level takes it), byte offset of the operand tables behind the index
     int pyrFrameBytes;
     int iniTh, minTh;
     int scanCap;               // LDS scan workspace entries for k_quadtree
@@ -178,6 +183,7 @@ struct eao_orb {
     eao::DevBuf<Geom> d_geom;
     eao::DevBuf<CellDesc> d_cells;
     eao::DevBuf<uint8_t> d_pyr, d_blur, d_in;
+    eao::DevBuf<uint8_t> d_blurTab;        // k_blur7_mfma: table index + operand tables of this geometry (orb_blur_tables.h)
     eao::DevBuf<unsigned> d_cellcand, d_cand, d_levelkps;
     eao::DevBuf<unsigned short> d_nodeof;
     eao::DevBuf<unsigned char> d_qtnodes;   // global node lists (only when they do not fit in LDS)

@@ -41,6 +41,11 @@ def sha16(rel):
 
 SRC = {rel: sha16(rel) for rel in ("eao_fusion_amd/csrc/orb.hip", "eao_fusion_amd/csrc/orb_internal.h", "eao_fusion_amd/csrc/hamming.hip", "eao_fusion_amd/csrc/lm_internal.h", "eao_fusion_amd/csrc/lba.hip", "eao_fusion_amd/csrc/gba.hip", "eao_fusion_amd/csrc/lm_host.hip")}      # what bench.py checks before it derives anything
 a, b, h = load(R + "_sq_a"), load(R + "_sq_b"), load(R + "_sq_h")
+c = load(R + "_sq_c")                                    # the matrix pipe of the blur (SQ_VALU_MFMA_BUSY_CYCLES), a pass of its own
+blur_kernel = "k_blur7_mfma" if "k_blur7_mfma" in a else "k_blur7"
+for t in (a, b, c):                                    # the blur stage is k_blur7_mfma unless EAO_ORB_BLUR_MFMA=0: one row, named k_blur7, that says which kernel ran
+    if "k_blur7_mfma" in t:
+        t["k_blur7"] = dict(t.pop("k_blur7_mfma"))
 fe, wr = load(R + "_fetch"), load(R + "_write")
 batch = int(os.environ.get("EAO_PMC_BATCH", "64"))
 steps = a.get("k_blur7", {}).get("launches", 1)         # one blur launch per bench step (timed and profiled alike)
@@ -61,30 +66,34 @@ for name, row in stage.items():
         d.update({k: v for k, v in rb.items() if k != "launches"})
     # launches per bench step (k_fast_cells<true>: one per PROFILED step, which is where its duration is measured)
     d["launches_per_step"] = 1 if name == "k_fast_cells" else round(ra["launches"] / steps, 2)
+    if name == "k_blur7":
+        d.update({k: v for k, v in (pick(c) or {}).items() if k == "SQ_VALU_MFMA_BUSY_CYCLES"})
+        d["kernel"] = blur_kernel
     sq["kernels"][name] = d
 for k, v in h.items():
     if k.startswith("k_hamming"):
         sq["kernels_extra"][k.split("<")[0]] = {c: x for c, x in v.items()}
 json.dump(sq, open(os.path.join(O, R + "_pmc_sq.json"), "w"), indent=1)
 cols = ["SQ_WAVES", "SQ_INSTS_VALU", "SQ_ACTIVE_INST_VALU", "SQ_BUSY_CYCLES", "SQ_WAVE_CYCLES", "SQ_INSTS_LDS", "SQ_ACTIVE_INST_LDS", "SQ_WAIT_INST_LDS",
-        "SQ_LDS_BANK_CONFLICT", "SQ_LDS_IDX_ACTIVE", "SQ_WAIT_ANY", "SQ_WAIT_INST_ANY", "SQ_ACTIVE_INST_ANY", "SQ_INSTS_SALU", "SQ_INSTS_VMEM_RD", "SQ_INSTS_VMEM_WR"]
+        "SQ_LDS_BANK_CONFLICT", "SQ_LDS_IDX_ACTIVE", "SQ_WAIT_ANY", "SQ_WAIT_INST_ANY", "SQ_ACTIVE_INST_ANY", "SQ_INSTS_SALU", "SQ_INSTS_VMEM_RD", "SQ_INSTS_VMEM_WR",
+        "SQ_VALU_MFMA_BUSY_CYCLES"]
 with open(os.path.join(O, R + "_pmc_sq.txt"), "w") as f:
     f.write("# SQ counters per launch, 64-frame batch (tools/prof_round.sh)\n")
     f.write("kernel".ljust(22) + "".join(c.replace("SQ_", "").rjust(17) for c in cols) + "\n")
     for k, d in list(sq["kernels"].items()) + list(sq["kernels_extra"].items()):
-        f.write(k[:22].ljust(22) + "".join(("%.4g" % d[c]).rjust(17) if c in d else "-".rjust(17) for c in cols) + "\n")
+        f.write(k[:22].ljust(22) + "".join(("%.4g" % d[q]).rjust(17) if q in d else "-".rjust(17) for q in cols) + "\n")
 print(open(os.path.join(O, R + "_pmc_sq.txt")).read())
 # traffic
 tr = {"_note": "rocprofv3 --kernel-trace --pmc FETCH_SIZE / --pmc WRITE_SIZE (two separate passes) -- python3 bench.py --steps 3 --warmup 1 --full --no-cpu-baseline "
                "--no-extra; bytes = KiB counter x 1024, RAW counters.  MI355X_MICROARCH.md (HBM): FETCH_SIZE reports half the bytes of a streaming read on gfx950 "
-               "-- bench.py doubles it; self-check: k_blur7 reads 22/16 x 60.8 MB = 83.6 MB (16-row strips + 6 halo rows), 2 x FETCH_SIZE counted below.",
+               "-- bench.py doubles it; self-check: the blur reads every level once plus the halo of its tiling (k_blur7: 22/16 x 60.8 MB = 83.6 MB), 2 x FETCH_SIZE counted below.",
       "batch": batch, "source_sha16": SRC, "kernels": {}}
 names = {"pyramid": "k_resize", "fast": "k_fast_cells", "blur": "k_blur7", "quadtree": "k_quadtree", "orient_describe": "k_orient_describe"}
 for st, kn in names.items():
     f_tot = sum(v["FETCH_SIZE"] * v["launches"] for k, v in fe.items() if k.startswith(kn) and "FETCH_SIZE" in v) * 1024
     w_tot = sum(v["WRITE_SIZE"] * v["launches"] for k, v in wr.items() if k.startswith(kn) and "WRITE_SIZE" in v) * 1024
     nl = sum(v["launches"] for k, v in fe.items() if k.startswith(kn))
-    tr["kernels"][st] = {"kernel": kn, "launches_per_step": round(nl / steps, 2), "fetch_bytes_per_step": int(f_tot / steps), "write_bytes_per_step": int(w_tot / steps),
+    tr["kernels"][st] = {"kernel": blur_kernel if st == "blur" else kn, "launches_per_step": round(nl / steps, 2), "fetch_bytes_per_step": int(f_tot / steps), "write_bytes_per_step": int(w_tot / steps),
                          "hbm_bytes_per_step_corrected": int((2 * f_tot + w_tot) / steps)}
 json.dump(tr, open(os.path.join(O, R + "_pmc_traffic.json"), "w"), indent=1)
 print(json.dumps(tr["kernels"], indent=1))
