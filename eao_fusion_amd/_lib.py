@@ -168,6 +168,19 @@ class KeyFrameDbScored(C.Structure):   # eao_keyframe_db_scored
                 ("n_scored", C.c_int32), ("scored_id", C.c_void_p), ("scored_score", C.c_void_p)]
 
 
+class PlaneSegCfg(C.Structure):   # eao_plane_seg_cfg
+    _fields_ = [("width", C.c_int32), ("height", C.c_int32), ("fx", C.c_float), ("fy", C.c_float), ("cx", C.c_float), ("cy", C.c_float),
+                ("window", C.c_int32), ("min_support", C.c_int32), ("max_step", C.c_int32), ("leaf", C.c_float),
+                ("depth_min", C.c_double), ("depth_max", C.c_double), ("depth_sigma", C.c_double), ("std_tol_init", C.c_double), ("std_tol_merge", C.c_double),
+                ("z_near", C.c_double), ("z_far", C.c_double), ("angle_near", C.c_double), ("angle_far", C.c_double),
+                ("similarity_merge", C.c_double), ("similarity_refine", C.c_double), ("depth_alpha", C.c_double), ("depth_change_tol", C.c_double)]
+
+
+class PlaneSegPlane(C.Structure):   # eao_plane_seg_plane
+    _fields_ = [("normal", C.c_double * 3), ("center", C.c_double * 3), ("mse", C.c_double), ("curvature", C.c_double), ("N", C.c_int32), ("rid", C.c_int32),
+                ("coef", C.c_float * 4), ("kept", C.c_int32), ("cloud_offset", C.c_int32), ("cloud_count", C.c_int32), ("n_pixels", C.c_int32)]
+
+
 # every symbol include/eao_fusion.h declares: (restype, argtypes)
 _P = C.c_void_p
 _I = C.c_int32
@@ -266,6 +279,20 @@ SYMBOLS = {
     "eao_plane_map_erase": (_I, [_P, C.c_uint64]),
     "eao_plane_map_boundary": (_I, [_P, C.c_uint64, _I, _P, C.POINTER(_I), _P]),
     "eao_plane_map_associate": (_I, [_P, _I, _P, _P, _P, _I, _P, C.c_float, C.c_float, _P, _P, _P, _P, _P]),
+    "eao_plane_seg_cfg_default": (None, [C.POINTER(PlaneSegCfg), _I, _I, C.c_float, C.c_float, C.c_float, C.c_float]),
+    "eao_plane_seg_create": (_I, [C.POINTER(PlaneSegCfg), C.POINTER(_P)]),
+    "eao_plane_seg_destroy": (None, [_P]),
+    "eao_plane_seg_run": (_I, [_P, _P, _I]),
+    "eao_plane_seg_set_profiling": (_I, [_P, _I]),
+    "eao_plane_seg_last_timing": (_I, [_P, _P]),
+    "eao_plane_seg_info": (_I, [_P, C.POINTER(_I), C.POINTER(_I), C.POINTER(_I), C.POINTER(_I)]),
+    "eao_plane_seg_planes": (_I, [_P, _I, _P, C.POINTER(_I)]),
+    "eao_plane_seg_cloud": (_I, [_P, _I, _I, _P, C.POINTER(_I)]),
+    "eao_plane_seg_membership": (_I, [_P, _P]),
+    "eao_plane_seg_blocks": (_I, [_P, _I, _P, C.POINTER(_I)]),
+    "eao_plane_seg_middle": (_I, [_P, _P, _I, _P, C.POINTER(_I), _I, _P, C.POINTER(_I)]),
+    "eao_plane_map_add_from_seg": (_I, [_P, C.c_uint64, _P, _P, _I, _P]),
+    "eao_plane_map_update_boundary_from_seg": (_I, [_P, C.c_uint64, _P, _I, _P]),
     "eao_bundle_adjustment_plan": (_I, [_I, _I, _P, _P, _I, _P, _P, _P, _I, _P, _I, _P, _I, _P, _I, _P, _I, _P, _I]),
 }
 

@@ -21,6 +21,7 @@
 
 #include "lm_internal.h"      // se3_from_Tcw_f32, quat_to_matrix: Converter::toSE3Quat and the isometry it becomes
 #include "plane_map_internal.h"
+#include "plane_seg_shared.h"      // plane_seg_kept_cloud: the *_from_seg entry points
 
 namespace pmap = eao::pmap;
 static_assert(pmap::kMaxRows == EAO_PLANE_MAP_MAX_ROWS && pmap::kMaxPointsPerPlane == EAO_PLANE_MAP_MAX_POINTS &&
@@ -47,10 +48,11 @@ struct Xf {      // rows 0..2 of T.inverse().matrix(), double
     double m[12];
 };
 
-__global__ __launch_bounds__(256) void k_pm_transform(int n, const float* __restrict__ xyz, Xf X, int identity, float4* __restrict__ out) {
+// xyz: `stride` floats per point (3: the caller's packed points; 4: a segmentation handle's cloud)
+__global__ __launch_bounds__(256) void k_pm_transform(int n, const float* __restrict__ xyz, int stride, Xf X, int identity, float4* __restrict__ out) {
     const int i = blockIdx.x * 256 + threadIdx.x;
     if (i >= n) return;
-    const float x = xyz[3 * (size_t)i], y = xyz[3 * (size_t)i + 1], z = xyz[3 * (size_t)i + 2];
+    const float x = xyz[stride * (size_t)i], y = xyz[stride * (size_t)i + 1], z = xyz[stride * (size_t)i + 2];
     float4 o;
     if (identity) {
         o = make_float4(x, y, z, 0.0f);
@@ -232,7 +234,19 @@ Xf inverse_isometry(const float* Tcw) {
     return X;
 }
 
-// n points of the caller's into the arena at `begin` (reserved by the caller); the handle's mutex is held
+// n points in device memory, `stride` floats apart, through the transform into the arena at `begin` (reserved by the caller); the handle's mutex is held
+eao_status transform_into(eao_plane_map* pm, PmapCtx& ctx, uint64_t begin, int32_t n, const float* devXyz, int stride, const float* Tcw) {
+    Xf X = Xf();
+    if (Tcw) X = inverse_isometry(Tcw);
+    hipLaunchKernelGGL(k_pm_transform, dim3(eao::cdiv(n, 256)), dim3(256), 0, ctx.stream, n, devXyz, stride, X, Tcw ? 0 : 1, pm->pts + begin);
+    const hipError_t launchErr = hipGetLastError();
+    const hipError_t syncErr = hipStreamSynchronize(ctx.stream);
+    EAO_HIP(launchErr);
+    EAO_HIP(syncErr);
+    return EAO_OK;
+}
+
+// n points of the caller's into the arena at `begin`
 eao_status store_cloud(eao_plane_map* pm, PmapCtx& ctx, uint64_t begin, int32_t n, const float* xyz, const float* Tcw) {
     if (n == 0) return EAO_OK;
     const size_t bytes = (size_t)n * 12;
@@ -241,13 +255,30 @@ eao_status store_cloud(eao_plane_map* pm, PmapCtx& ctx, uint64_t begin, int32_t 
     if ((st = ctx.host.reserve(bytes))) return st;
     std::memcpy(ctx.host.p, xyz, bytes);
     EAO_HIP(hipMemcpyAsync(ctx.dev.p, ctx.host.p, bytes, hipMemcpyHostToDevice, ctx.stream));
-    Xf X = Xf();
-    if (Tcw) X = inverse_isometry(Tcw);
-    hipLaunchKernelGGL(k_pm_transform, dim3(eao::cdiv(n, 256)), dim3(256), 0, ctx.stream, n, (const float*)ctx.dev.p, X, Tcw ? 0 : 1, pm->pts + begin);
-    const hipError_t launchErr = hipGetLastError();
-    const hipError_t syncErr = hipStreamSynchronize(ctx.stream);
-    EAO_HIP(launchErr);
-    EAO_HIP(syncErr);
+    return transform_into(pm, ctx, begin, n, (const float*)ctx.dev.p, 3, Tcw);
+}
+
+// add (isAdd) or update_boundary from a segmentation handle's kept plane, device to device: the table logic of the host-pointer forms
+eao_status store_from_seg(eao_plane_map* pm, bool isAdd, uint64_t id, const float* world_pos, eao_plane_seg* seg, int32_t plane, const float* Tcw) {
+    std::lock_guard<std::mutex> lock(pm->mutex);
+    std::unique_lock<std::mutex> segLock;      // (always taken after the map's: nothing in plane_seg.hip takes a map's mutex)
+    const float* src = nullptr;
+    int32_t n = 0;
+    eao_status st = eao::plane_seg_kept_cloud(seg, plane, segLock, &src, &n);
+    if (st) return st;
+    const std::string err = pm->table.check_cloud(id, n, isAdd);
+    EAO_REQUIRE(err.empty(), "%s: %s", isAdd ? "eao_plane_map_add_from_seg" : "eao_plane_map_update_boundary_from_seg", err.c_str());
+    PmapCtx& ctx = g_pmap;
+    if ((st = ctx.ready(eao::StreamClass::Latency))) return st;
+    const uint64_t begin = pm->table.usedPoints;
+    if ((st = reserve_points(pm, begin + (uint64_t)n, ctx.stream))) return st;
+    if (n > 0 && (st = transform_into(pm, ctx, begin, n, src, 4, Tcw))) return st;
+    if (isAdd) {
+        pm->table.append(id, (uint32_t)n, world_pos);
+        return EAO_OK;
+    }
+    pm->table.replace(id, (uint32_t)n);
+    if (pm->table.wants_compaction()) return compact(pm, ctx.stream);
     return EAO_OK;
 }
 
@@ -312,6 +343,16 @@ eao_status eao_plane_map_update_boundary(eao_plane_map* pm, uint64_t id, int32_t
     pm->table.replace(id, (uint32_t)n);
     if (pm->table.wants_compaction()) return compact(pm, ctx.stream);
     return EAO_OK;
+}
+
+eao_status eao_plane_map_add_from_seg(eao_plane_map* pm, uint64_t id, const float* world_pos, eao_plane_seg* seg, int32_t plane, const float* Tcw) {
+    EAO_REQUIRE(pm && world_pos && seg, "bad argument");
+    return store_from_seg(pm, true, id, world_pos, seg, plane, Tcw);
+}
+
+eao_status eao_plane_map_update_boundary_from_seg(eao_plane_map* pm, uint64_t id, eao_plane_seg* seg, int32_t plane, const float* Tcw) {
+    EAO_REQUIRE(pm && seg, "bad argument");
+    return store_from_seg(pm, false, id, nullptr, seg, plane, Tcw);
 }
 
 eao_status eao_plane_map_set_world_pos(eao_plane_map* pm, uint64_t id, const float* world_pos) {

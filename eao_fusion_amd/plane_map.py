@@ -33,6 +33,15 @@ class PlaneMap:
         p, T = _f32(xyz, (-1, 3)), _f32(Tcw, 16)
         _lib.check(self._lib.eao_plane_map_update_boundary(self.h, int(plane_id), len(p), _lib.ptr(p), _lib.ptr(T)))
 
+    def add_from_seg(self, plane_id, world_pos, seg, plane, Tcw=None):
+        """add() with the cloud of kept plane `plane` of a plane_seg.PlaneSegmenter's last run, device to device"""
+        w, T = _f32(world_pos, 4), _f32(Tcw, 16)
+        _lib.check(self._lib.eao_plane_map_add_from_seg(self.h, int(plane_id), _lib.ptr(w), seg.h, int(plane), _lib.ptr(T)))
+
+    def update_boundary_from_seg(self, plane_id, seg, plane, Tcw=None):
+        T = _f32(Tcw, 16)
+        _lib.check(self._lib.eao_plane_map_update_boundary_from_seg(self.h, int(plane_id), seg.h, int(plane), _lib.ptr(T)))
+
     def set_world_pos(self, plane_id, world_pos):
         w = _f32(world_pos, 4)
         _lib.check(self._lib.eao_plane_map_set_world_pos(self.h, int(plane_id), _lib.ptr(w)))

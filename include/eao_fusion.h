@@ -1245,6 +1245,88 @@ eao_status eao_plane_map_associate(eao_plane_map* pm, int32_t n_sets, const floa
                                    const float* coef /* rows*4 */, int32_t n_cand, const uint64_t* cand_id, float dis_th, float angle_th, int32_t* match,
                                    float* match_dis, float* world_coef, float* dis, uint8_t* gated);
 
+/* ---- Plane segmentation: Frame::ComputePlanesFromPEAC (src/Frame.cc:381-460), called from the RGB-D constructor (:240) --------------------------------------
+ * The depth image becomes the organised cloud of src/Frame.cc:391-405, PEAC segments it (include/PEAC/AHCPlaneFitter.hpp run :209-258: initGraph :784-953,
+ * ahCluster :981-1187, refineDetails :297-377 with findBlockMembership :483-585 and floodFill :426-474, at the constructor defaults of :152-156: doRefine,
+ * ERODE_ALL_BORDER, INIT_STRICT; nothing else is offered), and every plane's points go through pcl::VoxelGrid (src/Frame.cc:435-439) and PlaneNotSeen
+ * (:349-371).  The two passes over all pixels run on the device, the block graph between them on the host (csrc/plane_seg_internal.h); the readings this
+ * build fixes where upstream leaves a value or an order open are in DESIGN.md section 4k.  The ParamSet is in millimetre units although the cloud is in
+ * metres: upstream's behaviour, kept.
+ * A handle is serialised by one mutex; distinct handles run side by side on the Latency stream class.  An invalid ARGUMENT (a NULL, a stride below the width, a
+ * capacity below the count, an index out of range) leaves every output and all state untouched.  Two EAO_ERR_INVALID returns of eao_plane_seg_run depend on the
+ * image instead and come after the run has started: more than EAO_PLANE_SEG_MAX_PLANES final planes, and a voxel grid past INT_MAX cells for one plane or
+ * EAO_PLANE_SEG_MAX_CELLS for all.  These two, like a device error, DROP THE PREVIOUS FRAME'S RESULTS: the handle is left without results and the read-backs
+ * fail with EAO_ERR_INVALID until the next successful run.  Two runs on the same image return the same bytes, on one handle or on two. */
+#define EAO_PLANE_SEG_MAX_PIXELS (1 << 22)       /* width * height */
+#define EAO_PLANE_SEG_MAX_WINDOW 32              /* window: 2 .. 32 */
+#define EAO_PLANE_SEG_MAX_PLANES 64              /* final planes of one frame; more is EAO_ERR_INVALID from eao_plane_seg_run */
+#define EAO_PLANE_SEG_MAX_CELLS 0x7fffffff       /* voxel cells of all final planes' grids together; one plane's grid past INT_MAX is refused as PCL refuses it */
+typedef struct {
+    int32_t width, height;
+    float fx, fy, cx, cy;              /* the Frame's static floats (src/Frame.cc:401-402) */
+    int32_t window;                    /* windowWidth == windowHeight (AHCPlaneFitter.hpp:154) */
+    int32_t min_support, max_step;     /* :153 */
+    float leaf;                        /* src/Frame.cc:436 */
+    double depth_min, depth_max;       /* src/Frame.cc:396: a pixel is invalid if isnan(d) || d > depth_max || d < depth_min */
+    /* ParamSet, AHCParamSet.hpp:68-76 */
+    double depth_sigma, std_tol_init, std_tol_merge;
+    double z_near, z_far, angle_near, angle_far;
+    double similarity_merge, similarity_refine;
+    double depth_alpha, depth_change_tol;
+} eao_plane_seg_cfg;
+/* One window x window block after the block constructor (AHCPlaneSeg.hpp:211-285) and Stats::compute (:125-156).  flag: bit 0 the block holds an invalid pixel,
+ * bit 1 a valid pixel of it differs from a valid right / lower neighbour by more than T_dz; 0: N = window * window and the rest is filled.  A flagged block has
+ * N = 0, zero sums, centre and normal, and the quiet NaN 0x7ff8000000000000 as mse and curvature. */
+typedef struct {
+    int32_t flag, N;
+    double sums[9];                    /* sx sy sz sxx syy szz sxy syz sxz, each accumulated in row-major order */
+    double center[3], normal[3], mse, curvature;
+} eao_plane_seg_block;
+/* One entry of plane_filter.extractedPlanes after run() (src/Frame.cc:425-456), in its order.  coef: (nx, ny, nz, d) as floats, negated when d < 0 (:441-445);
+ * kept: PlaneNotSeen against the kept planes before it (:447); cloud_offset / cloud_count: its voxel centroids among the handle's points (16 bytes each on the
+ * device); n_pixels: plane_vertices_[i].size(). */
+typedef struct {
+    double normal[3], center[3], mse, curvature;
+    int32_t N, rid;
+    float coef[4];
+    int32_t kept, cloud_offset, cloud_count, n_pixels;
+} eao_plane_seg_plane;
+typedef struct eao_plane_seg eao_plane_seg;
+/* PlaneFitter() (AHCPlaneFitter.hpp:152-156), ParamSet() (AHCParamSet.hpp:68-76) and the literals of src/Frame.cc:396 and :436 */
+void eao_plane_seg_cfg_default(eao_plane_seg_cfg* cfg, int32_t width, int32_t height, float fx, float fy, float cx, float cy);
+eao_status eao_plane_seg_create(const eao_plane_seg_cfg* cfg, eao_plane_seg** out);
+void eao_plane_seg_destroy(eao_plane_seg* h);
+/* Frame::ComputePlanesFromPEAC(imDepth) (src/Frame.cc:381-460): depth is height rows of width floats, `stride` floats apart (>= width).  The results stay in
+ * the handle until the next run. */
+eao_status eao_plane_seg_run(eao_plane_seg* h, const float* depth, int32_t stride);
+/* Counts of the last run: planes (plane_num_, :410), points of all clouds, blocks, pixels the flood fill claimed.  Any pointer may be NULL. */
+eao_status eao_plane_seg_info(eao_plane_seg* h, int32_t* n_planes, int32_t* n_points, int32_t* n_blocks, int32_t* n_claims);
+/* The plane table (:425-456).  planes == NULL: only *n.  cap below the count is EAO_ERR_INVALID. */
+eao_status eao_plane_seg_planes(eao_plane_seg* h, int32_t cap, eao_plane_seg_plane* planes, int32_t* n);
+/* coarseCloud of plane `plane` (:435-439, the public PCL 1.8 VoxelGrid: one centroid per occupied voxel in ascending voxel index, each the float sum of its
+ * points in ascending pixel index over the float count), whether kept or not.  xyz == NULL: only *n. */
+eao_status eao_plane_seg_cloud(eao_plane_seg* h, int32_t plane, int32_t cap, float* xyz /* cap*3 */, int32_t* n);
+/* membershipImg after refineDetails (AHCPlaneFitter.hpp:358-370) as width * height plane indices, -1 where upstream paints black */
+eao_status eao_plane_seg_membership(eao_plane_seg* h, int32_t* image /* width*height */);
+/* The per-block records of the last run, (height / window) * (width / window) of them in row-major block order; for the tests.  blocks == NULL: only *n. */
+eao_status eao_plane_seg_blocks(eao_plane_seg* h, int32_t cap, eao_plane_seg_block* blocks, int32_t* n);
+/* What the host's middle handed to the device, for the tests: blkMap (:131, one per block, indices into the planes of the FIRST ahCluster), plidmap (:327-342)
+ * and the pixels floodFill claimed as (pixel, plane) pairs in ascending pixel order.  Any array may be NULL. */
+eao_status eao_plane_seg_middle(eao_plane_seg* h, int32_t* blk_map, int32_t cap_old, int32_t* plidmap, int32_t* n_old, int32_t cap_claims, int32_t* claims /* cap_claims*2 */,
+                                int32_t* n_claims);
+/* Per-stage times of eao_plane_seg_run, for tools/bench_plane_segmentation.py.  With profiling on a run waits once more (behind the upload), so that the stages
+ * can be told apart; results are unchanged.  us[4], microseconds on the host's clock, every stage ending in a wait: upload of the depth image; k_ps_block_init
+ * and the download of the block records; the host's middle; membership and the voxel stage.  EAO_ERR_INVALID when the last run did not have profiling on. */
+eao_status eao_plane_seg_set_profiling(eao_plane_seg* h, int32_t on);
+eao_status eao_plane_seg_last_timing(eao_plane_seg* h, double* us /* 4 */);
+/* eao_plane_map_add / eao_plane_map_update_boundary (MapPlane::MapPlane, src/MapPlane.cc:34-37; UpdateBoundary, :150-153) with the cloud taken from the kept
+ * plane `plane` (an index into eao_plane_seg_planes) of a segmentation handle's last run, device to device: mvBoundaryPoints[i] of the frame never visits the
+ * host.  The same transform kernel and the same table as the host-pointer forms: the resident bytes are those of eao_plane_map_add on the read-back cloud.  A plane
+ * that was not kept, an index out of range and a handle without results are EAO_ERR_INVALID; nothing changes then.  The map's mutex is taken first, then the
+ * segmentation handle's. */
+eao_status eao_plane_map_add_from_seg(eao_plane_map* pm, uint64_t id, const float* world_pos /* 4 */, eao_plane_seg* seg, int32_t plane, const float* Tcw /* 16 or NULL */);
+eao_status eao_plane_map_update_boundary_from_seg(eao_plane_map* pm, uint64_t id, eao_plane_seg* seg, int32_t plane, const float* Tcw /* 16 or NULL */);
+
 /* The value of EAO_ABI_VERSION the library was built with. Bumped whenever an entry point's parameter list or a struct's layout changes (round 3
  * changed eao_tracker_track_local_map and eao_track_result in place); a caller compiled against another version must not call into the library.
  * Result structs are zero-initialised by the caller (`eao_track_result R = {0};`) before their array pointers are set: a pointer member the
