@@ -1,10 +1,9 @@
 // keyframe_db.hip -- KeyFrameDatabase on the device (include/eao_fusion.h, "KeyFrameDatabase"; reference src/KeyFrameDatabase.cc): the BoW vectors of the added
 // keyframes stay in HBM, a query uploads the query vector alone and downloads 16 bytes per live keyframe.
 //
-// Resident: one arena of word ids (uint32) and one of values (double), appended to by add; one (begin, count) record per LIVE entry in storage order, which is
-// what the kernel's grid runs over.  The full entry table (begin, count, add sequence, live flag) and the per-keyframe state are the host's (keyframe_db_internal.h).
-// The arenas grow by allocating twice the size and copying device to device; erase marks the entry dead and, once the dead words exceed half of the words in use,
-// the live vectors are copied together into a fresh allocation.
+// Resident: one arena of two columns, word ids (uint32) and values (double), appended to by add; one (begin, count) record per LIVE entry in storage order, which
+// is what the kernel's grid runs over.  The entry table and the per-keyframe state are the host's (keyframe_db_internal.h); growth and compaction are the policy
+// of resident_arena.h, carried out by dev_arena.h.
 //
 // k_kfdb_intersect: one wavefront per live stored vector, four per workgroup (the shape of k_bow_score_l1), the query's ids staged in LDS.  Upstream's inverted-file walk is, per stored
 // keyframe, the count of the query's words it holds; its scoring is the sorted intersection of the same two vectors.  One pass of bow_l1_pair gives the count,
@@ -15,34 +14,28 @@
 #include <vector>
 
 #include "bow_intersect.h"
-#include "common.h"
+#include "dev_arena.h"
 #include "keyframe_db_internal.h"
 
 namespace kfdb = eao::kfdb;
 static_assert(kfdb::kMaxWordsPerVector == EAO_VOCABULARY_MAX_FEATURES, "the cap of a vector is the vocabulary's");
 
+namespace {
+constexpr size_t kInitialWords = 1 << 14;      // 192 KiB of arena; doubles from there
+constexpr size_t kInitialRecs = 256;
+constexpr uint64_t kMaxArenaWords = 0xffffffffull;      // a record's begin is 32 bits
+}  // namespace
+
 struct eao_keyframe_db {
     std::mutex mutex;      // upstream's mMutex, widened to the whole call
     int32_t nWords = 0;
     kfdb::Table table;
-    unsigned* ids = nullptr;      // the arenas: capWords entries each
-    double* vals = nullptr;
-    size_t capWords = 0;
-    uint2* rec = nullptr;         // (begin, count) of the live entries, storage order
-    size_t capRec = 0;
-    bool recStale = false;        // an erase / compaction / clear happened since rec was written
-    ~eao_keyframe_db() {
-        if (ids) (void)hipFree(ids);
-        if (vals) (void)hipFree(vals);
-        if (rec) (void)hipFree(rec);
-    }
+    eao::DevArena<unsigned, double> words{kInitialWords, kMaxArenaWords};      // the arena: ids (0) and values (1)
+    eao::DevArena<uint2> rec{kInitialRecs};      // (begin, count) of the live entries, storage order
+    bool recStale = false;                       // an erase / compaction / clear happened since rec was written
 };
 
 namespace {
-
-constexpr size_t kInitialWords = 1 << 14;      // 192 KiB of arena; doubles from there
-constexpr size_t kInitialRecs = 256;
-constexpr uint64_t kMaxArenaWords = 0xffffffffull;      // a record's begin is 32 bits
 
 // The workgroup stages the query's ids in LDS first (nq <= 8192 ids = 32 KiB of dynamic LDS) and the binary searches probe LDS: measured against probing
 // global memory (profiles/keyframe_database_timing.txt: 0.132 against 0.203 ms at 20 000 keyframes), after which the plain form was dropped.
@@ -71,80 +64,12 @@ struct KfdbCtx : eao::ThreadStream {
 };
 thread_local KfdbCtx g_kfdb;
 
-// a larger allocation with the first `used` elements of the old one; the old one is freed once the copy has ended
-template <typename T>
-eao_status regrow(T*& p, size_t used, size_t newCap, hipStream_t stream) {
-    T* q = nullptr;
-    EAO_HIP(hipMalloc((void**)&q, newCap * sizeof(T)));
-    hipError_t e = hipSuccess;
-    if (used > 0) e = hipMemcpyAsync(q, p, used * sizeof(T), hipMemcpyDeviceToDevice, stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(stream);
-    if (e != hipSuccess) {
-        (void)hipFree(q);
-        EAO_HIP(e);
-    }
-    if (p) (void)hipFree(p);
-    p = q;
-    return EAO_OK;
-}
-
 eao_status reserve_words(eao_keyframe_db* db, uint64_t need, hipStream_t stream) {
-    if (need <= db->capWords) return EAO_OK;
     if (need > kMaxArenaWords) {
         eao::set_error("the arena would hold %llu words; at most %llu are supported", (unsigned long long)need, (unsigned long long)kMaxArenaWords);
         return EAO_ERR_CAPACITY;
     }
-    size_t cap = db->capWords ? db->capWords : kInitialWords;
-    while (cap < need) cap *= 2;
-    if (cap > kMaxArenaWords) cap = (size_t)kMaxArenaWords;
-    const size_t used = (size_t)db->table.usedWords;
-    eao_status st = regrow(db->ids, used, cap, stream);
-    if (st) return st;      // (ids may be the larger one now; capWords still names what both hold)
-    if ((st = regrow(db->vals, used, cap, stream))) return st;
-    db->capWords = cap;
-    return EAO_OK;
-}
-
-eao_status reserve_recs(eao_keyframe_db* db, size_t need, size_t used, hipStream_t stream) {
-    if (need <= db->capRec) return EAO_OK;
-    size_t cap = db->capRec ? db->capRec : kInitialRecs;
-    while (cap < need) cap *= 2;
-    const eao_status st = regrow(db->rec, used, cap, stream);
-    if (st) return st;
-    db->capRec = cap;
-    return EAO_OK;
-}
-
-// the dead words exceed their share: the live vectors into a fresh allocation, in storage order
-eao_status compact(eao_keyframe_db* db, hipStream_t stream) {
-    std::vector<kfdb::Move> moves;
-    const uint64_t live = db->table.plan_compaction(moves);
-    size_t cap = kInitialWords;
-    while (cap < live * 2) cap *= 2;
-    if (cap > kMaxArenaWords) cap = (size_t)kMaxArenaWords;
-    unsigned* nIds = nullptr;
-    double* nVals = nullptr;
-    EAO_HIP(hipMalloc((void**)&nIds, cap * sizeof(unsigned)));
-    hipError_t e = hipMalloc((void**)&nVals, cap * sizeof(double));
-    for (size_t m = 0; m < moves.size() && e == hipSuccess; m++) {
-        e = hipMemcpyAsync(nIds + moves[m].dst, db->ids + moves[m].src, moves[m].count * sizeof(unsigned), hipMemcpyDeviceToDevice, stream);
-        if (e == hipSuccess) e = hipMemcpyAsync(nVals + moves[m].dst, db->vals + moves[m].src, moves[m].count * sizeof(double), hipMemcpyDeviceToDevice, stream);
-    }
-    if (e == hipSuccess) e = hipStreamSynchronize(stream);
-    if (e != hipSuccess) {      // nothing changed: the old arenas and the table stand
-        (void)hipStreamSynchronize(stream);
-        (void)hipFree(nIds);
-        if (nVals) (void)hipFree(nVals);
-        EAO_HIP(e);
-    }
-    (void)hipFree(db->ids);
-    (void)hipFree(db->vals);
-    db->ids = nIds;
-    db->vals = nVals;
-    db->capWords = cap;
-    db->table.apply_compaction();
-    db->recStale = true;
-    return EAO_OK;
+    return db->words.reserve(need, db->table.used, stream);
 }
 
 eao_status check_query(const eao_keyframe_db* db, int32_t nq, const uint32_t* qId, const double* qVal) {
@@ -191,15 +116,15 @@ eao_status intersect(eao_keyframe_db* db, int32_t nq, const uint32_t* qId, const
         EAO_HIP(hipMemcpyAsync(d, h, inEnd, hipMemcpyHostToDevice, ctx.stream));
     }
     if (db->recStale) {      // after an erase: the records of the live entries again (8 bytes each)
-        if ((st = reserve_recs(db, (size_t)n, 0, ctx.stream))) return st;
+        if ((st = db->rec.reserve((size_t)n, 0, ctx.stream))) return st;
         uint2* hr = (uint2*)(h + oRec);
         size_t k = 0;
         for (const kfdb::Entry& e : db->table.entries)
             if (e.live) hr[k++] = make_uint2((unsigned)e.begin, e.count);
-        EAO_HIP(hipMemcpyAsync(db->rec, hr, (size_t)n * sizeof(uint2), hipMemcpyHostToDevice, ctx.stream));
+        EAO_HIP(hipMemcpyAsync(db->rec.at(), hr, (size_t)n * sizeof(uint2), hipMemcpyHostToDevice, ctx.stream));
     }
-    hipLaunchKernelGGL(k_kfdb_intersect, dim3(eao::cdiv(n, 4)), dim3(256), (size_t)nq * 4, ctx.stream, nq, (const unsigned*)(d + oQi), (const double*)(d + oQv), n, db->rec,
-                       db->ids, db->vals, (int*)(d + oCommon), (unsigned*)(d + oFirst), (double*)(d + oScore));
+    hipLaunchKernelGGL(k_kfdb_intersect, dim3(eao::cdiv(n, 4)), dim3(256), (size_t)nq * 4, ctx.stream, nq, (const unsigned*)(d + oQi), (const double*)(d + oQv), n, db->rec.at(),
+                       db->words.at<0>(), db->words.at<1>(), (int*)(d + oCommon), (unsigned*)(d + oFirst), (double*)(d + oScore));
     const hipError_t launchErr = hipGetLastError();
     if (launchErr != hipSuccess) (void)hipStreamSynchronize(ctx.stream);      // (the uploads out of this thread's staging block are enqueued)
     EAO_HIP(launchErr);
@@ -241,8 +166,8 @@ eao_status eao_keyframe_db_info(eao_keyframe_db* db, int32_t* n_live, int64_t* n
     EAO_REQUIRE(db, "db is NULL");
     std::lock_guard<std::mutex> lock(db->mutex);
     if (n_live) *n_live = db->table.nLive;
-    if (n_stored_words) *n_stored_words = (int64_t)db->table.usedWords;
-    if (arena_capacity) *arena_capacity = (int64_t)db->capWords;
+    if (n_stored_words) *n_stored_words = (int64_t)db->table.used;
+    if (arena_capacity) *arena_capacity = (int64_t)db->words.cap;
     return EAO_OK;
 }
 
@@ -255,25 +180,25 @@ eao_status eao_keyframe_db_add(eao_keyframe_db* db, uint64_t kf_id, int32_t n, c
     KfdbCtx& ctx = g_kfdb;
     eao_status st = ctx.ready(eao::StreamClass::Latency);
     if (st) return st;
-    const uint64_t begin = db->table.usedWords;
+    const uint64_t begin = db->table.used;
     if ((st = reserve_words(db, begin + (uint64_t)n, ctx.stream))) return st;
     const size_t at = (size_t)db->table.nLive;      // the new entry's record (when the records are stale the next query writes them all)
-    if (!db->recStale && (st = reserve_recs(db, at + 1, at, ctx.stream))) return st;
+    if (!db->recStale && (st = db->rec.reserve(at + 1, at, ctx.stream))) return st;
     const size_t oId = 0, oVal = eao::align256((size_t)n * 4), oRec = oVal + eao::align256((size_t)n * 8);
     if ((st = ctx.host.reserve(oRec + sizeof(uint2)))) return st;
     unsigned char* h = ctx.host.p;
     if (n > 0) {
         std::memcpy(h + oId, word_id, (size_t)n * 4);
         std::memcpy(h + oVal, word_val, (size_t)n * 8);
-        EAO_HIP(hipMemcpyAsync(db->ids + begin, h + oId, (size_t)n * 4, hipMemcpyHostToDevice, ctx.stream));
-        EAO_HIP(hipMemcpyAsync(db->vals + begin, h + oVal, (size_t)n * 8, hipMemcpyHostToDevice, ctx.stream));
+        EAO_HIP(hipMemcpyAsync(db->words.at<0>() + begin, h + oId, (size_t)n * 4, hipMemcpyHostToDevice, ctx.stream));
+        EAO_HIP(hipMemcpyAsync(db->words.at<1>() + begin, h + oVal, (size_t)n * 8, hipMemcpyHostToDevice, ctx.stream));
     }
     if (!db->recStale) {
         *(uint2*)(h + oRec) = make_uint2((unsigned)begin, (unsigned)n);
-        EAO_HIP(hipMemcpyAsync(db->rec + at, h + oRec, sizeof(uint2), hipMemcpyHostToDevice, ctx.stream));
+        EAO_HIP(hipMemcpyAsync(db->rec.at() + at, h + oRec, sizeof(uint2), hipMemcpyHostToDevice, ctx.stream));
     }
     EAO_HIP(hipStreamSynchronize(ctx.stream));
-    db->table.append(kf_id, (uint32_t)n);      // (only now: a failed call leaves the table as it was; words past usedWords are never read)
+    db->table.append(kf_id, (uint32_t)n);      // (only now: a failed call leaves the table as it was)
     return EAO_OK;
 }
 
@@ -282,13 +207,7 @@ eao_status eao_keyframe_db_erase(eao_keyframe_db* db, uint64_t kf_id) {
     std::lock_guard<std::mutex> lock(db->mutex);
     if (!db->table.erase(kf_id)) return EAO_OK;      // unknown: a no-op, as upstream (:52-64 finds nothing to erase)
     db->recStale = true;
-    if (db->table.wants_compaction()) {
-        KfdbCtx& ctx = g_kfdb;
-        eao_status st = ctx.ready(eao::StreamClass::Latency);
-        if (st) return st;
-        if ((st = compact(db, ctx.stream))) return st;
-    }
-    return EAO_OK;
+    return eao::compact_if_wanted(g_kfdb, db->table, db->words);
 }
 
 eao_status eao_keyframe_db_intersect(eao_keyframe_db* db, int32_t nq, const uint32_t* q_id, const double* q_val, int32_t cap, uint64_t* kf_id, int32_t* common,

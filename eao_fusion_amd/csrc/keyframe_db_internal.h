@@ -16,8 +16,7 @@
 //   - erasing an unknown id is a no-op, as upstream;
 //   - a re-added id starts with fresh state (upstream's KeyFrame object would keep its members; a keyframe is erased when it is set bad and never comes back);
 //   - word ids at or above n_words are refused (upstream indexes past mvInvertedFile).
-// Compaction: erase leaves the entry's words dead in the arena; when the dead words exceed HALF of the words in use the live entries are copied together, in
-// storage order (plan_compaction / apply_compaction), so the arena never holds more than twice the live words plus its growth slack.
+// Storage: the policy of resident_arena.h over one arena of words; storage order is add order.
 #pragma once
 #include <algorithm>
 #include <cstdint>
@@ -25,6 +24,8 @@
 #include <unordered_map>
 #include <unordered_set>
 #include <vector>
+
+#include "resident_arena.h"
 
 namespace eao {
 namespace kfdb {
@@ -42,31 +43,14 @@ struct KfState {      // include/KeyFrame.h:207-212
     bool relocSet = false;
 };
 
-struct Entry {      // one stored vector: words begin .. begin + count - 1 of the arena
-    uint64_t id;
-    uint64_t begin;
-    uint32_t count;
-    uint64_t seq;      // add sequence number (storage order is add order, so it ascends along the table)
-    bool live;
-};
+using Entry = arena::Entry<arena::NoPayload>;      // one stored vector: words begin .. begin + count - 1 of the arena
 
-struct Move {      // compaction: count words from src of the old arena to dst of the new one
-    uint64_t src, dst, count;
-};
-
-struct Table {
-    std::vector<Entry> entries;                        // storage order
-    std::unordered_map<uint64_t, size_t> byId;         // live ids -> position in entries
+struct Table : arena::Table<arena::NoPayload> {      // entries in storage order = add order
     std::unordered_map<uint64_t, KfState> state;       // live ids
-    uint64_t nextSeq = 0, usedWords = 0, deadWords = 0;
-    int32_t nLive = 0;
 
     void clear() {
-        entries.clear();
-        byId.clear();
+        arena::Table<arena::NoPayload>::clear();
         state.clear();
-        usedWords = deadWords = 0;
-        nLive = 0;
     }
     // "" when (id, n, wordId) may be added
     std::string check_add(uint64_t id, int64_t n, const uint32_t* wordId, int64_t nWords) const {
@@ -80,57 +64,14 @@ struct Table {
         }
         return "";
     }
-    // appends; returns the arena position of the vector's first word
+    // appends with fresh state; returns the arena position of the vector's first word
     uint64_t append(uint64_t id, uint32_t n) {
-        const uint64_t begin = usedWords;
-        byId[id] = entries.size();
-        entries.push_back(Entry{id, begin, n, nextSeq++, true});
         state[id] = KfState();
-        usedWords += n;
-        nLive++;
-        return begin;
+        return arena::Table<arena::NoPayload>::append(id, n);
     }
     bool erase(uint64_t id) {
-        auto it = byId.find(id);
-        if (it == byId.end()) return false;
-        Entry& e = entries[it->second];
-        e.live = false;
-        deadWords += e.count;
-        byId.erase(it);
         state.erase(id);
-        nLive--;
-        return true;
-    }
-    bool wants_compaction() const { return deadWords * 2 > usedWords || (nLive == 0 && !entries.empty()); }
-    // compaction, planned: the copies that bring the live vectors together in storage order (consecutive live entries joined into one copy; a run that
-    // stays where it is is listed too, since the copies go into a fresh allocation).  Returns the live words.  Nothing changes before apply_compaction().
-    uint64_t plan_compaction(std::vector<Move>& moves) const {
-        moves.clear();
-        uint64_t at = 0;
-        for (const Entry& e : entries) {
-            if (!e.live || e.count == 0) continue;
-            if (!moves.empty() && moves.back().src + moves.back().count == e.begin) moves.back().count += e.count;
-            else moves.push_back(Move{e.begin, at, e.count});
-            at += e.count;
-        }
-        return at;
-    }
-    // drops the dead entries and closes the gaps
-    void apply_compaction() {
-        std::vector<Entry> kept;
-        kept.reserve((size_t)nLive);
-        uint64_t at = 0;
-        for (const Entry& e : entries) {
-            if (!e.live) continue;
-            kept.push_back(e);
-            kept.back().begin = at;
-            at += e.count;
-        }
-        entries.swap(kept);
-        byId.clear();
-        for (size_t i = 0; i < entries.size(); i++) byId[entries[i].id] = i;
-        usedWords = at;
-        deadWords = 0;
+        return arena::Table<arena::NoPayload>::erase(id);
     }
     KfState read(uint64_t id) const {
         auto it = state.find(id);

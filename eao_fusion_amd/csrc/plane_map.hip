@@ -3,8 +3,8 @@
 // coefficients and download one index per plane.
 //
 // Resident: one arena of points, 16 bytes each (x, y, z, 0), appended to by add / update_boundary.  The table (id, offset, count, world position per plane) is
-// the host's (plane_map_internal.h); a query uploads one 32-byte record per candidate, so nothing on the device goes stale when a plane moves or leaves.  The
-// arena grows by allocating twice the size and copying device to device; replaced and erased clouds are compacted away once they exceed half of the points in use.
+// the host's (plane_map_internal.h); a query uploads one 32-byte record per candidate, so nothing on the device goes stale when a plane moves or leaves.
+// Growth and compaction are the policy of resident_arena.h, carried out by dev_arena.h.
 //
 // k_pm_transform   pcl::transformPointCloud(cloud, out, T.inverse().matrix()): one thread per point, double, rounded once per coordinate
 // k_pm_min_dist    one workgroup per (candidate, chunk of 512 of its points): the query rows (world-frame coefficients) and this candidate's gate flags in LDS,
@@ -19,6 +19,7 @@
 #include <string>
 #include <vector>
 
+#include "dev_arena.h"
 #include "lm_internal.h"      // se3_from_Tcw_f32, quat_to_matrix: Converter::toSE3Quat and the isometry it becomes
 #include "plane_map_internal.h"
 #include "plane_seg_shared.h"      // plane_seg_kept_cloud: the *_from_seg entry points
@@ -27,19 +28,18 @@ namespace pmap = eao::pmap;
 static_assert(pmap::kMaxRows == EAO_PLANE_MAP_MAX_ROWS && pmap::kMaxPointsPerPlane == EAO_PLANE_MAP_MAX_POINTS &&
               pmap::kMaxCandidates == EAO_PLANE_MAP_MAX_CANDIDATES, "the caps of the header are the table's");
 
+namespace {
+constexpr size_t kInitialPoints = 1 << 13;      // 128 KiB of arena; doubles from there
+}  // namespace
+
 struct eao_plane_map {
     std::mutex mutex;      // upstream's mMutexMap around both loops, widened to every call
     pmap::Table table;
-    float4* pts = nullptr;      // the arena: capPoints entries
-    size_t capPoints = 0;
-    ~eao_plane_map() {
-        if (pts) (void)hipFree(pts);
-    }
+    eao::DevArena<float4> pts{kInitialPoints};      // the arena (check_cloud bounds the points in use, so the doubling needs no clamp)
 };
 
 namespace {
 
-constexpr size_t kInitialPoints = 1 << 13;      // 128 KiB of arena; doubles from there
 constexpr int kRowTile = 8;                     // rows whose minima a lane keeps in registers at a time
 constexpr unsigned kNoDistanceBits = 0x42C80000u;      // 100.0f
 static_assert(pmap::kChunk == 512, "k_pm_min_dist holds two points per lane of 256");
@@ -175,51 +175,6 @@ struct PmapCtx : eao::ThreadStream {
 };
 thread_local PmapCtx g_pmap;
 
-// a larger arena with the first `used` points of the old one; the old one is freed once the copy has ended
-eao_status reserve_points(eao_plane_map* pm, uint64_t need, hipStream_t stream) {
-    if (need <= pm->capPoints) return EAO_OK;
-    size_t cap = pm->capPoints ? pm->capPoints : kInitialPoints;
-    while (cap < need) cap *= 2;
-    float4* q = nullptr;
-    EAO_HIP(hipMalloc((void**)&q, cap * sizeof(float4)));
-    const size_t used = (size_t)pm->table.usedPoints;
-    hipError_t e = hipSuccess;
-    if (used > 0) e = hipMemcpyAsync(q, pm->pts, used * sizeof(float4), hipMemcpyDeviceToDevice, stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(stream);
-    if (e != hipSuccess) {
-        (void)hipFree(q);
-        EAO_HIP(e);
-    }
-    if (pm->pts) (void)hipFree(pm->pts);
-    pm->pts = q;
-    pm->capPoints = cap;
-    return EAO_OK;
-}
-
-// the dead points exceed their share: the live clouds into a fresh allocation, in table order
-eao_status compact(eao_plane_map* pm, hipStream_t stream) {
-    std::vector<pmap::Move> moves;
-    const uint64_t live = pm->table.plan_compaction(moves);
-    size_t cap = kInitialPoints;
-    while (cap < live * 2) cap *= 2;
-    float4* q = nullptr;
-    EAO_HIP(hipMalloc((void**)&q, cap * sizeof(float4)));
-    hipError_t e = hipSuccess;
-    for (size_t m = 0; m < moves.size() && e == hipSuccess; m++)
-        e = hipMemcpyAsync(q + moves[m].dst, pm->pts + moves[m].src, moves[m].count * sizeof(float4), hipMemcpyDeviceToDevice, stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(stream);
-    if (e != hipSuccess) {      // nothing changed: the old arena and the table stand
-        (void)hipStreamSynchronize(stream);
-        (void)hipFree(q);
-        EAO_HIP(e);
-    }
-    (void)hipFree(pm->pts);
-    pm->pts = q;
-    pm->capPoints = cap;
-    pm->table.apply_compaction();
-    return EAO_OK;
-}
-
 // T.inverse().matrix() of Eigen::Isometry3d T = Converter::toSE3Quat(Tcw) (src/MapPlane.cc:34-36): the unit quaternion of the rotation block and the
 // translation, as a rotation matrix again, inverted as R^T, -(R^T t)
 Xf inverse_isometry(const float* Tcw) {
@@ -238,7 +193,7 @@ Xf inverse_isometry(const float* Tcw) {
 eao_status transform_into(eao_plane_map* pm, PmapCtx& ctx, uint64_t begin, int32_t n, const float* devXyz, int stride, const float* Tcw) {
     Xf X = Xf();
     if (Tcw) X = inverse_isometry(Tcw);
-    hipLaunchKernelGGL(k_pm_transform, dim3(eao::cdiv(n, 256)), dim3(256), 0, ctx.stream, n, devXyz, stride, X, Tcw ? 0 : 1, pm->pts + begin);
+    hipLaunchKernelGGL(k_pm_transform, dim3(eao::cdiv(n, 256)), dim3(256), 0, ctx.stream, n, devXyz, stride, X, Tcw ? 0 : 1, pm->pts.at() + begin);
     const hipError_t launchErr = hipGetLastError();
     const hipError_t syncErr = hipStreamSynchronize(ctx.stream);
     EAO_HIP(launchErr);
@@ -246,40 +201,55 @@ eao_status transform_into(eao_plane_map* pm, PmapCtx& ctx, uint64_t begin, int32
     return EAO_OK;
 }
 
-// n points of the caller's into the arena at `begin`
-eao_status store_cloud(eao_plane_map* pm, PmapCtx& ctx, uint64_t begin, int32_t n, const float* xyz, const float* Tcw) {
-    if (n == 0) return EAO_OK;
+// n points of the caller's through this thread's staging block into device memory
+eao_status upload_cloud(PmapCtx& ctx, int32_t n, const float* xyz) {
     const size_t bytes = (size_t)n * 12;
     eao_status st;
     if ((st = ctx.dev.reserve(bytes))) return st;
     if ((st = ctx.host.reserve(bytes))) return st;
     std::memcpy(ctx.host.p, xyz, bytes);
     EAO_HIP(hipMemcpyAsync(ctx.dev.p, ctx.host.p, bytes, hipMemcpyHostToDevice, ctx.stream));
-    return transform_into(pm, ctx, begin, n, (const float*)ctx.dev.p, 3, Tcw);
+    return EAO_OK;
 }
 
-// add (isAdd) or update_boundary from a segmentation handle's kept plane, device to device: the table logic of the host-pointer forms
-eao_status store_from_seg(eao_plane_map* pm, bool isAdd, uint64_t id, const float* world_pos, eao_plane_seg* seg, int32_t plane, const float* Tcw) {
+// where a cloud comes from: the caller's n packed points at xyz, or (seg != NULL) the voxel cloud of a segmentation handle's kept plane, device to device
+struct CloudSource {
+    int32_t n;
+    const float* xyz;
+    eao_plane_seg* seg;
+    int32_t plane;
+};
+
+// The one body of add (isAdd) and update_boundary and of their *_from_seg forms.  `name` is the entry point's, in front of what check_cloud objects to.
+eao_status store(eao_plane_map* pm, const char* name, bool isAdd, uint64_t id, const float* world_pos, const CloudSource& src, const float* Tcw) {
     std::lock_guard<std::mutex> lock(pm->mutex);
     std::unique_lock<std::mutex> segLock;      // (always taken after the map's: nothing in plane_seg.hip takes a map's mutex)
-    const float* src = nullptr;
-    int32_t n = 0;
-    eao_status st = eao::plane_seg_kept_cloud(seg, plane, segLock, &src, &n);
-    if (st) return st;
+    eao_plane_seg* const seg = src.seg;
+    const float *xyz = src.xyz, *devXyz = nullptr;
+    int32_t n = src.n;
+    eao_status st;
+    if (seg && (st = eao::plane_seg_kept_cloud(seg, src.plane, segLock, &devXyz, &n))) return st;
     const std::string err = pm->table.check_cloud(id, n, isAdd);
-    EAO_REQUIRE(err.empty(), "%s: %s", isAdd ? "eao_plane_map_add_from_seg" : "eao_plane_map_update_boundary_from_seg", err.c_str());
+    EAO_REQUIRE(err.empty(), "%s: %s", name, err.c_str());
+    EAO_REQUIRE(seg || n == 0 || xyz, "xyz is NULL");
     PmapCtx& ctx = g_pmap;
     if ((st = ctx.ready(eao::StreamClass::Latency))) return st;
-    const uint64_t begin = pm->table.usedPoints;
-    if ((st = reserve_points(pm, begin + (uint64_t)n, ctx.stream))) return st;
-    if (n > 0 && (st = transform_into(pm, ctx, begin, n, src, 4, Tcw))) return st;
+    const uint64_t begin = pm->table.used;
+    if ((st = pm->pts.reserve(begin + (uint64_t)n, begin, ctx.stream))) return st;
+    if (n > 0) {
+        if (!seg) {
+            if ((st = upload_cloud(ctx, n, xyz))) return st;
+            devXyz = (const float*)ctx.dev.p;
+        }
+        if ((st = transform_into(pm, ctx, begin, n, devXyz, seg ? 4 : 3, Tcw))) return st;
+    }
+    // (only now: a failed call leaves the table as it was)
     if (isAdd) {
         pm->table.append(id, (uint32_t)n, world_pos);
         return EAO_OK;
     }
     pm->table.replace(id, (uint32_t)n);
-    if (pm->table.wants_compaction()) return compact(pm, ctx.stream);
-    return EAO_OK;
+    return eao::compact_if_wanted(ctx, pm->table, pm->pts);
 }
 
 }  // namespace
@@ -307,52 +277,29 @@ eao_status eao_plane_map_info(eao_plane_map* pm, int32_t* n_live, int64_t* n_poi
     EAO_REQUIRE(pm, "pm is NULL");
     std::lock_guard<std::mutex> lock(pm->mutex);
     if (n_live) *n_live = pm->table.nLive;
-    if (n_points_in_use) *n_points_in_use = (int64_t)pm->table.usedPoints;
-    if (arena_capacity) *arena_capacity = (int64_t)pm->capPoints;
+    if (n_points_in_use) *n_points_in_use = (int64_t)pm->table.used;
+    if (arena_capacity) *arena_capacity = (int64_t)pm->pts.cap;
     return EAO_OK;
 }
 
 eao_status eao_plane_map_add(eao_plane_map* pm, uint64_t id, const float* world_pos, int32_t n, const float* xyz, const float* Tcw) {
     EAO_REQUIRE(pm && world_pos, "bad argument");
-    std::lock_guard<std::mutex> lock(pm->mutex);
-    const std::string err = pm->table.check_cloud(id, n, true);
-    EAO_REQUIRE(err.empty(), "eao_plane_map_add: %s", err.c_str());
-    EAO_REQUIRE(n == 0 || xyz, "xyz is NULL");
-    PmapCtx& ctx = g_pmap;
-    eao_status st = ctx.ready(eao::StreamClass::Latency);
-    if (st) return st;
-    const uint64_t begin = pm->table.usedPoints;
-    if ((st = reserve_points(pm, begin + (uint64_t)n, ctx.stream))) return st;
-    if ((st = store_cloud(pm, ctx, begin, n, xyz, Tcw))) return st;
-    pm->table.append(id, (uint32_t)n, world_pos);      // (only now: a failed call leaves the table as it was; points past usedPoints are never read)
-    return EAO_OK;
+    return store(pm, "eao_plane_map_add", true, id, world_pos, CloudSource{n, xyz, nullptr, 0}, Tcw);
 }
 
 eao_status eao_plane_map_update_boundary(eao_plane_map* pm, uint64_t id, int32_t n, const float* xyz, const float* Tcw) {
     EAO_REQUIRE(pm, "pm is NULL");
-    std::lock_guard<std::mutex> lock(pm->mutex);
-    const std::string err = pm->table.check_cloud(id, n, false);
-    EAO_REQUIRE(err.empty(), "eao_plane_map_update_boundary: %s", err.c_str());
-    EAO_REQUIRE(n == 0 || xyz, "xyz is NULL");
-    PmapCtx& ctx = g_pmap;
-    eao_status st = ctx.ready(eao::StreamClass::Latency);
-    if (st) return st;
-    const uint64_t begin = pm->table.usedPoints;
-    if ((st = reserve_points(pm, begin + (uint64_t)n, ctx.stream))) return st;
-    if ((st = store_cloud(pm, ctx, begin, n, xyz, Tcw))) return st;
-    pm->table.replace(id, (uint32_t)n);
-    if (pm->table.wants_compaction()) return compact(pm, ctx.stream);
-    return EAO_OK;
+    return store(pm, "eao_plane_map_update_boundary", false, id, nullptr, CloudSource{n, xyz, nullptr, 0}, Tcw);
 }
 
 eao_status eao_plane_map_add_from_seg(eao_plane_map* pm, uint64_t id, const float* world_pos, eao_plane_seg* seg, int32_t plane, const float* Tcw) {
     EAO_REQUIRE(pm && world_pos && seg, "bad argument");
-    return store_from_seg(pm, true, id, world_pos, seg, plane, Tcw);
+    return store(pm, "eao_plane_map_add_from_seg", true, id, world_pos, CloudSource{0, nullptr, seg, plane}, Tcw);
 }
 
 eao_status eao_plane_map_update_boundary_from_seg(eao_plane_map* pm, uint64_t id, eao_plane_seg* seg, int32_t plane, const float* Tcw) {
     EAO_REQUIRE(pm && seg, "bad argument");
-    return store_from_seg(pm, false, id, nullptr, seg, plane, Tcw);
+    return store(pm, "eao_plane_map_update_boundary_from_seg", false, id, nullptr, CloudSource{0, nullptr, seg, plane}, Tcw);
 }
 
 eao_status eao_plane_map_set_world_pos(eao_plane_map* pm, uint64_t id, const float* world_pos) {
@@ -367,13 +314,7 @@ eao_status eao_plane_map_erase(eao_plane_map* pm, uint64_t id) {
     EAO_REQUIRE(pm, "pm is NULL");
     std::lock_guard<std::mutex> lock(pm->mutex);
     if (!pm->table.erase(id)) return EAO_OK;      // unknown: a no-op, as std::set::erase (src/Map.cc:150)
-    if (pm->table.wants_compaction()) {
-        PmapCtx& ctx = g_pmap;
-        eao_status st = ctx.ready(eao::StreamClass::Latency);
-        if (st) return st;
-        return compact(pm, ctx.stream);
-    }
-    return EAO_OK;
+    return eao::compact_if_wanted(g_pmap, pm->table, pm->pts);
 }
 
 eao_status eao_plane_map_boundary(eao_plane_map* pm, uint64_t id, int32_t cap, float* xyz, int32_t* n, float* world_pos) {
@@ -390,7 +331,7 @@ eao_status eao_plane_map_boundary(eao_plane_map* pm, uint64_t id, int32_t cap, f
         const size_t bytes = (size_t)cnt * 12;
         if ((st = ctx.dev.reserve(bytes))) return st;
         if ((st = ctx.host.reserve(bytes))) return st;
-        hipLaunchKernelGGL(k_pm_read, dim3(eao::cdiv(cnt, 256)), dim3(256), 0, ctx.stream, cnt, (const float4*)(pm->pts + e->begin), (float*)ctx.dev.p);
+        hipLaunchKernelGGL(k_pm_read, dim3(eao::cdiv(cnt, 256)), dim3(256), 0, ctx.stream, cnt, (const float4*)(pm->pts.at() + e->begin), (float*)ctx.dev.p);
         EAO_HIP(hipGetLastError());
         EAO_HIP(hipMemcpyAsync(ctx.host.p, ctx.dev.p, bytes, hipMemcpyDeviceToHost, ctx.stream));
         EAO_HIP(hipStreamSynchronize(ctx.stream));
@@ -450,7 +391,7 @@ eao_status eao_plane_map_associate(eao_plane_map* pm, int32_t n_sets, const floa
         EAO_HIP(hipMemsetD32Async((hipDeviceptr_t)(d + oDis), (int)kNoDistanceBits, (size_t)nPairs, ctx.stream));
         const size_t lds = (size_t)nRows * 17 + (size_t)eao::cdiv(nRows, kRowTile);
         hipLaunchKernelGGL(k_pm_min_dist, dim3((unsigned)work.size()), dim3(256), lds, ctx.stream, nRows, n_cand, (const float4*)(d + oRows),
-                           (const pmap::Cand*)(d + oCand), (const pmap::Work*)(d + oWork), (const float4*)pm->pts, angle_th, (unsigned*)(d + oDis), d + oGated);
+                           (const pmap::Cand*)(d + oCand), (const pmap::Work*)(d + oWork), (const float4*)pm->pts.at(), angle_th, (unsigned*)(d + oDis), d + oGated);
         launchErr = hipGetLastError();
     }
     if (launchErr == hipSuccess) {

@@ -2,10 +2,8 @@
 // position per MapPlane), the plan of a compaction, the work list of the distance kernel and upstream's selection loop (reference src/Map.cc:173-203, :264-290)
 // in plain C++, which tools/plane_association_walk.cpp walks stand-alone.
 //
-// Storage policy (that of keyframe_db_internal.h): one arena of points, appended to by add and by update_boundary; a replaced or erased cloud stays in the arena
-// as dead points; when the dead points exceed HALF of the points in use the live clouds are copied together, in table order (plan_compaction /
-// apply_compaction).  The table keeps ADD order: update_boundary moves a plane's cloud to the end of the arena but not the plane's place in the table, and a
-// candidate list of NULL means the live planes in that order.
+// Storage: the policy of resident_arena.h over one arena of points, appended to by add and by update_boundary.  The table keeps ADD order, and a candidate
+// list of NULL means the live planes in that order.
 //
 // Deviations from upstream:
 //   - adding an id that is live is refused (upstream's ids are unique: MapPlane::nLastId++, src/MapPlane.cc:26);
@@ -19,6 +17,8 @@
 #include <unordered_map>
 #include <vector>
 
+#include "resident_arena.h"
+
 namespace eao {
 namespace pmap {
 
@@ -30,105 +30,23 @@ constexpr uint64_t kMaxArenaPoints = 1ull << 28;      // 4 GiB of 16-byte points
 constexpr int kChunk = 512;                  // points of one workgroup of the distance kernel: 256 lanes x 2 points
 constexpr float kNoDistance = 100.0f;        // PointDistanceFromPlane's initial value, src/Map.cc:219
 
-struct Entry {      // one plane: points begin .. begin + count - 1 of the arena
-    uint64_t id;
-    uint64_t begin;
-    uint32_t count;
+struct World {
     float world[4];      // mWorldPos
-    bool live;
 };
+using Entry = arena::Entry<World>;      // one plane: points begin .. begin + count - 1 of the arena
 
-struct Move {      // compaction: count points from src of the old arena to dst of the new one
-    uint64_t src, dst, count;
-};
-
-struct Table {
-    std::vector<Entry> entries;                     // add order
-    std::unordered_map<uint64_t, size_t> byId;      // live ids -> position in entries
-    uint64_t usedPoints = 0, deadPoints = 0;
-    int32_t nLive = 0;
-
-    void clear() {
-        entries.clear();
-        byId.clear();
-        usedPoints = deadPoints = 0;
-        nLive = 0;
-    }
-    const Entry* find(uint64_t id) const {
-        auto it = byId.find(id);
-        return it == byId.end() ? nullptr : &entries[it->second];
-    }
+struct Table : arena::Table<World> {
     // "" when a cloud of n points may be stored (for add: under an id that is not live; for update: under one that is)
     std::string check_cloud(uint64_t id, int64_t n, bool add) const {
         if (n < 0) return "n < 0";
         if (n > kMaxPointsPerPlane) return "the cloud has " + std::to_string(n) + " points; at most " + std::to_string(kMaxPointsPerPlane) + " are supported";
         if (add && byId.count(id)) return "plane " + std::to_string(id) + " is already held";
         if (!add && !byId.count(id)) return "plane " + std::to_string(id) + " is not held";
-        if (usedPoints + (uint64_t)n > kMaxArenaPoints) return "the arena would hold more than " + std::to_string(kMaxArenaPoints) + " points";
+        if (used + (uint64_t)n > kMaxArenaPoints) return "the arena would hold more than " + std::to_string(kMaxArenaPoints) + " points";
         return "";
     }
-    // appends; returns the arena position of the cloud's first point
-    uint64_t append(uint64_t id, uint32_t n, const float world[4]) {
-        const uint64_t begin = usedPoints;
-        byId[id] = entries.size();
-        Entry e{id, begin, n, {world[0], world[1], world[2], world[3]}, true};
-        entries.push_back(e);
-        usedPoints += n;
-        nLive++;
-        return begin;
-    }
-    // UpdateBoundary: the old cloud dies where it lies, the new one goes to the end of the arena; the plane keeps its place in the table
-    uint64_t replace(uint64_t id, uint32_t n) {
-        Entry& e = entries[byId.at(id)];
-        deadPoints += e.count;
-        e.begin = usedPoints;
-        e.count = n;
-        usedPoints += n;
-        return e.begin;
-    }
+    uint64_t append(uint64_t id, uint32_t n, const float world[4]) { return arena::Table<World>::append(id, n, World{{world[0], world[1], world[2], world[3]}}); }
     void set_world(uint64_t id, const float world[4]) { std::memcpy(entries[byId.at(id)].world, world, 16); }
-    bool erase(uint64_t id) {
-        auto it = byId.find(id);
-        if (it == byId.end()) return false;
-        Entry& e = entries[it->second];
-        e.live = false;
-        deadPoints += e.count;
-        byId.erase(it);
-        nLive--;
-        return true;
-    }
-    bool wants_compaction() const { return deadPoints * 2 > usedPoints || (nLive == 0 && !entries.empty()); }
-    // compaction, planned: the copies that bring the live clouds together in table order (clouds that follow one another in the old arena joined into one
-    // copy; a run that stays where it is is listed too, since the copies go into a fresh allocation).  Returns the live points.  Nothing changes before
-    // apply_compaction().
-    uint64_t plan_compaction(std::vector<Move>& moves) const {
-        moves.clear();
-        uint64_t at = 0;
-        for (const Entry& e : entries) {
-            if (!e.live || e.count == 0) continue;
-            if (!moves.empty() && moves.back().src + moves.back().count == e.begin) moves.back().count += e.count;
-            else moves.push_back(Move{e.begin, at, e.count});
-            at += e.count;
-        }
-        return at;
-    }
-    // drops the dead entries and closes the gaps
-    void apply_compaction() {
-        std::vector<Entry> kept;
-        kept.reserve((size_t)nLive);
-        uint64_t at = 0;
-        for (const Entry& e : entries) {
-            if (!e.live) continue;
-            kept.push_back(e);
-            kept.back().begin = at;
-            at += e.count;
-        }
-        entries.swap(kept);
-        byId.clear();
-        for (size_t i = 0; i < entries.size(); i++) byId[entries[i].id] = i;
-        usedPoints = at;
-        deadPoints = 0;
-    }
 };
 
 // one candidate of a query as the kernels read it (32 bytes)

@@ -119,14 +119,40 @@ def test_random_sequences(walk, seed):
     assert quiet(run_walk(walk, script, initial=16)) == want
 
 
+def doubled(start, need):
+    """the smallest start * 2^k that is at least need"""
+    c = start
+    while c < need:
+        c *= 2
+    return c
+
+
 def test_the_sequences_reach_growth_and_compaction(walk):
+    """... and every capacity the walk prints is the storage policy's: initial * 2^k; a growth doubles the capacity it found until the points in use fit; a
+    compaction leaves the smallest initial * 2^k that is at least twice the points in use of the `table` line that follows (all live by then)."""
+    initial = 16
     grew = compacted = model_compactions = 0
     for seed in range(8):
         script, _, c = random_sequence(seed)
-        got = run_walk(walk, script, initial=16)
-        grew += sum(ln.startswith("grew") for ln in got)
-        compacted += sum(ln.startswith("compacted") for ln in got)
+        got = run_walk(walk, script, initial=initial)
         model_compactions += c
+        cap = 0      # (clear keeps the allocation)
+        for i, ln in enumerate(got):
+            if not ln.startswith(("grew", "compacted")):
+                continue
+            n = int(ln.split()[1])
+            table = next(x for x in got[i + 1:] if x.startswith("table")).split()
+            used, dead = int(table[2]), int(table[4])
+            assert n == doubled(initial, n), (seed, i, ln)
+            if ln.startswith("grew"):
+                grew += 1
+                assert n > cap and n >= used, (seed, i, ln, cap, used)
+                if got[i + 1].startswith("table"):      # no compaction in between: `used` is what the growth had to hold
+                    assert used > cap and n == doubled(cap or initial, used), (seed, i, ln, cap, used)
+            else:
+                compacted += 1
+                assert got[i + 1].startswith("table") and dead == 0 and n == doubled(initial, 2 * used), (seed, i, ln, used, dead)
+            cap = n
     assert grew > 8 and compacted > 8 and compacted == model_compactions
 
 

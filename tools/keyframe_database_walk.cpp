@@ -54,7 +54,7 @@ static int script() {
             uint64_t id;
             in >> id;
             if (t.erase(id) && t.wants_compaction()) {
-                std::vector<kfdb::Move> moves;
+                std::vector<eao::arena::Move> moves;
                 const uint64_t live = t.plan_compaction(moves);
                 uint64_t moved = 0;
                 for (const auto& m : moves) {
@@ -62,7 +62,7 @@ static int script() {
                     moved += m.count;
                 }
                 t.apply_compaction();
-                if (moved != live || t.usedWords != live || t.deadWords != 0) return 3;
+                if (moved != live || t.used != live || t.dead != 0) return 3;
                 std::printf("compacted %" PRIu64 "\n", live);
             }
         } else if (cmd == "clear") {

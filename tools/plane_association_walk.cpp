@@ -1,5 +1,5 @@
 // plane_association_walk.cpp -- Map::AssociatePlanesByBoundary / Map::SearchMatchedPlanes as the reference runs them (src/Map.cc:155-292): one host thread, the
-// literal loops, over the bookkeeping of eao_fusion_amd/csrc/plane_map_internal.h with a host arena in place of the device's.  Two uses:
+// literal loops, over the bookkeeping of eao_fusion_amd/csrc/plane_map_internal.h (the table and capacity rules of resident_arena.h) with a host arena in place of the device's.  Two uses:
 //
 //   g++ -O3 -march=native -ffp-contract=off -std=c++17 tools/plane_association_walk.cpp -o walk
 //   ./walk bench <rows> <planes> <points> <sets> <reps>      the baseline of tools/bench_plane_association.py: microseconds per call, single thread
@@ -35,21 +35,19 @@ struct HostMap {
 
     void reserve(uint64_t need) {
         if (need <= cap) return;
-        size_t c = cap ? cap : initial;
-        while (c < need) c *= 2;
+        const size_t c = (size_t)eao::arena::grown_capacity(cap, initial, need, eao::arena::kUnbounded);
         std::unique_ptr<float[]> q(new float[c * 4]);
-        if (table.usedPoints) std::memcpy(q.get(), pts.get(), (size_t)table.usedPoints * 16);
+        if (table.used) std::memcpy(q.get(), pts.get(), (size_t)table.used * 16);
         pts.swap(q);
         cap = c;
         if (verbose) std::printf("grew %zu\n", cap);
     }
     void compact() {
-        std::vector<pmap::Move> moves;
+        std::vector<eao::arena::Move> moves;
         const uint64_t live = table.plan_compaction(moves);
-        size_t c = initial;
-        while (c < live * 2) c *= 2;
+        const size_t c = (size_t)eao::arena::compacted_capacity(initial, live, eao::arena::kUnbounded);
         std::unique_ptr<float[]> q(new float[c * 4]);
-        for (const pmap::Move& m : moves) std::memcpy(q.get() + m.dst * 4, pts.get() + m.src * 4, (size_t)m.count * 16);
+        for (const eao::arena::Move& m : moves) std::memcpy(q.get() + m.dst * 4, pts.get() + m.src * 4, (size_t)m.count * 16);
         pts.swap(q);
         cap = c;
         table.apply_compaction();
@@ -63,7 +61,7 @@ struct HostMap {
     }
     bool add(uint64_t id, const float w[4], uint32_t n, const float* xyz) {
         if (!table.check_cloud(id, n, true).empty()) return false;
-        const uint64_t begin = table.usedPoints;
+        const uint64_t begin = table.used;
         reserve(begin + n);
         store(begin, n, xyz);
         table.append(id, n, w);
@@ -71,7 +69,7 @@ struct HostMap {
     }
     bool update(uint64_t id, uint32_t n, const float* xyz) {
         if (!table.check_cloud(id, n, false).empty()) return false;
-        const uint64_t begin = table.usedPoints;
+        const uint64_t begin = table.used;
         reserve(begin + n);
         store(begin, n, xyz);
         table.replace(id, n);
@@ -177,7 +175,7 @@ static int run_script(size_t initial) {
         } else if (cmd == "clear") {
             hm.table.clear();
         } else if (cmd == "table") {
-            std::printf("table used %llu dead %llu live %d |", (unsigned long long)hm.table.usedPoints, (unsigned long long)hm.table.deadPoints, hm.table.nLive);
+            std::printf("table used %llu dead %llu live %d |", (unsigned long long)hm.table.used, (unsigned long long)hm.table.dead, hm.table.nLive);
             for (const pmap::Entry& e : hm.table.entries)
                 if (e.live) std::printf(" %llu:%llu:%u", (unsigned long long)e.id, (unsigned long long)e.begin, e.count);
             std::printf("\n");
