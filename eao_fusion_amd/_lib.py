@@ -293,6 +293,11 @@ SYMBOLS = {
     "eao_plane_seg_middle": (_I, [_P, _P, _I, _P, C.POINTER(_I), _I, _P, C.POINTER(_I)]),
     "eao_plane_map_add_from_seg": (_I, [_P, C.c_uint64, _P, _P, _I, _P]),
     "eao_plane_map_update_boundary_from_seg": (_I, [_P, C.c_uint64, _P, _I, _P]),
+    "eao_iforest_scores_batch": (_I, [_I, _P, _P, _P, _P, _P, _P, _P, _P, C.c_int64, _P]),
+    "eao_object_iforest_outliers_batch": (_I, [_I, _P, _P, _P, _I, _P, _P, _P]),
+    "eao_iforest_set_profiling": (_I, [_I]),
+    "eao_iforest_last_kernel_ms": (_I, [_P]),
+    "eao_iforest_last_stage_us": (_I, [_P]),
     "eao_bundle_adjustment_plan": (_I, [_I, _I, _P, _P, _I, _P, _P, _P, _I, _P, _I, _P, _I, _P, _I, _P, _I, _P, _I]),
 }
 

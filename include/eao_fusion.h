@@ -1327,6 +1327,53 @@ eao_status eao_plane_seg_last_timing(eao_plane_seg* h, double* us /* 4 */);
 eao_status eao_plane_map_add_from_seg(eao_plane_map* pm, uint64_t id, const float* world_pos /* 4 */, eao_plane_seg* seg, int32_t plane, const float* Tcw /* 16 or NULL */);
 eao_status eao_plane_map_update_boundary_from_seg(eao_plane_map* pm, uint64_t id, eao_plane_seg* seg, int32_t plane, const float* Tcw /* 16 or NULL */);
 
+/* ---- Object layer: Object_Map::IsolationForestDeleteOutliers (src/Object.cc:1239-1348; called at :718, :1596, :1692, :1699) ---------------------------------
+ * The isolation forest of include/isolation_forest.h over an object's map points: IsolationForest::Build (:448-477), IsolationTree::Build (:301-345), Node::Build
+ * (:165-224), GetAnomalyScores (:499-529).  Every forest is a pure function of its point list, and the result is bit for bit what the reference's header
+ * computes under libstdc++ (g++ 11): std::mt19937, std::shuffle's two-swaps-per-draw path, uniform_int_distribution's multiply-and-reject method,
+ * generate_canonical<float, 24> and u * (b - a) + a rounded operation by operation (csrc/iforest_internal.h).  One wavefront builds one
+ * tree; one wavefront scores one point, a lane per tree; the host divides by the tree count and applies libm's pow.
+ * The entries are stateless; each host thread has its own stream and staging.  EAO_ERR_INVALID leaves every output untouched.  Two calls on the same arguments
+ * return the same bytes, on one thread or on several.
+ *
+ * eao_iforest_scores_batch: the general entry.  Object j owns points start[j] .. start[j+1] - 1 of xyz (3 floats each; start[0] >= 0, ascending) and entry j of
+ * tree_count, seed and sample_size (Build's treeCount, seed, sampleSize).  scores and total_path_len (optional) are indexed like the points: per point the
+ * score pow(2, -(total / tree_count) / C(sample_size)) (:524-526; NaN where C is 0, as upstream) and the total path length over the trees in index order
+ * (:517-522).  stream_start (optional, n_obj + 1 entries) receives the byte offsets of the objects' streams; stream (optional, needs stream_start; capacity
+ * stream_cap bytes) the exact bytes of IsolationForest::Serialize (:532-560) per object, back to back: a 16-byte forest header (size_t 3, tree count, sample
+ * size), per tree a 12-byte header (size_t 3, sample size) and the 12-byte node records {dim u32, split f32, size u32} in preorder, size == 0 on inner nodes.
+ * A stream buffer that is too short is EAO_ERR_CAPACITY: stream_start is filled, nothing else is written.
+ * Refused with EAO_ERR_INVALID: sample_size == 0, sample_size above the object's points, tree_count == 0, a non-finite coordinate (it breaks std::sort's
+ * ordering contract upstream: undefined behaviour), more than EAO_IFOREST_MAX_POINTS points (libstdc++'s shuffle takes its other path above), and an object on
+ * which upstream's own Build returns false (a split rounded above the maximum of its range, :167). */
+#define EAO_IFOREST_MAX_POINTS 65535
+#define EAO_OBJECT_IFOREST_TREES 50             /* src/Object.cc:1296 */
+#define EAO_OBJECT_IFOREST_SEED 12345           /* :1296 */
+#define EAO_OBJECT_IFOREST_MIN_POINTS 30        /* :1256 */
+#define EAO_OBJECT_IFOREST_EXEMPT_CLASS_A 75    /* :1245 */
+#define EAO_OBJECT_IFOREST_EXEMPT_CLASS_B 64
+#define EAO_OBJECT_IFOREST_EXEMPT_CLASS_C 65
+eao_status eao_iforest_scores_batch(int32_t n_obj, const int32_t* start /* n_obj+1 */, const float* xyz, const int32_t* tree_count /* n_obj */,
+                                    const uint32_t* seed /* n_obj */, const int32_t* sample_size /* n_obj */, double* scores, double* total_path_len,
+                                    uint8_t* stream, int64_t stream_cap, int64_t* stream_start /* n_obj+1 */);
+/* The whole of Object_Map::IsolationForestDeleteOutliers for a batch of objects: xyz = GetWorldPos() of mvpMapObjectMappoints in vector order, class_id =
+ * mnClass, bi_forest = the file-level flag biForest (:1241).  An object runs when bi_forest is set, its class is none of 75 / 64 / 65 (:1245) and it has at least
+ * 30 points (:1256); then Build(50, 12345, data, N / 2) (:1296) and a point is flagged when its score exceeds th = 0.6f, or 0.65f for class 62 (:1248-1250,
+ * :1317; th is a float promoted to double).  flags (one byte per point, indexed like the points): 1 = erase; removed (n_obj): the number flagged; scores
+ * (optional): the anomaly scores, -1.0 for the points of objects the rules skip.  Skipped objects come back without flags and cost no device work, and their
+ * points are not read.  An object on which upstream's Build returns false comes back without flags, as upstream leaves it.  A non-finite coordinate in an
+ * object that runs is EAO_ERR_INVALID for the whole call.  The caller erases exactly the flagged indices (upstream's own loop reads outliernum one past its
+ * end after the last outlier, :1336; include/eaofusion/ObjectMap.h does not). */
+eao_status eao_object_iforest_outliers_batch(int32_t n_obj, const int32_t* start /* n_obj+1 */, const float* xyz, const int32_t* class_id /* n_obj */,
+                                             int32_t bi_forest, uint8_t* flags, int32_t* removed /* n_obj */, double* scores);
+/* Diagnostic (tools/bench_isolation_forest.py): after eao_iforest_set_profiling(1) on this thread, the device time in ms of k_iforest_build and k_iforest_score of
+ * the thread's last forest call, from HIP events on its stream.  EAO_ERR_INVALID when there is no measurement. */
+eao_status eao_iforest_set_profiling(int32_t on);
+eao_status eao_iforest_last_kernel_ms(float* kernel_ms /* 2 */);
+/* The same measurement inside k_iforest_build: the mean over the trees of the last call, in microseconds of the device's constant clock, of seeding the
+ * generator, of the shuffle with the copy of the sample, and of the depth-first walk. */
+eao_status eao_iforest_last_stage_us(double* stage_us /* 3 */);
+
 /* The value of EAO_ABI_VERSION the library was built with. Bumped whenever an entry point's parameter list or a struct's layout changes (round 3
  * changed eao_tracker_track_local_map and eao_track_result in place); a caller compiled against another version must not call into the library.
  * Result structs are zero-initialised by the caller (`eao_track_result R = {0};`) before their array pointers are set: a pointer member the
