@@ -298,6 +298,11 @@ SYMBOLS = {
     "eao_iforest_set_profiling": (_I, [_I]),
     "eao_iforest_last_kernel_ms": (_I, [_P]),
     "eao_iforest_last_stage_us": (_I, [_P]),
+    "eao_object_np_counts_batch": (_I, [_I, _P, _P, _I, _P, _P, _P, _I, _P, _P, _P, _P]),
+    "eao_object_np_association_batch": (_I, [_I, _P, _P, _I, _P, _P, _P, _I, _P, _P, _P, _P, _P]),
+    "eao_object_project_rects_batch": (_I, [_I, _P, _P, _P] + [C.c_float] * 4 + [_I, _I, _P, _P, _P]),
+    "eao_object_assoc_set_profiling": (_I, [_I]),
+    "eao_object_assoc_last_kernel_ms": (_I, [_P]),
     "eao_bundle_adjustment_plan": (_I, [_I, _I, _P, _P, _I, _P, _P, _P, _I, _P, _I, _P, _I, _P, _I, _P, _I, _P, _I]),
 }
 

@@ -1374,6 +1374,60 @@ eao_status eao_iforest_last_kernel_ms(float* kernel_ms /* 2 */);
  * generator, of the shuffle with the copy of the sample, and of the depth-first walk. */
 eao_status eao_iforest_last_stage_us(double* stage_us /* 3 */);
 
+/* ---- Object layer: the per-frame data association of Tracking step 10 (src/Tracking.cc:2036-2069) -----------------------------------------------------------
+ * Object_2D::NoParaDataAssociation (src/Object.cc:728-962; called for one detection against every map object of its class, :260-277): the Wilcoxon rank-sum
+ * test of a detection's map points against a map object's, and Object_Map::ComputeProjectRectFrame (:1606-1651; called per object at src/Tracking.cc:2049): the
+ * bounding box of an object's projected points.  Both are pure functions of point lists and both are exact: integer counts, and the cv::Mat arithmetic
+ * convention of DESIGN.md section 2 (csrc/object_assoc_internal.h).  The entries are stateless; each host thread has its own stream and
+ * staging.  EAO_ERR_INVALID leaves every output untouched.  Two calls on the same arguments return the same bytes, on one thread or on several.
+ *
+ * The lists: detection d owns points det_start[d] .. det_start[d+1] - 1 of det_xyz, map object j points map_start[j] .. map_start[j+1] - 1 of map_xyz (3 floats
+ * each; starts >= 0 and ascending).  They hold the GOOD points only -- not isBad() and not out_point (:737, :751) -- gathered in vector order; map_total[j] is
+ * mvpMapObjectMappoints.size() with the bad ones, which upstream's sampling step is computed from (:779), so map_total[j] >= the list's length.  Pair p tests
+ * detection pair_det[p] against map object pair_map[p]; pairs may repeat.
+ *
+ * eao_object_np_counts_batch: per pair mns = {m, n, step} and counts = {w_x_12, w_x_21, w_x_00, w_y_.., w_z_..} of :830-923 as integers (upstream's float counters
+ * hold the same values: m * n < 2^24 under the bound below).  m = the detection's points, nGood = the map object's.
+ *   m < 20 (:760) or otherwise nGood < 20 (:764)   n = nGood, step = 0 (upstream has not declared step), counts = 0
+ *   nGood <= 3 m                                   n = nGood, step = 1 (:775, :826)
+ *   nGood > 3 m                                    step = map_total / (3 m) (:779), n = ceil(nGood / step) (:802-808)
+ *   m n (m + n + 1) > INT32_MAX                    n and step as in the two rows above, counts = 0: upstream's int product at :942 overflows (undefined)
+ * eao_object_np_association_batch: per pair upstream's return value -- 0 (m < 20: go on with the t-tests), 1 (associated), 2 (failed, nGood < 20 included) -- or
+ * EAO_OBJECT_NP_UNDEFINED where the int product overflows; the other pairs of the call are unaffected.  w (optional, 3 per pair) = w_x, w_y, w_z of :930-932 and
+ * r (optional, 2 per pair) = r1, r2 of :942-943; zero for the pairs the counts do not decide.  Those pairs cost no device work and their points are not read.
+ * Refused with EAO_ERR_INVALID: a negative count, starts that do not ascend, map_total below the list's length, a pair index out of range, and a NaN
+ * coordinate in a list that a pair whose counts decide reads (upstream would count such a value in none of its three counters; infinities compare normally). */
+#define EAO_OBJECT_NP_MIN_DET_POINTS 20         /* src/Object.cc:760 */
+#define EAO_OBJECT_NP_MIN_MAP_POINTS 20         /* :764 */
+#define EAO_OBJECT_NP_SAMPLE_RATIO 3            /* :776 */
+#define EAO_OBJECT_NP_CRITICAL 1.282            /* :942 */
+#define EAO_OBJECT_NP_VARIANCE_DIVISOR 12       /* :942 */
+#define EAO_OBJECT_NP_HALF 0.5                  /* :942 */
+#define EAO_OBJECT_NP_UNDEFINED 3
+eao_status eao_object_np_counts_batch(int32_t n_det, const int32_t* det_start /* n_det+1 */, const float* det_xyz, int32_t n_map,
+                                      const int32_t* map_start /* n_map+1 */, const float* map_xyz, const int32_t* map_total /* n_map */, int32_t n_pair,
+                                      const int32_t* pair_det, const int32_t* pair_map, int32_t* mns /* n_pair x 3 */, uint32_t* counts /* n_pair x 9 */);
+eao_status eao_object_np_association_batch(int32_t n_det, const int32_t* det_start /* n_det+1 */, const float* det_xyz, int32_t n_map,
+                                           const int32_t* map_start /* n_map+1 */, const float* map_xyz, const int32_t* map_total /* n_map */, int32_t n_pair,
+                                           const int32_t* pair_det, const int32_t* pair_map, int32_t* verdict /* n_pair */, float* w /* n_pair x 3 */,
+                                           float* r /* n_pair x 2 */);
+/* Object_Map::ComputeProjectRectFrame for a batch of map objects under one pose: map_xyz = GetWorldPos() of ALL of mvpMapObjectMappoints in vector order (the
+ * function does not filter), Tcw = mCurrentFrame.mTcw (4x4 row-major), fx .. cy = the frame's intrinsics, cols and rows = the image's.  Per object rect = {x, y,
+ * width, height} of mRectProject (:1650) and status:
+ *   0  no points: upstream returns at :1631 and rect is untouched
+ *   1  rect is written
+ *   2  upstream is undefined and rect is untouched: a projection is a NaN (std::sort's ordering contract at :1634), or a clamped value (:1641-1648) or a
+ *      difference of two lies outside int, where cv::Rect's float -> int conversion is undefined.  An infinite projection (z = 0 with x != 0) is defined.
+ * uv (optional, 2 floats per point, indexed like the points): u and v of :1623-1624.  Refused with EAO_ERR_INVALID: a negative count, starts that do not
+ * ascend. */
+eao_status eao_object_project_rects_batch(int32_t n_map, const int32_t* map_start /* n_map+1 */, const float* map_xyz, const float* Tcw /* 16 */, float fx, float fy,
+                                          float cx, float cy, int32_t cols, int32_t rows, int32_t* rect /* n_map x 4 */, uint8_t* status /* n_map */, float* uv);
+/* Diagnostic (tools/bench_object_association.py): after eao_object_assoc_set_profiling(1) on this thread, the device time in ms of k_np_counts in the thread's
+ * last rank-sum call that reached the device and of k_project_rects in its last rect call, from HIP events on its stream; -1 for a kernel that has not run
+ * since.  EAO_ERR_INVALID when there is no measurement at all. */
+eao_status eao_object_assoc_set_profiling(int32_t on);
+eao_status eao_object_assoc_last_kernel_ms(float* kernel_ms /* 2 */);
+
 /* The value of EAO_ABI_VERSION the library was built with. Bumped whenever an entry point's parameter list or a struct's layout changes (round 3
  * changed eao_tracker_track_local_map and eao_track_result in place); a caller compiled against another version must not call into the library.
  * Result structs are zero-initialised by the caller (`eao_track_result R = {0};`) before their array pointers are set: a pointer member the
