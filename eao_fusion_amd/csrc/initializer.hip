@@ -41,7 +41,7 @@ using eao::init::kMaxMotions;
 
 namespace {
 
-// ---- Initializer's literals (tests/golden/initializer_constants.json, read from the reference text by tools/gen_initializer_constants.py; held to it by
+// ---- Initializer's literals (tests/golden/initializer_constants.json, read from the reference text by tools/reference_literals.py; held to it by
 // tests/test_initializer_reference_cpu.py).  Nothing else in this file spells them.  (1.0 and 50 of :116 / :118 are the adapter's: include/eaofusion/Initializer.h.)
 constexpr double kRatioH = 0.40;                // src/Initializer.cc:115  RH>0.40
 constexpr float kChi2H = 5.991;                 // :333  const float th = 5.991;   :409  const float thScore = 5.991;

@@ -20,7 +20,7 @@
 namespace eao {
 namespace pnp {
 
-// ---- PnPsolver's literals (tests/golden/pnp_solver_constants.json, read from the reference text by tools/gen_pnp_solver_constants.py; held to it by
+// ---- PnPsolver's literals (tests/golden/pnp_solver_constants.json, read from the reference text by tools/reference_literals.py; held to it by
 // tests/test_pnp_solver_reference_cpu.py).  Nothing else in this file spells them.
 // pnp-constants-begin
 constexpr int kGaussNewtonIterations = 5;      // iterations_number

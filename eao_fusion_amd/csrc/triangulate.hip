@@ -20,7 +20,7 @@
 
 namespace {
 
-// ---- the loop's literals (tests/golden/triangulation_constants.json, read from the reference text by tools/gen_triangulation_constants.py; held to it by
+// ---- the loop's literals (tests/golden/triangulation_constants.json, read from the reference text by tools/reference_literals.py; held to it by
 // tests/test_triangulation_reference_cpu.py).  Nothing else in this file spells them.
 constexpr double kLowParallaxCos = 0.9998;      // src/LocalMapping.cc:323  cosParallaxRays<0.9998
 constexpr double kChi2Mono = 5.991;             // :378, :404  > 5.991*sigmaSquare

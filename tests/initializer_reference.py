@@ -8,17 +8,20 @@ The null-vector / SVD step comes in three variants:
   f64        numpy's float64 SVD of the float A, rounded to float,
   f64jacobi  the eigenvector of A^T A (double, from the float A) by cyclic Jacobi with the device's sweep counts, rounded to float.
 The score comes as the exact double sum rounded once (`double`, the library's) and as upstream's sequential float sum (`float`)."""
-import json
 import os
+import sys
 
 import numpy as np
+
+sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tools"))
+from reference_literals import literals  # noqa: E402
 
 f32, f64 = np.float32, np.float64
 VARIANTS = ("f32", "f64", "f64jacobi")
 BRANCH_H, BRANCH_F = 0, 1
 SWEEPS = {3: 8, 4: 8, 9: 12}      # csrc/small_dense.h
 
-_C = {c["name"]: c["literal"] for c in json.load(open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "initializer_constants.json")))["constants"]}
+_C = literals("initializer")
 RATIO_H = float(_C["RATIO_H"])
 CHI2_H, CHI2_F, CHI2_SCORE = f32(_C["CHI2_H"]), f32(_C["CHI2_F"]), f32(_C["CHI2_SCORE"])
 COS_PARALLAX = float(_C["COS_PARALLAX"])

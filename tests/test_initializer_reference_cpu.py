@@ -2,9 +2,8 @@
 
 Noise-free scenes: the yardstick recovers the true H (planar), the true F up to scale and the true (R, t / |t|), in all three variants; the eight H-decompositions and the
 four E-decompositions each contain the truth.  The draw loop reproduces a recorded rand() sequence through a stub generator.  Each irregular family reaches the line it
-claims.  The conditions of the bands hold on the friendly families; tests/initializer_tolerances.py equals profiles/initializer_bands.txt; the constants fixture equals
-the reference text (when EAO_REFERENCE_DIR names the reference tree), the kernel's constant block and the adapter's defaults."""
-import json
+claims.  The conditions of the bands hold on the friendly families; tests/initializer_tolerances.py equals profiles/initializer_bands.txt; the constants fixture (held to the
+reference text by tests/test_reference_literals.py) equals the kernel's constant block and the adapter's defaults."""
 import os
 import re
 import sys
@@ -19,6 +18,7 @@ import initializer_tolerances as T
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "tools"))
 import initializer_bands as B      # noqa: E402
+from reference_literals import literals  # noqa: E402
 
 PLANE = (0.9, -0.2)
 
@@ -210,24 +210,8 @@ def test_workload_scene_outcome():
     assert r["returned"] and r["branch"] == R.BRANCH_F and abs(float(r["RH"]) - R.RATIO_H) >= T.RH_CLEARANCE
 
 
-def _fixture():
-    return json.load(open(os.path.join(ROOT, "tests", "golden", "initializer_constants.json")))["constants"]
-
-
-def test_constants_equal_reference_text():
-    import gen_initializer_constants as G
-    fix = _fixture()
-    assert [(e["name"], e["where"]) for e in fix] == [(n, "%s:%d" % (G.REL, line)) for n, line, _rx in G.SPEC]
-    # EAO_REFERENCE_DIR: the project's convention (tests/test_triangulation_reference_cpu.py) -- whoever has a checkout of the reference tree sets it to that
-    # directory when running the suite or regenerating the fixture; the repository names no path outside itself, so without it only the fixture's shape is held
-    ref = os.environ.get("EAO_REFERENCE_DIR")
-    if not ref:
-        pytest.skip("EAO_REFERENCE_DIR does not name a reference tree")
-    assert G.parse(ref) == fix
-
-
 def test_kernel_and_adapter_spell_the_fixture():
-    c = {e["name"]: e["literal"] for e in _fixture()}
+    c = literals("initializer")      # (held to the reference text by tests/test_reference_literals.py)
     src = open(os.path.join(ROOT, "eao_fusion_amd", "csrc", "initializer.hip")).read()
     block = src[src.index("// ---- Initializer's literals"):src.index("// ----\n")]
     got = dict(re.findall(r"constexpr \w+ (k\w+) = ([0-9.]+);", block))

@@ -2,7 +2,6 @@
 (tests/golden/isolation_forest/*.npz, written by tools/gen_golden_isolation_forest.py): both restated builds to the recorded Serialize bytes, the scores, the
 branch each scene is named for, the gap around the thresholds, the literals, and generate_canonical's clamp."""
 import hashlib
-import json
 import os
 import re
 import subprocess
@@ -15,6 +14,9 @@ import isolation_forest_reference as Y
 import isolation_forest_scenes as SC
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.join(ROOT, "tools"))
+from reference_literals import literals  # noqa: E402
+
 GOLD = os.path.join(ROOT, "tests", "golden", "isolation_forest")
 SCENES = SC.scenes()
 SORTED_FORM_MAX = 300      # the literal, sorting build restated in Python is held on every scene up to this size
@@ -173,8 +175,7 @@ def test_lds_edge_scenes_sit_on_the_header_budget():
 
 
 def test_constants():
-    fix = json.load(open(os.path.join(ROOT, "tests", "golden", "isolation_forest_constants.json")))["constants"]
-    lit = {c["name"]: c["literal"] for c in fix}
+    lit = literals("isolation_forest")      # (held to the reference text by tests/test_reference_literals.py)
     assert (int(lit["TREE_COUNT"]), int(lit["SEED"]), int(lit["MIN_POINTS"]), int(lit["SAMPLE_DIVISOR"])) == (Y.TREE_COUNT, Y.SEED, Y.MIN_POINTS, Y.SAMPLE_DIVISOR)
     assert (int(lit["EXEMPT_CLASS_A"]), int(lit["EXEMPT_CLASS_B"]), int(lit["EXEMPT_CLASS_C"])) == Y.EXEMPT_CLASSES
     assert (float(lit["THRESHOLD"]), int(lit["THRESHOLD_CLASS"]), float(lit["THRESHOLD_OF_CLASS"])) == (Y.THRESHOLD, Y.THRESHOLD_CLASS, Y.THRESHOLD_OF_CLASS)
@@ -185,6 +186,5 @@ def test_constants():
                  "kThresholdClass = %s;" % lit["THRESHOLD_CLASS"], "kThresholdOfClass = %sf;" % lit["THRESHOLD_OF_CLASS"]):
         assert want in hdr, want
     ref = os.environ.get("EAO_REFERENCE_DIR")
-    if ref and os.path.isdir(ref):      # with the reference tree at hand: the fixtures against the text and the header themselves
-        subprocess.check_call([sys.executable, os.path.join(ROOT, "tools", "gen_isolation_forest_constants.py"), ref, "--check"])
+    if ref and os.path.isdir(ref):      # with the reference tree at hand: the golden files against the header itself
         subprocess.check_call([sys.executable, os.path.join(ROOT, "tools", "gen_golden_isolation_forest.py"), ref, "--check"])

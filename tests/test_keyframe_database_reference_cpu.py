@@ -3,6 +3,7 @@ a hand-computed example, every scene reaching the branch it claims, the float-ag
 neighbours against the reference text."""
 import os
 import re
+import sys
 
 import numpy as np
 import pytest
@@ -11,6 +12,8 @@ import keyframe_database_reference as Y
 import keyframe_database_scenes as SC
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.join(ROOT, "tools"))
+from reference_literals import literals  # noqa: E402
 
 
 def test_hand_computed_example():
@@ -52,16 +55,25 @@ def test_yardstick_state_follows_upstream():
     assert not R[0]["res"]["sharing_id"]
 
 
+def test_header_and_yardstick_spell_the_fixture():
+    lit = literals("keyframe_database")
+    assert set(lit) == {"MIN_COMMON_WORDS_FACTOR", "MIN_SCORE_TO_RETAIN_FACTOR", "N_NEIGHBOURS"}
+    hdr = open(os.path.join(ROOT, "eao_fusion_amd", "csrc", "keyframe_db_internal.h")).read()
+    assert "maxCommonWords * %s" % lit["MIN_COMMON_WORDS_FACTOR"] in hdr and "%s * bestAccScore" % lit["MIN_SCORE_TO_RETAIN_FACTOR"] in hdr
+    assert Y.N_NEIGHBOURS == int(lit["N_NEIGHBOURS"])
+
+
 def test_literals_equal_the_reference_text():
+    """What the fixture's six rows do not say: each literal stands at no third site, bestAccScore starts where upstream starts it, and the KeyFrame
+    constructor leaves the scores unset."""
     ref = os.environ.get("EAO_REFERENCE_DIR")
     if not ref or not os.path.exists(os.path.join(ref, "src", "KeyFrameDatabase.cc")):
         pytest.skip("EAO_REFERENCE_DIR does not name a reference tree")
+    lit = {k: re.escape(v) for k, v in literals("keyframe_database").items()}
     src = open(os.path.join(ref, "src", "KeyFrameDatabase.cc")).read()
-    assert len(re.findall(r"int minCommonWords = maxCommonWords\*0\.8f;", src)) == 2
-    assert len(re.findall(r"float minScoreToRetain = 0\.75f\*bestAccScore;", src)) == 2
-    assert len(re.findall(r"GetBestCovisibilityKeyFrames\(10\)", src)) == 2 and Y.N_NEIGHBOURS == 10
+    assert len(re.findall(r"int minCommonWords = maxCommonWords\*%s;" % lit["MIN_COMMON_WORDS_FACTOR"], src)) == 2
+    assert len(re.findall(r"float minScoreToRetain = %s\*bestAccScore;" % lit["MIN_SCORE_TO_RETAIN_FACTOR"], src)) == 2
+    assert len(re.findall(r"GetBestCovisibilityKeyFrames\(%s\)" % lit["N_NEIGHBOURS"], src)) == 2
     assert "float bestAccScore = minScore;" in src and "float bestAccScore = 0;" in src
-    hdr = open(os.path.join(ROOT, "eao_fusion_amd", "csrc", "keyframe_db_internal.h")).read()
-    assert "maxCommonWords * 0.8f" in hdr and "0.75f * bestAccScore" in hdr
     kf = open(os.path.join(ref, "src", "KeyFrame.cc")).read()
     assert "mnLoopQuery(0), mnLoopWords(0), mnRelocQuery(0), mnRelocWords(0)" in kf and "mLoopScore(" not in kf and "mRelocScore(" not in kf

@@ -2,7 +2,6 @@
 Object_Map::ComputeProjectRectFrame, and a sort-free / vectorised form of each) on its own: every scene reaches the branch it is named for, the two forms
 agree on every scene and on a few hundred random small cases, the float counters stay exact under the overflow bound, the literals are the reference text's, and
 the golden files are what the yardstick computes."""
-import json
 import os
 import re
 import subprocess
@@ -15,6 +14,9 @@ import object_association_reference as Y
 import object_association_scenes as SC
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.join(ROOT, "tools"))
+from reference_literals import literals  # noqa: E402
+
 GOLD = os.path.join(ROOT, "tests", "golden", "object_association")
 NP_SCENES, RECT_SCENES = SC.np_scenes(), SC.rect_scenes()
 CAM = ("fx", "fy", "cx", "cy", "cols", "rows")
@@ -134,8 +136,7 @@ def test_rect_scene_reaches_its_branch_and_both_forms_agree(name):
 
 
 def test_constants():
-    fix = json.load(open(os.path.join(ROOT, "tests", "golden", "object_association_constants.json")))["constants"]
-    lit = {c["name"]: c["literal"] for c in fix}
+    lit = literals("object_association")      # (held to the reference text by tests/test_reference_literals.py)
     assert (int(lit["MIN_DET_POINTS"]), int(lit["MIN_MAP_POINTS"]), int(lit["SAMPLE_RATIO"]), int(lit["SAMPLE_RATIO_N"])) == (Y.MIN_DET_POINTS, Y.MIN_MAP_POINTS,
                                                                                                                               Y.SAMPLE_RATIO, Y.SAMPLE_RATIO)
     assert (float(lit["HALF"]), float(lit["CRITICAL"]), int(lit["VARIANCE_DIVISOR"])) == (Y.HALF, Y.CRITICAL, Y.VARIANCE_DIVISOR)
@@ -149,9 +150,6 @@ def test_constants():
     for name, key in (("MIN_DET_POINTS", "MIN_DET_POINTS"), ("MIN_MAP_POINTS", "MIN_MAP_POINTS"), ("SAMPLE_RATIO", "SAMPLE_RATIO"), ("CRITICAL", "CRITICAL"),
                       ("VARIANCE_DIVISOR", "VARIANCE_DIVISOR"), ("HALF", "HALF")):
         assert re.search(r"#define EAO_OBJECT_NP_%s %s\s" % (name, re.escape(lit[key])), header), name
-    ref = os.environ.get("EAO_REFERENCE_DIR")
-    if ref and os.path.isdir(ref):      # with the reference tree at hand: the fixture against the text itself
-        subprocess.check_call([sys.executable, os.path.join(ROOT, "tools", "gen_object_association_constants.py"), ref, "--check"])
 
 
 def test_golden_files_are_the_yardsticks():

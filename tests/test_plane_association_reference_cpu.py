@@ -1,9 +1,9 @@
 """The yardstick of the plane association (tests/plane_association_reference.py) held to what every scene of tests/plane_association_scenes.py claims -- the
 branch the scene was built for is the branch the reference's loops take --, its vectorised form held equal to the literal loops bit for bit, and the three
 literals (mfDisTh, mfAngleTh, the 100 of PointDistanceFromPlane) held to the reference text through tests/golden/plane_association_constants.json."""
-import json
 import os
 import re
+import sys
 
 import numpy as np
 import pytest
@@ -12,6 +12,8 @@ import plane_association_reference as Y
 import plane_association_scenes as SC
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.join(ROOT, "tools"))
+from reference_literals import literals  # noqa: E402
 
 
 def bits(a):
@@ -82,8 +84,7 @@ def test_model_compacts_past_half():
 
 
 def test_literals_match_the_reference_text():
-    fix = json.load(open(os.path.join(ROOT, "tests", "golden", "plane_association_constants.json")))["constants"]
-    lit = {c["name"]: c["literal"] for c in fix}
+    lit = literals("plane_association")      # (held to the reference text by tests/test_reference_literals.py)
     assert set(lit) == {"DIS_TH", "ANGLE_TH", "NO_DISTANCE"}
     assert np.float32(float(lit["DIS_TH"])) == Y.DIS_TH and np.float32(float(lit["ANGLE_TH"])) == Y.ANGLE_TH and np.float32(float(lit["NO_DISTANCE"])) == Y.NO_DISTANCE
     hdr = open(os.path.join(ROOT, "include", "eao_fusion.h")).read()
@@ -96,8 +97,3 @@ def test_literals_match_the_reference_text():
     assert "DIS_TH = %s " % lit["DIS_TH"] in py and "ANGLE_TH = %s " % lit["ANGLE_TH"] in py and "NO_DISTANCE = %s.0 " % lit["NO_DISTANCE"] in py
     adapter = open(os.path.join(ROOT, "include", "eaofusion", "MapPlanes.h")).read()
     assert "EAO_PLANE_MAP_DIS_TH" in adapter and "EAO_PLANE_MAP_ANGLE_TH" in adapter
-    ref = os.environ.get("EAO_REFERENCE_DIR")
-    if ref and os.path.isdir(ref):      # with the reference tree at hand: the fixture against the text itself
-        for c in fix:
-            rel, line = c["where"].rsplit(":", 1)
-            assert c["literal"] in open(os.path.join(ref, rel), errors="replace").read().split("\n")[int(line) - 1]

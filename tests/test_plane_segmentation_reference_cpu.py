@@ -1,15 +1,11 @@
 """The yardstick of the plane segmentation (tests/plane_segmentation_reference.py) held to itself, without a device: every scene of
 tests/plane_segmentation_scenes.py reaches the branch it claims; both eigen-solve variants (the chosen Jacobi and numpy.linalg.eigh) give the same block flags,
 merge sequence, membership image and kept set on every scene; the vectorised forms equal the literal loops; the literals are the reference text's
-(tests/golden/plane_segmentation_constants.json); the golden files are what the yardstick computes.
-
-The fixture is compared with the reference text itself only when EAO_REFERENCE_DIR names a reference tree (a clean checkout has none: the repository stands
-alone), as in the other features' constants tests; otherwise the literals are held to the committed fixture, which tools/gen_plane_segmentation_constants.py
-writes from, and with --check compares against, the reference text."""
-import json
+(tests/golden/plane_segmentation_constants.json, held to that text by tests/test_reference_literals.py); the golden files are what the yardstick computes."""
 import math
 import os
 import re
+import sys
 
 import numpy as np
 import pytest
@@ -18,6 +14,9 @@ import plane_segmentation_reference as R
 import plane_segmentation_scenes as SC
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.join(ROOT, "tools"))
+from reference_literals import literals  # noqa: E402
+
 SCENES = SC.scenes()
 _runs = {}
 
@@ -136,8 +135,7 @@ def test_voxel_grid_by_hand():
 
 
 def test_literals_match_the_reference_text():
-    fix = json.load(open(os.path.join(ROOT, "tests", "golden", "plane_segmentation_constants.json")))["constants"]
-    lit = {c["name"]: c["literal"] for c in fix}
+    lit = literals("plane_segmentation")      # (held to the reference text by tests/test_reference_literals.py)
     c = R.default_cfg()
     assert (c.depth_max, c.depth_min, float(c.leaf)) == (float(lit["DEPTH_MAX"]), float(lit["DEPTH_MIN"]), float(np.float32(float(lit["LEAF"]))))
     assert (R.SEEN_DIST, R.SEEN_ANGLE) == (float(lit["SEEN_DIST"]), float(lit["SEEN_ANGLE"]))
@@ -171,11 +169,6 @@ def test_literals_match_the_reference_text():
     import ctypes
     from eao_fusion_amd import _lib
     assert ctypes.sizeof(_lib.PlaneSegCfg) == 144 and ctypes.sizeof(_lib.PlaneSegPlane) == 104
-    ref = os.environ.get("EAO_REFERENCE_DIR")
-    if ref and os.path.isdir(ref):      # with the reference tree at hand: the fixture against the text itself
-        for c in fix:
-            rel, line = c["where"].rsplit(":", 1)
-            assert c["literal"] in open(os.path.join(ref, rel), errors="replace").read().split("\n")[int(line) - 1]
 
 
 @pytest.mark.parametrize("name", list(SCENES))

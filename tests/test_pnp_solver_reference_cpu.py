@@ -6,8 +6,7 @@ Two findings shape those tests, and this file keeps them true:
      min_set >= 6 only; at 4 the device tests hold the replay, the sequential rule, Refine on the device's own set, and the outcome on exact-inlier scenes.
   2. From six points up the variants agree to 1e-9 or better ONCE the sign of the PCA axes is fixed (sign_rows); one ulp on the inputs then moves a pose by about 1e-6.
 Also: tests/pnp_solver_tolerances.py equals profiles/pnp_solver_bands.txt; the literal upstream loop (Refine at every gate-passing hypothesis) and the once-per-record
-form the device computes give identical results; the special lines are reached; the constants fixture equals the reference text, kernel, yardstick and adapter."""
-import json
+form the device computes give identical results; the special lines are reached; the constants fixture (held to the reference text by tests/test_reference_literals.py) equals kernel, yardstick and adapter."""
 import os
 import re
 import sys
@@ -21,6 +20,8 @@ import pnp_solver_tolerances as T
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "tools"))
+from reference_literals import literals  # noqa: E402
+
 NAMES = [name for name, _ in SC.all_families()]
 _runs = {}
 
@@ -183,23 +184,8 @@ def test_ransac_parameters(args, want):
     assert Y.ransac_parameters(*args) == want
 
 
-def _fixture():
-    return json.load(open(os.path.join(ROOT, "tests", "golden", "pnp_solver_constants.json")))["constants"]
-
-
-def test_constants_equal_reference_text():
-    import gen_pnp_solver_constants as G
-    fix = _fixture()
-    assert [(e["name"], e["where"]) for e in fix] == [(n, "%s:%d" % (rel, line)) for n, rel, line, _rx, _g in G.SPEC]
-    # EAO_REFERENCE_DIR: the project's convention (tests/test_triangulation_reference_cpu.py) -- whoever has a checkout of the reference tree sets it
-    ref = os.environ.get("EAO_REFERENCE_DIR")
-    if not ref:
-        pytest.skip("EAO_REFERENCE_DIR does not name a reference tree")
-    assert G.parse(ref) == fix
-
-
 def test_kernel_yardstick_and_adapter_spell_the_fixture():
-    c = {e["name"]: e["literal"] for e in _fixture()}
+    c = literals("pnp_solver")      # (held to the reference text by tests/test_reference_literals.py)
     src = open(os.path.join(ROOT, "eao_fusion_amd", "csrc", "pnp_internal.h")).read()
     block = src[src.index("// pnp-constants-begin"):src.index("// pnp-constants-end")]
     got = dict(re.findall(r"constexpr \w+ (k\w+) = ([0-9.]+f?);", block))

@@ -1,9 +1,8 @@
 """The thresholds, chi2 gates, Huber deltas and iteration schedules of the hot path are DATA taken from the reference's text
 (tools/gen_ref_constants.py -> tests/golden/ref_constants.json + two generated .inc files), the way the rBRIEF pattern table is
-(VERDICT r2 next #2d).  Checked here: the fixture equals the reference text where it is present; both generated headers equal the
-fixture; oracle AND product consume the named constants (no stray literal copies in the kernels or the oracle); the adapters
+(VERDICT r2 next #2d).  Checked here: the fixture carries the generator's types and notes (tests/test_reference_literals.py holds it to
+the reference text); both generated headers equal the fixture; oracle AND product consume the named constants (no stray literal copies in the kernels or the oracle); the adapters
 and the Python mirror carry the same numbers."""
-import json
 import os
 import re
 import sys
@@ -11,7 +10,10 @@ import sys
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-FIX = json.load(open(os.path.join(ROOT, "tests", "golden", "ref_constants.json")))["constants"]
+sys.path.insert(0, os.path.join(ROOT, "tools"))
+from reference_literals import load  # noqa: E402
+
+FIX = load("ref")
 BY_NAME = {e["name"]: e for e in FIX}
 INC = {"product": os.path.join(ROOT, "eao_fusion_amd", "csrc", "ref_constants.inc"), "oracle": os.path.join(ROOT, "oracle", "ref_constants.inc")}
 
@@ -24,21 +26,14 @@ def _parse_inc(path):
     return out
 
 
-def test_fixture_equals_reference_text_when_present():
-    """Every entry of the fixture is what tools/gen_ref_constants.py records for its SPEC row: same name, type, file:line and note, in SPEC's
-    order; a literal of the form the row's regular expression captures; the value parse() derives from it.  With a reference tree named by
-    EAO_REFERENCE_DIR, re-parsing its text gives the same entries."""
-    sys.path.insert(0, os.path.join(ROOT, "tools"))
+def test_fixture_carries_the_typed_table():
+    """Every entry of the fixture carries what tools/gen_ref_constants.py adds to its row of the text (name, literal and file:line are held by
+    tests/test_reference_literals.py): the type and the note of TYPED, in TYPED's order, and the value typed() derives from the literal."""
     import gen_ref_constants as G
-    assert [(e["name"], e["type"], e["where"], e["note"]) for e in FIX] == [(n, t, "%s:%d" % (rel, line), note) for n, t, rel, line, _rx, note in G.SPEC]
-    for e, (name, ctype, _rel, _line, rx, _note) in zip(FIX, G.SPEC):
-        group = re.search(r"(?<!\\)\(((?:\\.|[^()\\])*)\)", rx).group(1)      # the row's one capture group
-        assert re.fullmatch(group, e["literal"]), (name, group, e["literal"])
-        assert e["value"] == (int(e["literal"]) if ctype == "int" else float(e["literal"])) and type(e["value"]) is (int if ctype == "int" else float), name
-    ref = os.environ.get("EAO_REFERENCE_DIR")
-    if ref:
-        now = G.parse(ref)
-        assert [(e["name"], e["literal"], e["where"]) for e in now] == [(e["name"], e["literal"], e["where"]) for e in FIX]
+    assert [(e["name"], e["type"], e["note"]) for e in FIX] == G.TYPED
+    assert G.typed([{k: e[k] for k in ("name", "literal", "where")} for e in FIX]) == FIX
+    for e in FIX:
+        assert type(e["value"]) is (int if e["type"] == "int" else float), e["name"]
 
 
 @pytest.mark.parametrize("who", ["product", "oracle"])

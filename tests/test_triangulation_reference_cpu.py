@@ -1,7 +1,6 @@
 """CPU: the triangulation yardstick (tests/triangulation_reference.py) and its scenes (tests/triangulation_scenes.py) hold what they claim; the bands file, the
 tolerances and the probe agree; the loop's literals in the kernel's constant block, the yardstick and the adapter are those of the reference text; the header, the
 ctypes mirror and the golden files carry the feature."""
-import json
 import os
 import re
 import sys
@@ -12,6 +11,7 @@ import pytest
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 sys.path.insert(0, os.path.join(ROOT, "tools"))
+from reference_literals import literals  # noqa: E402
 import triangulation_reference as Y  # noqa: E402
 import triangulation_scenes as S  # noqa: E402
 import triangulation_tolerances as T  # noqa: E402
@@ -121,17 +121,8 @@ def test_bands_file_tolerances_and_probe_agree():
 
 
 def test_the_loops_literals_are_the_reference_text():
-    fix = json.load(open(os.path.join(ROOT, "tests", "golden", "triangulation_constants.json")))["constants"]
-    assert all(set(e) == {"name", "literal", "where"} for e in fix)
-    lit = {}
-    for e in fix:
-        assert lit.setdefault(e["name"], e["literal"]) == e["literal"]
+    lit = literals("triangulation")      # (held to the reference text by tests/test_reference_literals.py)
     assert set(lit) == {"RATIO_FACTOR_BASE", "LOW_PARALLAX_COS", "CHI2_MONO", "CHI2_STEREO"}
-    import gen_triangulation_constants as G
-    assert [(e["name"], e["where"]) for e in fix] == [(n, "%s:%d" % (G.REL, line)) for n, line, _rx in G.SPEC]
-    ref = os.environ.get("EAO_REFERENCE_DIR")
-    if ref:
-        assert G.parse(ref) == fix
     # the yardstick
     for name, literal in lit.items():
         assert getattr(Y, name) == float(literal), name
