@@ -126,6 +126,65 @@ struct ThreadStream {
     }
 };
 
+// The end of a call on a thread's stream.  Whatever a call enqueues reads and writes the thread's staging block and device arena, and the next call on the thread
+// rewrites both: nothing returns before the stream is empty.  Constructed right before the call's first enqueue (upload, memset or launch) and alive to the end of the
+// call, so every EAO_HIP / EAO_REQUIRE return in between drains the stream on its way out (result ignored: the call already has its error).  wait() is the call's
+// final wait and disarms; a call that waits mid-way and enqueues again uses wait_more(), which leaves the guard armed; disarm() is for the one call that sees the end
+// of its last kernel without a stream wait (the done word of keyframe.hip).  The kind of each wait is the site's own choice: Latency polls first and stamps the
+// process-wide latency marker (wait_latency above), Block is a plain hipStreamSynchronize.
+struct Drain {
+    enum Kind { Latency, Block };
+    explicit Drain(hipStream_t s) : stream(s) {}
+    Drain(const Drain&) = delete; Drain& operator=(const Drain&) = delete;
+    ~Drain() { if (armed) (void)hipStreamSynchronize(stream); }
+    hipError_t wait_more(Kind k) { return k == Latency ? wait_latency(stream) : hipStreamSynchronize(stream); }
+    hipError_t wait(Kind k) { armed = false; return wait_more(k); }
+    void disarm() { armed = false; }
+private:
+    hipStream_t stream;
+    bool armed = true;
+};
+
+// Times each of the N kernels of this thread's last call (a diagnostic of the bench tools): N+1 marks around the launches, read() after the call.  A diagnostic cannot
+// fail a product call: when an event call fails, that measurement is lost and the sticky error is cleared, so that the call's own hipGetLastError() does not take it
+// for a launch error.  Results stay until the next arm(); a slot whose two marks were not both recorded in a call keeps what it had (-1: not measured).
+template <int N>
+struct KernelClock {
+    KernelClock() { arm(false); }
+    KernelClock(const KernelClock&) = delete; KernelClock& operator=(const KernelClock&) = delete;
+    ~KernelClock() { for (hipEvent_t e : ev) if (e) (void)hipEventDestroy(e); }
+    bool armed() const { return on; }
+    void arm(bool v) { on = v; marked = 0; for (float& m : ms) m = -1.f; }
+    // mark k goes before kernel k and after kernel k - 1
+    void mark(int k, hipStream_t s) {
+        if (!on) return;
+        if ((ev[k] || hipEventCreate(&ev[k]) == hipSuccess) && hipEventRecord(ev[k], s) == hipSuccess) marked |= 1u << k;
+        else (void)hipGetLastError();
+    }
+    // after the call's wait: this call's marks become milliseconds
+    void collect() {
+        for (int k = 0; k < N; k++)
+            if ((marked >> k & 3u) == 3u && hipEventElapsedTime(&ms[k], ev[k], ev[k + 1]) != hipSuccess) {
+                ms[k] = -1.f;
+                (void)hipGetLastError();
+            }
+        marked = 0;
+    }
+    // EAO_ERR_INVALID with the module's message when no slot is measured; -1 in a slot that is not
+    eao_status read(float* out, const char* nothing) const {
+        bool any = false;
+        for (float m : ms) any = any || m >= 0.f;
+        EAO_REQUIRE(any, "%s", nothing);
+        for (int k = 0; k < N; k++) out[k] = ms[k];
+        return EAO_OK;
+    }
+private:
+    hipEvent_t ev[N + 1] = {};
+    float ms[N];
+    unsigned marked = 0;
+    bool on = false;
+};
+
 #if defined(__HIPCC__)
 // THE hand-over point between the lanes of ONE wavefront through LDS (or through memory the wave alone touches): the
 // lanes' earlier stores are visible to the other lanes' later loads.  The hardware needs nothing for that -- a wave's

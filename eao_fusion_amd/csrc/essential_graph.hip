@@ -636,6 +636,7 @@ eao_status run_essential_graph(const eao_essential_graph_problem* p, eao_essenti
     }
     std::memset(c.status, 0, sizeof(EgStatus));
     hipStream_t s = c.stream;
+    Drain drain(s);
     EAO_HIP(hipMemcpyAsync(d, h, upEnd, hipMemcpyHostToDevice, s));
     EAO_HIP(hipMemsetAsync(d + upEnd, 0, L.scratchEnd - upEnd, s));
     EAO_HIP(hipEventRecord(c.ev0, s));
@@ -657,7 +658,7 @@ eao_status run_essential_graph(const eao_essential_graph_problem* p, eao_essenti
                 hipLaunchKernelGGL(k_eg_decide, dim3(1), dim3(256), 0, s, D);
             }
             EAO_HIP(hipGetLastError());
-            EAO_HIP(hipStreamSynchronize(s));
+            EAO_HIP(drain.wait_more(Drain::Block));
         }
         EAO_REQUIRE(c.status->done, "internal: the LM loop did not reach a verdict");
     }
@@ -665,7 +666,7 @@ eao_status run_essential_graph(const eao_essential_graph_problem* p, eao_essenti
     EAO_HIP(hipGetLastError());
     EAO_HIP(hipEventRecord(c.ev1, s));
     EAO_HIP(hipMemcpyAsync(h + outOff, d + outOff, L.outEnd - outOff, hipMemcpyDeviceToHost, s));
-    EAO_HIP(hipStreamSynchronize(s));
+    EAO_HIP(drain.wait(Drain::Block));
     float ms = 0;
     EAO_HIP(hipEventElapsedTime(&ms, c.ev0, c.ev1));
     g_trace.clear();

@@ -131,6 +131,7 @@ eao_status eao_frame_is_in_frustum(const eao_frustum_frame* Fr, const eao_map_po
     std::memcpy(c.host.p + oMax, pts->max_dist_inv, 4 * (size_t)n);
     std::memcpy(c.host.p + oNum, pts->max_dist, 4 * (size_t)n);
     hipStream_t s = c.stream;
+    eao::Drain drain(s);
     EAO_HIP(hipMemcpyAsync(c.dev.p, c.host.p, inBytes, hipMemcpyHostToDevice, s));
     // outputs of points that are not in view stay as the caller left them: seed the device copies with the caller's values
     std::memcpy(c.host.p + oU, proj_x, 4 * (size_t)n); std::memcpy(c.host.p + oV, proj_y, 4 * (size_t)n);
@@ -153,7 +154,7 @@ eao_status eao_frame_is_in_frustum(const eao_frustum_frame* Fr, const eao_map_po
     A.viewCos = (float*)(c.dev.p + oCos); A.level = (int*)(c.dev.p + oLvl); A.inView = c.dev.p + oIn;
     hipLaunchKernelGGL(k_is_in_frustum, dim3(eao::cdiv(n, 256)), dim3(256), 0, s, A);
     EAO_HIP(hipMemcpyAsync(c.host.p + oU, c.dev.p + oU, total - oU, hipMemcpyDeviceToHost, s));
-    EAO_HIP(eao::wait_latency(s));
+    EAO_HIP(drain.wait(eao::Drain::Latency));
     EAO_HIP(hipGetLastError());
     std::memcpy(proj_x, c.host.p + oU, 4 * (size_t)n); std::memcpy(proj_y, c.host.p + oV, 4 * (size_t)n);
     std::memcpy(proj_xr, c.host.p + oUr, 4 * (size_t)n); std::memcpy(view_cos, c.host.p + oCos, 4 * (size_t)n);
@@ -179,13 +180,14 @@ eao_status eao_assign_features_to_grid(int32_t n, const float* kp_x, const float
     if ((st = c.dev.reserve(total))) return st;
     std::memcpy(c.host.p + oX, kp_x, 4 * (size_t)n); std::memcpy(c.host.p + oY, kp_y, 4 * (size_t)n);
     hipStream_t s = c.stream;
+    eao::Drain drain(s);
     EAO_HIP(hipMemcpyAsync(c.dev.p, c.host.p, oS, hipMemcpyHostToDevice, s));
     const size_t lds = (size_t)npow2 * sizeof(unsigned);
     EAO_HIP(hipFuncSetAttribute((const void*)k_grid_assign, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     hipLaunchKernelGGL(k_grid_assign, dim3(1), dim3(kGridThreads), lds, s, n, (const float*)(c.dev.p + oX), (const float*)(c.dev.p + oY),
                        min_x, min_y, grid_inv_w, grid_inv_h, cols, rows, npow2, (int*)(c.dev.p + oS), (int*)(c.dev.p + oI));
     EAO_HIP(hipMemcpyAsync(c.host.p + oS, c.dev.p + oS, total - oS, hipMemcpyDeviceToHost, s));
-    EAO_HIP(eao::wait_latency(s));
+    EAO_HIP(drain.wait(eao::Drain::Latency));
     EAO_HIP(hipGetLastError());
     std::memcpy(cell_start, c.host.p + oS, 4 * (size_t)(nCells + 1));
     std::memcpy(items, c.host.p + oI, 4 * (size_t)cell_start[nCells]);
@@ -210,12 +212,13 @@ eao_status eao_compute_stereo_from_rgbd(int32_t n, const float* kp_x, const floa
     std::memcpy(c.host.p + oX, kp_x, 4 * (size_t)n); std::memcpy(c.host.p + oY, kp_y, 4 * (size_t)n); std::memcpy(c.host.p + oU, kpu_x, 4 * (size_t)n);
     if (!depth_on_device) std::memcpy(c.host.p + oD, depth, 4 * (size_t)pitch * height);
     hipStream_t s = c.stream;
+    eao::Drain drain(s);
     EAO_HIP(hipMemcpyAsync(c.dev.p, c.host.p, inBytes, hipMemcpyHostToDevice, s));
     const float* dDepth = depth_on_device ? depth : (const float*)(c.dev.p + oD);
     hipLaunchKernelGGL(k_stereo_from_rgbd, dim3(eao::cdiv(n, 256)), dim3(256), 0, s, n, (const float*)(c.dev.p + oX), (const float*)(c.dev.p + oY),
                        (const float*)(c.dev.p + oU), dDepth, pitch, mbf, (float*)(c.dev.p + oUr), (float*)(c.dev.p + oZ));
     EAO_HIP(hipMemcpyAsync(c.host.p + oUr, c.dev.p + oUr, total - oUr, hipMemcpyDeviceToHost, s));
-    EAO_HIP(eao::wait_latency(s));
+    EAO_HIP(drain.wait(eao::Drain::Latency));
     EAO_HIP(hipGetLastError());
     std::memcpy(u_right, c.host.p + oUr, 4 * (size_t)n); std::memcpy(out_depth, c.host.p + oZ, 4 * (size_t)n);
     return EAO_OK;
@@ -236,11 +239,12 @@ eao_status eao_undistort_keypoints(int32_t n, const float* kp_x, const float* kp
     if ((st = c.dev.reserve(total))) return st;
     std::memcpy(c.host.p, kp_x, 4 * (size_t)n); std::memcpy(c.host.p + fN, kp_y, 4 * (size_t)n);
     hipStream_t s = c.stream;
+    eao::Drain drain(s);
     EAO_HIP(hipMemcpyAsync(c.dev.p, c.host.p, 2 * fN, hipMemcpyHostToDevice, s));
     hipLaunchKernelGGL(k_undistort, dim3(eao::cdiv(n, 256)), dim3(256), 0, s, D, n, (const float*)c.dev.p, (const float*)(c.dev.p + fN), (float*)(c.dev.p + 2 * fN),
                        (float*)(c.dev.p + 3 * fN));
     EAO_HIP(hipMemcpyAsync(c.host.p + 2 * fN, c.dev.p + 2 * fN, 2 * fN, hipMemcpyDeviceToHost, s));
-    EAO_HIP(eao::wait_latency(s));
+    EAO_HIP(drain.wait(eao::Drain::Latency));
     EAO_HIP(hipGetLastError());
     std::memcpy(out_x, c.host.p + 2 * fN, 4 * (size_t)n); std::memcpy(out_y, c.host.p + 3 * fN, 4 * (size_t)n);
     return EAO_OK;

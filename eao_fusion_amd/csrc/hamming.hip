@@ -628,6 +628,8 @@ eao_status eao_distinctive_descriptors(int32_t n_sets, const int32_t* set_start,
     std::vector<int> rowset(std::max(total, 1));
     for (int s2 = 0; s2 < n_sets; s2++)
         for (int k = set_start[s2]; k < set_start[s2 + 1]; k++) rowset[k] = s2;
+    std::vector<unsigned> key(n_sets);
+    eao::Drain drain(c.stream);      // (declared behind the vectors the copies read and write: it waits before they go)
     EAO_HIP(hipMemcpyAsync(c.start.p, set_start, ((size_t)n_sets + 1) * sizeof(int), hipMemcpyHostToDevice, c.stream));
     if (total) {
         EAO_HIP(hipMemcpyAsync(c.desc.p, desc, (size_t)total * 32, hipMemcpyHostToDevice, c.stream));
@@ -635,9 +637,8 @@ eao_status eao_distinctive_descriptors(int32_t n_sets, const int32_t* set_start,
     }
     EAO_HIP(hipMemsetAsync(c.key.p, 0xFF, (size_t)n_sets * sizeof(unsigned), c.stream));
     if (total) hipLaunchKernelGGL(k_distinct_rows, dim3(eao::cdiv(total, 4)), dim3(256), 0, c.stream, (const uint4*)c.desc.p, c.start.p, c.rowset.p, total, c.key.p);
-    std::vector<unsigned> key(n_sets);
     EAO_HIP(hipMemcpyAsync(key.data(), c.key.p, (size_t)n_sets * sizeof(unsigned), hipMemcpyDeviceToHost, c.stream));
-    EAO_HIP(hipStreamSynchronize(c.stream));
+    EAO_HIP(drain.wait(eao::Drain::Block));
     EAO_HIP(hipGetLastError());
     for (int s2 = 0; s2 < n_sets; s2++) best[s2] = key[s2] == 0xFFFFFFFFu ? -1 : (int)(key[s2] & 0xFFFFF);
     return EAO_OK;

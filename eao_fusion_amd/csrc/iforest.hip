@@ -394,11 +394,9 @@ struct ForestCtx : eao::ThreadStream {
     eao::DevBuf<unsigned short> ws;
     eao::PinBuf<hipHostMallocDefault> host;
     eao::DevBuf<unsigned long long> stamps;
-    bool profiling = false, measured = false;
-    float ms[2] = {0, 0};
+    eao::KernelClock<2> clock;          // k_iforest_build, k_iforest_score; armed, the build kernel also stamps its stages
+    bool staged = false;
     double stageUs[3] = {0, 0, 0};      // seeding, shuffle and sample, the walk: mean over the trees of the last call
-    hipEvent_t ev2 = nullptr;
-    ~ForestCtx() { if (ev2) (void)hipEventDestroy(ev2); }
 };
 thread_local ForestCtx g_forest;
 
@@ -457,31 +455,24 @@ eao_status run_forests(const std::vector<Job>& jobs, bool wantNodes, Built& B) {
     }
     std::memcpy(h + oObj, B.objs.data(), nJobs * sizeof(ObjDev));
     std::memset(h + oFail, 0, nJobs * 4);
-    if (ctx.profiling) {
-        if ((st = ctx.timing())) return st;
-        if (!ctx.ev2) EAO_HIP(hipEventCreate(&ctx.ev2));
-        if ((st = ctx.stamps.reserve(nTrees * 4))) return st;
-    }
+    const bool profiling = ctx.clock.armed();
+    if (profiling && (st = ctx.stamps.reserve(nTrees * 4))) return st;
+    eao::Drain drain(ctx.stream);
     EAO_HIP(hipMemcpyAsync(d, h, inEnd, hipMemcpyHostToDevice, ctx.stream));
-    if (ctx.profiling) (void)hipEventRecord(ctx.ev0, ctx.stream);
+    ctx.clock.mark(0, ctx.stream);
     hipLaunchKernelGGL(k_iforest_build, dim3((unsigned)nTrees), dim3(64), dynLds, ctx.stream, (const ObjDev*)(d + oObj), (const unsigned*)(d + oTo),
                        (const unsigned*)(d + oSeed), (const float*)(d + oXyz), ctx.nodes.p, (unsigned*)(d + oCnt), (unsigned*)(d + oFail), ctx.ws.p,
-                       ctx.profiling ? ctx.stamps.p : nullptr);
-    hipError_t launchErr = hipGetLastError();
-    if (ctx.profiling) (void)hipEventRecord(ctx.ev1, ctx.stream);
-    if (launchErr == hipSuccess) {
-        hipLaunchKernelGGL(k_iforest_score, dim3(eao::cdiv((int)maxN, kScoreWaves), (unsigned)nJobs), dim3(64 * kScoreWaves), 0, ctx.stream, (const ObjDev*)(d + oObj),
-                           (const float*)(d + oXyz), (const NodeDev*)ctx.nodes.p, (const double*)(d + oC), (const unsigned*)(d + oFail), (double*)(d + oTot));
-        launchErr = hipGetLastError();
-    }
-    if (ctx.profiling) (void)hipEventRecord(ctx.ev2, ctx.stream);
-    if (launchErr != hipSuccess) (void)hipStreamSynchronize(ctx.stream);      // (the upload out of this thread's staging block is enqueued: nothing returns before it ends)
-    EAO_HIP(launchErr);
+                       profiling ? ctx.stamps.p : nullptr);
+    EAO_HIP(hipGetLastError());      // (the scores are not launched over trees that were not built)
+    ctx.clock.mark(1, ctx.stream);
+    hipLaunchKernelGGL(k_iforest_score, dim3(eao::cdiv((int)maxN, kScoreWaves), (unsigned)nJobs), dim3(64 * kScoreWaves), 0, ctx.stream, (const ObjDev*)(d + oObj),
+                       (const float*)(d + oXyz), (const NodeDev*)ctx.nodes.p, (const double*)(d + oC), (const unsigned*)(d + oFail), (double*)(d + oTot));
+    EAO_HIP(hipGetLastError());
+    ctx.clock.mark(2, ctx.stream);
     EAO_HIP(hipMemcpyAsync(h + oFail, d + oFail, end - oFail, hipMemcpyDeviceToHost, ctx.stream));
-    EAO_HIP(eao::wait_latency(ctx.stream));
-    if (ctx.profiling) {
-        EAO_HIP(hipEventElapsedTime(&ctx.ms[0], ctx.ev0, ctx.ev1));
-        EAO_HIP(hipEventElapsedTime(&ctx.ms[1], ctx.ev1, ctx.ev2));
+    EAO_HIP(drain.wait(eao::Drain::Latency));
+    ctx.clock.collect();
+    if (profiling) {
         std::vector<unsigned long long> t(nTrees * 4);
         EAO_HIP(hipMemcpy(t.data(), ctx.stamps.p, t.size() * 8, hipMemcpyDeviceToHost));
         for (int k = 0; k < 3; k++) {
@@ -489,7 +480,7 @@ eao_status run_forests(const std::vector<Job>& jobs, bool wantNodes, Built& B) {
             for (size_t g = 0; g < nTrees; g++) sum += (double)(t[g * 4 + k + 1] - t[g * 4 + k]);
             ctx.stageUs[k] = sum / (double)nTrees / 100.0;      // 100 MHz ticks
         }
-        ctx.measured = true;
+        ctx.staged = true;
     }
     B.failed.assign((const uint32_t*)(h + oFail), (const uint32_t*)(h + oFail) + nJobs);
     B.totals.assign((const double*)(h + oTot), (const double*)(h + oTot) + nPts);
@@ -606,22 +597,19 @@ eao_status eao_object_iforest_outliers_batch(int32_t n_obj, const int32_t* start
 }
 
 eao_status eao_iforest_set_profiling(int32_t on) {
-    g_forest.profiling = on != 0;
-    g_forest.measured = false;
+    g_forest.clock.arm(on != 0);
+    g_forest.staged = false;
     return EAO_OK;
 }
 
 eao_status eao_iforest_last_kernel_ms(float* kernel_ms) {
     EAO_REQUIRE(kernel_ms, "null argument");
-    EAO_REQUIRE(g_forest.measured, "no measurement on this thread: eao_iforest_set_profiling(1) and a forest call come first");
-    kernel_ms[0] = g_forest.ms[0];
-    kernel_ms[1] = g_forest.ms[1];
-    return EAO_OK;
+    return g_forest.clock.read(kernel_ms, "no measurement on this thread: eao_iforest_set_profiling(1) and a forest call come first");
 }
 
 eao_status eao_iforest_last_stage_us(double* stage_us) {
     EAO_REQUIRE(stage_us, "null argument");
-    EAO_REQUIRE(g_forest.measured, "no measurement on this thread: eao_iforest_set_profiling(1) and a forest call come first");
+    EAO_REQUIRE(g_forest.staged, "no measurement on this thread: eao_iforest_set_profiling(1) and a forest call come first");
     for (int k = 0; k < 3; k++) stage_us[k] = g_forest.stageUs[k];
     return EAO_OK;
 }

@@ -560,14 +560,7 @@ constexpr int kKernels = 5;
 struct InitCtx : ThreadStream {
     DevBuf<unsigned char> dev;
     std::vector<unsigned char> host;
-    bool timed = false;                      // EAO_INIT_EVENTS=1 (tools/bench_initializer.py): an event before and after each kernel of this thread's calls
-    bool measured = false;
-    hipEvent_t ev[kKernels + 1] = {};
-    float ms[kKernels] = {};
-    ~InitCtx() {
-        for (hipEvent_t e : ev)
-            if (e) (void)hipEventDestroy(e);
-    }
+    KernelClock<kKernels> clock;      // EAO_INIT_EVENTS=1 (tools/bench_initializer.py)
 };
 thread_local InitCtx g_init;
 
@@ -710,32 +703,24 @@ eao_status eao_initializer_initialize(const eao_initializer_problem* problem, co
     W.out = (Out*)(d + oOut); W.out_p3d = (float*)(d + oP3d); W.out_tri = d + oTri;
     const Rec* dW = (const Rec*)d;
     static const bool envEvents = getenv("EAO_INIT_EVENTS") && atoi(getenv("EAO_INIT_EVENTS"));
-    ctx.timed = envEvents;
-    if (ctx.timed)
-        for (hipEvent_t& e : ctx.ev)
-            if (!e) EAO_HIP(hipEventCreate(&e));
-    auto mark = [&](int k) { if (ctx.timed) (void)hipEventRecord(ctx.ev[k], ctx.stream); };
+    if (envEvents != ctx.clock.armed()) ctx.clock.arm(envEvents);
+    Drain drain(ctx.stream);
     EAO_HIP(hipMemcpyAsync(d, h, inEnd, hipMemcpyHostToDevice, ctx.stream));
-    mark(0);
+    ctx.clock.mark(0, ctx.stream);
     hipLaunchKernelGGL(k_init_hypotheses, dim3(iterations, 2), dim3(64), 0, ctx.stream, dW);
-    mark(1);
+    ctx.clock.mark(1, ctx.stream);
     hipLaunchKernelGGL(k_init_scores, dim3(iterations, 2), dim3(kThreads), 0, ctx.stream, dW);
-    mark(2);
+    ctx.clock.mark(2, ctx.stream);
     hipLaunchKernelGGL(k_init_select, dim3(1), dim3(kThreads), 0, ctx.stream, dW);
-    mark(3);
+    ctx.clock.mark(3, ctx.stream);
     hipLaunchKernelGGL(k_init_check_rt, dim3(kMaxMotions), dim3(kThreads), 0, ctx.stream, dW);
-    mark(4);
+    ctx.clock.mark(4, ctx.stream);
     hipLaunchKernelGGL(k_init_finish, dim3(1), dim3(kThreads), 0, ctx.stream, dW);
-    mark(5);
-    const hipError_t launchErr = hipGetLastError();
-    if (launchErr != hipSuccess) (void)hipStreamSynchronize(ctx.stream);      // (the upload out of this thread's staging block is enqueued: nothing returns before it ends)
-    EAO_HIP(launchErr);
+    ctx.clock.mark(5, ctx.stream);
+    EAO_HIP(hipGetLastError());
     EAO_HIP(hipMemcpyAsync(h + oOut, d + oOut, (inspect ? inspEnd : outEnd) - oOut, hipMemcpyDeviceToHost, ctx.stream));
-    EAO_HIP(wait_latency(ctx.stream));
-    if (ctx.timed) {
-        for (int k = 0; k < kKernels; k++) EAO_HIP(hipEventElapsedTime(&ctx.ms[k], ctx.ev[k], ctx.ev[k + 1]));
-        ctx.measured = true;
-    }
+    EAO_HIP(drain.wait(Drain::Latency));
+    ctx.clock.collect();
     const Out& O = *(const Out*)(h + oOut);
     r.returned = O.returned; r.branch = O.branch; r.no_model = O.no_model; r.degenerate = O.degenerate;
     r.SH = O.SH; r.SF = O.SF; r.RH = O.RH;
@@ -770,9 +755,7 @@ eao_status eao_initializer_initialize(const eao_initializer_problem* problem, co
 
 eao_status eao_initializer_last_kernel_ms(float* kernel_ms) {
     EAO_REQUIRE(kernel_ms, "null argument");
-    EAO_REQUIRE(g_init.measured, "no measurement on this thread: EAO_INIT_EVENTS=1 and a call of eao_initializer_initialize come first");
-    for (int k = 0; k < kKernels; k++) kernel_ms[k] = g_init.ms[k];
-    return EAO_OK;
+    return g_init.clock.read(kernel_ms, "no measurement on this thread: EAO_INIT_EVENTS=1 and a call of eao_initializer_initialize come first");
 }
 
 }  // extern "C"

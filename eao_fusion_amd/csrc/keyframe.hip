@@ -434,7 +434,7 @@ __global__ __launch_bounds__(256) void k_kf_upload(const uint4* __restrict__ src
 }
 
 using PinBuf = eao::PinBuf<hipHostMallocMapped>;   // kernels read and write it in place through .d
-struct Ctx : eao::ThreadStream {   // per host thread, grow-only; the events, under EAO_TRI_EVENTS=1: around the triangulation launches (tools/bench_triangulation.py)
+struct Ctx : eao::ThreadStream {   // per host thread, grow-only
     PinBuf in, out;
     eao::DevBuf<int2> match;
     eao::DevBuf<unsigned char> dev;
@@ -442,7 +442,7 @@ struct Ctx : eao::ThreadStream {   // per host thread, grow-only; the events, un
     int ticketNext = 0;
     PinBuf doneWord;
     PinBuf tri;                    // eao_kf_create_new_map_points: [verdicts | points] in mapped host memory
-    float triMs = -1.f;
+    eao::KernelClock<1> triClock;  // EAO_TRI_EVENTS=1: around the triangulation launches (tools/bench_triangulation.py)
     eao::DevBuf<long long> dbg;
     int seq = 0;
     int gen = 0;
@@ -652,6 +652,7 @@ eao_status run_nodes(int mode, const eao_keyframe* k1, int nProb, const eao_keyf
     const int n1 = k1->D.n;
     if (n1 == 0 || nProb == 0) { for (int p = 0; p < nProb; p++) nmatches[p] = 0; return EAO_OK; }
     const size_t cells = (size_t)nProb * n1;
+    eao::Drain drain(c.stream);
     if (c.match.n < cells) {
         if ((st = c.match.reserve(cells + (cells >> 2)))) return st;
         EAO_HIP(hipMemsetAsync(c.match.p, 0, c.match.n * sizeof(int2), c.stream));      // (fresh memory may hold anything: no stamp of it may equal a generation)
@@ -722,9 +723,8 @@ eao_status run_nodes(int mode, const eao_keyframe* k1, int nProb, const eao_keyf
     // 50 ms): on any launch error, and after a poll that timed out, the counter and its host twin start again from zero
     const hipError_t launchErr = hipGetLastError();
     if (launchErr != hipSuccess) {
-        (void)hipStreamSynchronize(c.stream);
-        (void)hipMemsetAsync(c.ticket.p, 0, sizeof(int), c.stream);
-        (void)hipStreamSynchronize(c.stream);
+        (void)drain.wait_more(eao::Drain::Block);
+        (void)hipMemsetAsync(c.ticket.p, 0, sizeof(int), c.stream);      // (the guard waits for it)
         c.ticketNext = 0;
         eao::set_error("keyframe search launch failed: %s", hipGetErrorString(launchErr));
         return EAO_ERR_NO_DEVICE;
@@ -732,13 +732,8 @@ eao_status run_nodes(int mode, const eao_keyframe* k1, int nProb, const eao_keyf
     c.ticketNext += nProb;
     if (tail) {
         static const bool envEvents = getenv("EAO_TRI_EVENTS") && atoi(getenv("EAO_TRI_EVENTS"));
-        // the events are a diagnostic: the kernels above are enqueued and write into this thread's mapped buffers, so nothing here returns before the wait --
-        // an event call that fails only costs the measurement (triMs stays -1)
-        bool ev = envEvents;
-        for (hipEvent_t* e : {&c.ev0, &c.ev1})
-            if (ev && !*e) ev = hipEventCreate(e) == hipSuccess;
-        ev = ev && hipEventRecord(c.ev0, c.stream) == hipSuccess;
-        if (envEvents && !ev) (void)hipGetLastError();      // (not a launch error of the kernels below)
+        if (envEvents != c.triClock.armed()) c.triClock.arm(envEvents);
+        c.triClock.mark(0, c.stream);
         const eao::tri::Side S1 = tri_side(k1);
         for (int p0 = 0; p0 < nProb; p0 += eao::tri::kMaxProb) {
             const int np = std::min(eao::tri::kMaxProb, nProb - p0);
@@ -750,21 +745,20 @@ eao_status run_nodes(int mode, const eao_keyframe* k1, int nProb, const eao_keyf
             }
             eao::tri::launch(c.stream, S1, *tail->cam1, tail->ratioFactor, np, P, (int*)c.tri.d + (size_t)p0 * n1, (float*)(c.tri.d + oX3) + (size_t)p0 * n1 * 3);
         }
-        const hipError_t triErr = hipGetLastError();
-        ev = ev && hipEventRecord(c.ev1, c.stream) == hipSuccess;
-        EAO_HIP(eao::wait_latency(c.stream));
-        EAO_HIP(triErr);
-        if (!(ev && hipEventElapsedTime(&c.triMs, c.ev0, c.ev1) == hipSuccess)) c.triMs = -1.f;
-        if (envEvents && !ev) (void)hipGetLastError();      // (a failed event call is not this call's failure)
+        EAO_HIP(hipGetLastError());
+        c.triClock.mark(1, c.stream);
+        EAO_HIP(drain.wait_more(eao::Drain::Latency));
+        c.triClock.collect();
         seen = true;
     }
     const auto t0 = std::chrono::steady_clock::now();
     for (unsigned spins = 0; !seen && !(seen = *doneHost == seq); spins++)
         if ((spins & 1023) == 1023 && std::chrono::steady_clock::now() - t0 > std::chrono::milliseconds(50)) break;
     std::atomic_thread_fence(std::memory_order_acquire);
-    if (!seen) {
-        EAO_HIP(eao::wait_latency(c.stream));
-        EAO_HIP(hipMemsetAsync(c.ticket.p, 0, sizeof(int), c.stream)); EAO_HIP(eao::wait_latency(c.stream)); c.ticketNext = 0;
+    if (seen) drain.disarm();      // (the done word is the last store of the stream's last kernel; the tail's wait came behind its own kernels)
+    else {
+        EAO_HIP(drain.wait_more(eao::Drain::Latency));
+        EAO_HIP(hipMemsetAsync(c.ticket.p, 0, sizeof(int), c.stream)); EAO_HIP(drain.wait(eao::Drain::Latency)); c.ticketNext = 0;
     }
     EAO_HIP(hipGetLastError());
     if (c.dbg.p) {
@@ -853,9 +847,7 @@ eao_status eao_kf_create_new_map_points(const eao_keyframe* kf1, const eao_tri_c
 
 eao_status eao_kf_last_triangulation_ms(float* ms) {
     EAO_REQUIRE(ms, "null argument");
-    EAO_REQUIRE(g_kctx.triMs >= 0.f, "no measurement on this thread: EAO_TRI_EVENTS=1 and a call of eao_kf_create_new_map_points come first");
-    *ms = g_kctx.triMs;
-    return EAO_OK;
+    return g_kctx.triClock.read(ms, "no measurement on this thread: EAO_TRI_EVENTS=1 and a call of eao_kf_create_new_map_points come first");
 }
 
 eao_status eao_kf_fuse_search(int32_t n_kf, const eao_keyframe* const* kfs, int32_t use_sim3, const float* poses, float fx, float fy, float cx, float cy, float bf,
@@ -886,6 +878,7 @@ eao_status eao_kf_fuse_search(int32_t n_kf, const eao_keyframe* const* kfs, int3
     std::memcpy(hb + oDe, pts->desc, 32 * N);
     if ((st = c.out.reserve(4 * N * (size_t)n_kf))) return st;
     const size_t n16 = bytes / 16;
+    eao::Drain drain(c.stream);
     hipLaunchKernelGGL(k_kf_upload, dim3((unsigned)std::min<size_t>((n16 + 255) / 256, 256)), dim3(256), 0, c.stream, (const uint4*)c.in.d, (uint4*)c.dev.p, n16);
     for (int f0 = 0; f0 < n_kf; f0 += kMaxProb) {
         const int nf = std::min(kMaxProb, n_kf - f0);
@@ -911,7 +904,7 @@ eao_status eao_kf_fuse_search(int32_t n_kf, const eao_keyframe* const* kfs, int3
         }
         hipLaunchKernelGGL(k_kf_fuse, dim3(eao::cdiv(n, 4), nf), dim3(256), 0, c.stream, A);
     }
-    EAO_HIP(eao::wait_latency(c.stream));
+    EAO_HIP(drain.wait(eao::Drain::Latency));
     EAO_HIP(hipGetLastError());
     std::memcpy(best_kp, c.out.p, 4 * N * (size_t)n_kf);
     for (int f = 0; f < n_kf; f++) {

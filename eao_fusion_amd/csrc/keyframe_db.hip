@@ -110,6 +110,7 @@ eao_status intersect(eao_keyframe_db* db, int32_t nq, const uint32_t* qId, const
     if ((st = ctx.dev.reserve(end))) return st;
     if ((st = ctx.host.reserve(end))) return st;
     unsigned char *d = ctx.dev.p, *h = ctx.host.p;
+    eao::Drain drain(ctx.stream);
     if (nq > 0) {
         std::memcpy(h + oQi, qId, (size_t)nq * 4);
         std::memcpy(h + oQv, qVal, (size_t)nq * 8);
@@ -125,11 +126,9 @@ eao_status intersect(eao_keyframe_db* db, int32_t nq, const uint32_t* qId, const
     }
     hipLaunchKernelGGL(k_kfdb_intersect, dim3(eao::cdiv(n, 4)), dim3(256), (size_t)nq * 4, ctx.stream, nq, (const unsigned*)(d + oQi), (const double*)(d + oQv), n, db->rec.at(),
                        db->words.at<0>(), db->words.at<1>(), (int*)(d + oCommon), (unsigned*)(d + oFirst), (double*)(d + oScore));
-    const hipError_t launchErr = hipGetLastError();
-    if (launchErr != hipSuccess) (void)hipStreamSynchronize(ctx.stream);      // (the uploads out of this thread's staging block are enqueued)
-    EAO_HIP(launchErr);
+    EAO_HIP(hipGetLastError());
     EAO_HIP(hipMemcpyAsync(h + oCommon, d + oCommon, end - oCommon, hipMemcpyDeviceToHost, ctx.stream));
-    EAO_HIP(eao::wait_latency(ctx.stream));
+    EAO_HIP(drain.wait(eao::Drain::Latency));
     db->recStale = false;
     raw.common = (const int32_t*)(h + oCommon);
     raw.firstWord = (const uint32_t*)(h + oFirst);
@@ -181,6 +180,7 @@ eao_status eao_keyframe_db_add(eao_keyframe_db* db, uint64_t kf_id, int32_t n, c
     eao_status st = ctx.ready(eao::StreamClass::Latency);
     if (st) return st;
     const uint64_t begin = db->table.used;
+    eao::Drain drain(ctx.stream);      // (the arenas' growth enqueues its copies and waits for them itself)
     if ((st = reserve_words(db, begin + (uint64_t)n, ctx.stream))) return st;
     const size_t at = (size_t)db->table.nLive;      // the new entry's record (when the records are stale the next query writes them all)
     if (!db->recStale && (st = db->rec.reserve(at + 1, at, ctx.stream))) return st;
@@ -197,7 +197,7 @@ eao_status eao_keyframe_db_add(eao_keyframe_db* db, uint64_t kf_id, int32_t n, c
         *(uint2*)(h + oRec) = make_uint2((unsigned)begin, (unsigned)n);
         EAO_HIP(hipMemcpyAsync(db->rec.at() + at, h + oRec, sizeof(uint2), hipMemcpyHostToDevice, ctx.stream));
     }
-    EAO_HIP(hipStreamSynchronize(ctx.stream));
+    EAO_HIP(drain.wait(eao::Drain::Block));
     db->table.append(kf_id, (uint32_t)n);      // (only now: a failed call leaves the table as it was)
     return EAO_OK;
 }

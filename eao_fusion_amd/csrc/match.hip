@@ -308,6 +308,7 @@ eao_status eao::match::build_lists_multi(int nf, const eao_frame_view* const* Fs
     if ((st = c.meta.reserve(metaOff * sizeof(int)))) return st;
     if ((st = c.metaDev.reserve(metaOff))) return st;
     hipStream_t s = c.stream;
+    eao::Drain drain(s);
     EAO_HIP(hipMemcpyAsync(c.dev.p, hb, off, hipMemcpyHostToDevice, s));
     EAO_HIP(hipMemsetAsync(c.metaDev.p, 0, metaOff * sizeof(int), s));   // (the cursors)
     for (int f = 0; f < nf; f++) {
@@ -334,7 +335,7 @@ eao_status eao::match::build_lists_multi(int nf, const eao_frame_view* const* Fs
     }
     int* meta = (int*)c.meta.p;
     EAO_HIP(hipMemcpyAsync(meta, c.metaDev.p, metaOff * sizeof(int), hipMemcpyDeviceToHost, s));
-    EAO_HIP(eao::wait_latency(s));
+    EAO_HIP(drain.wait(eao::Drain::Latency));
     EAO_HIP(hipGetLastError());
     for (int f = 0; f < nf; f++) {
         const Plan& P = plan[f];
@@ -383,11 +384,12 @@ eao_status eao::match::pair_distances(const uint8_t* descA, int nA, const uint8_
     for (size_t k = 0; k < np; k++) { ((int*)(hb + oP))[2 * k] = ia[k]; ((int*)(hb + oP))[2 * k + 1] = ib[k]; }
     if ((st = c.dev.reserve(off))) return st;
     hipStream_t s = c.stream;
+    eao::Drain drain(s);
     EAO_HIP(hipMemcpyAsync(c.dev.p, hb, oD, hipMemcpyHostToDevice, s));
     if ((st = c.out.reserve(2 * np))) return st;
     hipLaunchKernelGGL(k_pair_distances, dim3(eao::cdiv((int)np, 256)), dim3(256), 0, s, (const uint4*)(c.dev.p + oA), (const uint4*)(c.dev.p + oB),
                        (const int2*)(c.dev.p + oP), (int)np, (unsigned short*)c.out.p);
-    EAO_HIP(eao::wait_latency(s));
+    EAO_HIP(drain.wait(eao::Drain::Latency));
     EAO_HIP(hipGetLastError());
     std::memcpy(dist.data(), c.out.p, 2 * np);
     return EAO_OK;

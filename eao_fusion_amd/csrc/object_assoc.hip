@@ -186,9 +186,7 @@ __global__ __launch_bounds__(64 * kRectWaves) void k_project_rects(int nMap, con
 struct AssocCtx : eao::ThreadStream {
     eao::DevBuf<unsigned char> dev;
     eao::PinBuf<hipHostMallocDefault> host;
-    bool profiling = false;
-    bool measured[2] = {false, false};
-    float ms[2] = {0, 0};      // k_np_counts, k_project_rects: each of its own last call
+    eao::KernelClock<2> clock;      // k_np_counts between marks 0 and 1, k_project_rects between 1 and 2: each of its own last call
 };
 thread_local AssocCtx g_assoc;
 
@@ -254,21 +252,16 @@ eao_status run_counts(const Lists& L, std::vector<Plan>& plans, std::vector<uint
     std::memcpy(h + oDet, L.det_xyz + (size_t)L.det_start[0] * 3, nDetPts * 12);
     std::memcpy(h + oMap, L.map_xyz + (size_t)L.map_start[0] * 3, nMapPts * 12);
     std::memcpy(h + oPair, open.data(), nOpen * sizeof(PairDev));
-    if (ctx.profiling && (st = ctx.timing())) return st;
+    eao::Drain drain(ctx.stream);
     EAO_HIP(hipMemcpyAsync(d, h, inEnd, hipMemcpyHostToDevice, ctx.stream));
-    if (ctx.profiling) (void)hipEventRecord(ctx.ev0, ctx.stream);
+    ctx.clock.mark(0, ctx.stream);
     hipLaunchKernelGGL(k_np_counts, dim3((unsigned)nOpen), dim3(kBlock), 0, ctx.stream, (const PairDev*)(d + oPair), (const float*)(d + oDet), (const float*)(d + oMap),
                        (unsigned*)(d + oCnt));
-    const hipError_t launchErr = hipGetLastError();
-    if (ctx.profiling) (void)hipEventRecord(ctx.ev1, ctx.stream);
-    if (launchErr != hipSuccess) (void)hipStreamSynchronize(ctx.stream);      // (the upload out of this thread's staging block is enqueued: nothing returns before it ends)
-    EAO_HIP(launchErr);
+    EAO_HIP(hipGetLastError());
+    ctx.clock.mark(1, ctx.stream);
     EAO_HIP(hipMemcpyAsync(h + oCnt, d + oCnt, nOpen * 36, hipMemcpyDeviceToHost, ctx.stream));
-    EAO_HIP(eao::wait_latency(ctx.stream));
-    if (ctx.profiling) {
-        EAO_HIP(hipEventElapsedTime(&ctx.ms[0], ctx.ev0, ctx.ev1));
-        ctx.measured[0] = true;
-    }
+    EAO_HIP(drain.wait(eao::Drain::Latency));
+    ctx.clock.collect();
     for (size_t q = 0; q < nOpen; q++) std::memcpy(counts.data() + (size_t)owner[q] * 9, h + oCnt + q * 36, 36);
     return EAO_OK;
 }
@@ -338,21 +331,16 @@ eao_status eao_object_project_rects_batch(int32_t n_map, const int32_t* map_star
     RectArgs A;
     std::memcpy(A.T, Tcw, sizeof(A.T));
     A.fx = fx; A.fy = fy; A.cx = cx; A.cy = cy;
-    if (ctx.profiling && (st = ctx.timing())) return st;
+    eao::Drain drain(ctx.stream);
     EAO_HIP(hipMemcpyAsync(d, h, inEnd, hipMemcpyHostToDevice, ctx.stream));
-    if (ctx.profiling) (void)hipEventRecord(ctx.ev0, ctx.stream);
+    ctx.clock.mark(1, ctx.stream);
     hipLaunchKernelGGL(k_project_rects, dim3((unsigned)eao::cdiv(n_map, kRectWaves)), dim3(64 * kRectWaves), 0, ctx.stream, (int)n_map, (const int*)(d + oStart),
                        (const float*)(d + oXyz), A, (RectDev*)(d + oOut), uv ? (float*)(d + oUv) : nullptr);
-    const hipError_t launchErr = hipGetLastError();
-    if (ctx.profiling) (void)hipEventRecord(ctx.ev1, ctx.stream);
-    if (launchErr != hipSuccess) (void)hipStreamSynchronize(ctx.stream);      // (the upload out of this thread's staging block is enqueued: nothing returns before it ends)
-    EAO_HIP(launchErr);
+    EAO_HIP(hipGetLastError());
+    ctx.clock.mark(2, ctx.stream);
     EAO_HIP(hipMemcpyAsync(h + oOut, d + oOut, end - oOut, hipMemcpyDeviceToHost, ctx.stream));
-    EAO_HIP(eao::wait_latency(ctx.stream));
-    if (ctx.profiling) {
-        EAO_HIP(hipEventElapsedTime(&ctx.ms[1], ctx.ev0, ctx.ev1));
-        ctx.measured[1] = true;
-    }
+    EAO_HIP(drain.wait(eao::Drain::Latency));
+    ctx.clock.collect();
     const RectDev* out = (const RectDev*)(h + oOut);
     for (int32_t j = 0; j < n_map; j++) {
         if (map_start[j + 1] == map_start[j]) {
@@ -367,18 +355,13 @@ eao_status eao_object_project_rects_batch(int32_t n_map, const int32_t* map_star
 }
 
 eao_status eao_object_assoc_set_profiling(int32_t on) {
-    g_assoc.profiling = on != 0;
-    g_assoc.measured[0] = g_assoc.measured[1] = false;
+    g_assoc.clock.arm(on != 0);
     return EAO_OK;
 }
 
 eao_status eao_object_assoc_last_kernel_ms(float* kernel_ms) {
     EAO_REQUIRE(kernel_ms, "null argument");
-    EAO_REQUIRE(g_assoc.measured[0] || g_assoc.measured[1],
-                "no measurement on this thread: eao_object_assoc_set_profiling(1) and a rank-sum call that reaches the device or a rect call come first");
-    kernel_ms[0] = g_assoc.measured[0] ? g_assoc.ms[0] : -1.0f;
-    kernel_ms[1] = g_assoc.measured[1] ? g_assoc.ms[1] : -1.0f;
-    return EAO_OK;
+    return g_assoc.clock.read(kernel_ms, "no measurement on this thread: eao_object_assoc_set_profiling(1) and a rank-sum call that reaches the device or a rect call come first");
 }
 
 }  // extern "C"

@@ -189,15 +189,13 @@ Xf inverse_isometry(const float* Tcw) {
     return X;
 }
 
-// n points in device memory, `stride` floats apart, through the transform into the arena at `begin` (reserved by the caller); the handle's mutex is held
+// n points in device memory, `stride` floats apart, through the transform into the arena at `begin` (reserved by the caller); the handle's mutex is held.
+// Enqueues only: the caller waits.
 eao_status transform_into(eao_plane_map* pm, PmapCtx& ctx, uint64_t begin, int32_t n, const float* devXyz, int stride, const float* Tcw) {
     Xf X = Xf();
     if (Tcw) X = inverse_isometry(Tcw);
     hipLaunchKernelGGL(k_pm_transform, dim3(eao::cdiv(n, 256)), dim3(256), 0, ctx.stream, n, devXyz, stride, X, Tcw ? 0 : 1, pm->pts.at() + begin);
-    const hipError_t launchErr = hipGetLastError();
-    const hipError_t syncErr = hipStreamSynchronize(ctx.stream);
-    EAO_HIP(launchErr);
-    EAO_HIP(syncErr);
+    EAO_HIP(hipGetLastError());
     return EAO_OK;
 }
 
@@ -237,11 +235,13 @@ eao_status store(eao_plane_map* pm, const char* name, bool isAdd, uint64_t id, c
     const uint64_t begin = pm->table.used;
     if ((st = pm->pts.reserve(begin + (uint64_t)n, begin, ctx.stream))) return st;
     if (n > 0) {
+        eao::Drain drain(ctx.stream);
         if (!seg) {
             if ((st = upload_cloud(ctx, n, xyz))) return st;
             devXyz = (const float*)ctx.dev.p;
         }
         if ((st = transform_into(pm, ctx, begin, n, devXyz, seg ? 4 : 3, Tcw))) return st;
+        EAO_HIP(drain.wait(eao::Drain::Block));
     }
     // (only now: a failed call leaves the table as it was)
     if (isAdd) {
@@ -331,10 +331,11 @@ eao_status eao_plane_map_boundary(eao_plane_map* pm, uint64_t id, int32_t cap, f
         const size_t bytes = (size_t)cnt * 12;
         if ((st = ctx.dev.reserve(bytes))) return st;
         if ((st = ctx.host.reserve(bytes))) return st;
+        eao::Drain drain(ctx.stream);
         hipLaunchKernelGGL(k_pm_read, dim3(eao::cdiv(cnt, 256)), dim3(256), 0, ctx.stream, cnt, (const float4*)(pm->pts.at() + e->begin), (float*)ctx.dev.p);
         EAO_HIP(hipGetLastError());
         EAO_HIP(hipMemcpyAsync(ctx.host.p, ctx.dev.p, bytes, hipMemcpyDeviceToHost, ctx.stream));
-        EAO_HIP(hipStreamSynchronize(ctx.stream));
+        EAO_HIP(drain.wait(eao::Drain::Block));
         std::memcpy(xyz, ctx.host.p, bytes);
     }
     *n = cnt;
@@ -385,25 +386,21 @@ eao_status eao_plane_map_associate(eao_plane_map* pm, int32_t n_sets, const floa
         std::memcpy(h + oCand, cands.data(), cands.size() * sizeof(pmap::Cand));
         std::memcpy(h + oWork, work.data(), work.size() * sizeof(pmap::Work));
     }
+    eao::Drain drain(ctx.stream);
     EAO_HIP(hipMemcpyAsync(d, h, inEnd, hipMemcpyHostToDevice, ctx.stream));
-    hipError_t launchErr = hipSuccess;
     if (n_cand > 0) {
         EAO_HIP(hipMemsetD32Async((hipDeviceptr_t)(d + oDis), (int)kNoDistanceBits, (size_t)nPairs, ctx.stream));
         const size_t lds = (size_t)nRows * 17 + (size_t)eao::cdiv(nRows, kRowTile);
         hipLaunchKernelGGL(k_pm_min_dist, dim3((unsigned)work.size()), dim3(256), lds, ctx.stream, nRows, n_cand, (const float4*)(d + oRows),
                            (const pmap::Cand*)(d + oCand), (const pmap::Work*)(d + oWork), (const float4*)pm->pts.at(), angle_th, (unsigned*)(d + oDis), d + oGated);
-        launchErr = hipGetLastError();
+        EAO_HIP(hipGetLastError());      // (no selection over distances that were not computed)
     }
-    if (launchErr == hipSuccess) {
-        hipLaunchKernelGGL(k_pm_select, dim3(eao::cdiv(nRows, 256)), dim3(256), 0, ctx.stream, nRows, n_cand, (const float*)(d + oDis), d + oGated, dis_th,
-                           (int*)(d + oMatch), (float*)(d + oMatchDis));
-        launchErr = hipGetLastError();
-    }
-    if (launchErr != hipSuccess) (void)hipStreamSynchronize(ctx.stream);      // (the upload out of this thread's staging block is enqueued)
-    EAO_HIP(launchErr);
+    hipLaunchKernelGGL(k_pm_select, dim3(eao::cdiv(nRows, 256)), dim3(256), 0, ctx.stream, nRows, n_cand, (const float*)(d + oDis), d + oGated, dis_th,
+                       (int*)(d + oMatch), (float*)(d + oMatchDis));
+    EAO_HIP(hipGetLastError());
     const bool full = n_cand > 0 && (dis || gated);
     EAO_HIP(hipMemcpyAsync(h + oMatch, d + oMatch, (full ? end : oDis) - oMatch, hipMemcpyDeviceToHost, ctx.stream));
-    EAO_HIP(eao::wait_latency(ctx.stream));
+    EAO_HIP(drain.wait(eao::Drain::Latency));
     std::memcpy(match, h + oMatch, (size_t)nRows * 4);
     std::memcpy(match_dis, h + oMatchDis, (size_t)nRows * 4);
     if (world_coef) std::memcpy(world_coef, hRows, (size_t)nRows * 16);

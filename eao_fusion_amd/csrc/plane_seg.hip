@@ -366,8 +366,9 @@ std::string check_cfg(const eao_plane_seg_cfg& c) {
     return std::string();
 }
 
-// everything after the host's middle: membership, then the voxel grid of every final plane.  The handle's mutex is held.
-eao_status device_tail(eao_plane_seg* h, PsegCtx& ctx) {
+// everything after the host's middle: membership, then the voxel grid of every final plane.  The handle's mutex is held; the run's guard is armed, and the
+// last wait here is the run's.
+eao_status device_tail(eao_plane_seg* h, PsegCtx& ctx, eao::Drain& drain) {
     const Intr& I = h->I;
     const pseg::Segmenter& sg = h->seg;
     const int n = h->nPixels, nPlanes = (int)sg.planes.size(), nOld = (int)sg.old.size(), nClaims = (int)(sg.claims.size() / 2);
@@ -393,7 +394,7 @@ eao_status device_tail(eao_plane_seg* h, PsegCtx& ctx) {
     }
     h->nVox = 0;
     if (nPlanes == 0) {
-        EAO_HIP(eao::wait_latency(s));      // (the upload out of this thread's staging block has ended)
+        EAO_HIP(drain.wait(eao::Drain::Latency));      // (the upload out of this thread's staging block has ended)
         return EAO_OK;
     }
     // min / max and pixel counts
@@ -401,16 +402,16 @@ eao_status device_tail(eao_plane_seg* h, PsegCtx& ctx) {
     EAO_HIP(hipMemsetAsync(dSmall, 0, (size_t)kSmall * 4, s));
     {
         unsigned* init = (unsigned*)ctx.host.p;      // (the upload above is ordered before this copy on the stream, but reads the same staging block: wait first)
-        EAO_HIP(hipStreamSynchronize(s));
+        EAO_HIP(drain.wait_more(eao::Drain::Block));
         for (int e = 0; e < nPlanes * 6; e++) init[e] = (e % 6) < 3 ? 0xffffffffu : 0u;
         EAO_HIP(hipMemcpyAsync(dSmall + oMM, init, (size_t)nPlanes * 24, hipMemcpyHostToDevice, s));
     }
     hipLaunchKernelGGL(k_ps_minmax, dim3(eao::cdiv(n, 256)), dim3(256), 0, s, I, nPlanes, (const float*)h->depth.p, (const int*)h->member.p,
                        (unsigned*)(dSmall + oMM), dSmall + oCount);
     EAO_HIP(hipGetLastError());
-    EAO_HIP(hipStreamSynchronize(s));
+    EAO_HIP(drain.wait_more(eao::Drain::Block));
     EAO_HIP(hipMemcpyAsync(ctx.host.p, dSmall, (size_t)kSmall * 4, hipMemcpyDeviceToHost, s));
-    EAO_HIP(eao::wait_latency(s));
+    EAO_HIP(drain.wait_more(eao::Drain::Latency));
     std::vector<int> pixCount(nPlanes);
     std::vector<Grid> grid(nPlanes);
     const float inv = 1.0f / h->cfg.leaf;
@@ -464,9 +465,9 @@ eao_status device_tail(eao_plane_seg* h, PsegCtx& ctx) {
     hipLaunchKernelGGL(k_ps_centroid, dim3(eao::cdiv(n, 256)), dim3(256), 0, s, I, n, nPlanes, (const float*)h->depth.p, (const Grid*)h->grid.p, (const unsigned*)kIn,
                        (const int*)pIn, (const int*)h->vstart.p, (const int*)(dSmall + oCounts), h->cloud.p, dSmall + oPlaneStart);
     EAO_HIP(hipGetLastError());
-    EAO_HIP(hipStreamSynchronize(s));      // (the grid's upload out of the staging block has ended before the block is written again)
+    EAO_HIP(drain.wait_more(eao::Drain::Block));      // (the grid's upload out of the staging block has ended before the block is written again)
     EAO_HIP(hipMemcpyAsync(ctx.host.p, dSmall, (size_t)(2 + kMaxPlanes) * 4, hipMemcpyDeviceToHost, s));
-    EAO_HIP(eao::wait_latency(s));
+    EAO_HIP(drain.wait(eao::Drain::Latency));
     const int* hs = (const int*)ctx.host.p;
     const int nVox = hs[oCounts];
     if (nVox < nPlanes || nVox > n) { eao::set_error("eao_plane_seg_run: %d voxels for %d planes", nVox, nPlanes); return EAO_ERR_INTERNAL; }
@@ -561,16 +562,15 @@ eao_status eao_plane_seg_run(eao_plane_seg* h, const float* depth, int32_t strid
     h->haveTiming = false;
     const auto t0 = std::chrono::steady_clock::now();
     for (int y = 0; y < I.H; y++) std::memcpy(ctx.host.p + (size_t)y * I.W * 4, depth + (size_t)y * stride, (size_t)I.W * 4);
+    eao::Drain drain(ctx.stream);      // (armed across the host's middle, to the last wait of device_tail)
     EAO_HIP(hipMemcpyAsync(h->depth.p, ctx.host.p, n * 4, hipMemcpyHostToDevice, ctx.stream));
-    if (h->profile) EAO_HIP(hipStreamSynchronize(ctx.stream));
+    if (h->profile) EAO_HIP(drain.wait_more(eao::Drain::Block));
     const auto t1 = std::chrono::steady_clock::now();
     hipLaunchKernelGGL(k_ps_block_init, dim3(h->nBlocks), dim3(64), 0, ctx.stream, I, (const float*)h->depth.p, h->rec.p);
-    const hipError_t launchErr = hipGetLastError();
-    if (launchErr != hipSuccess) (void)hipStreamSynchronize(ctx.stream);
-    EAO_HIP(launchErr);
-    EAO_HIP(hipStreamSynchronize(ctx.stream));      // (the depth left the staging block; the records come back into it)
+    EAO_HIP(hipGetLastError());
+    EAO_HIP(drain.wait_more(eao::Drain::Block));      // (the depth left the staging block; the records come back into it)
     EAO_HIP(hipMemcpyAsync(ctx.host.p, h->rec.p, recBytes, hipMemcpyDeviceToHost, ctx.stream));
-    EAO_HIP(eao::wait_latency(ctx.stream));
+    EAO_HIP(drain.wait_more(eao::Drain::Latency));
     h->records.resize((size_t)h->nBlocks);
     std::memcpy(h->records.data(), ctx.host.p, recBytes);
     const auto t2 = std::chrono::steady_clock::now();
@@ -590,11 +590,7 @@ eao_status eao_plane_seg_run(eao_plane_seg* h, const float* depth, int32_t strid
         o.mse = f.mse; o.curvature = f.curvature; o.N = f.N; o.rid = f.rid; o.kept = f.kept;
         std::memcpy(o.coef, f.coef, 16);
     }
-    st = device_tail(h, ctx);
-    if (st) {
-        (void)hipStreamSynchronize(ctx.stream);
-        return st;
-    }
+    if ((st = device_tail(h, ctx, drain))) return st;
     const auto t4 = std::chrono::steady_clock::now();
     auto us = [](std::chrono::steady_clock::time_point a, std::chrono::steady_clock::time_point b) { return std::chrono::duration<double, std::micro>(b - a).count(); };
     h->stageUs[0] = us(t0, t1); h->stageUs[1] = us(t1, t2); h->stageUs[2] = us(t2, t3); h->stageUs[3] = us(t3, t4);
@@ -654,8 +650,9 @@ eao_status eao_plane_seg_cloud(eao_plane_seg* h, int32_t plane, int32_t cap, flo
         if (st) return st;
         const size_t bytes = (size_t)p.cloud_count * 16;
         if ((st = ctx.host.reserve(bytes))) return st;
+        eao::Drain drain(ctx.stream);
         EAO_HIP(hipMemcpyAsync(ctx.host.p, h->cloud.p + p.cloud_offset, bytes, hipMemcpyDeviceToHost, ctx.stream));
-        EAO_HIP(eao::wait_latency(ctx.stream));
+        EAO_HIP(drain.wait(eao::Drain::Latency));
         const float* q = (const float*)ctx.host.p;
         for (int32_t i = 0; i < p.cloud_count; i++) { xyz[3 * i] = q[4 * i]; xyz[3 * i + 1] = q[4 * i + 1]; xyz[3 * i + 2] = q[4 * i + 2]; }
     }
@@ -672,8 +669,9 @@ eao_status eao_plane_seg_membership(eao_plane_seg* h, int32_t* image) {
     if (st) return st;
     const size_t bytes = (size_t)h->nPixels * 4;
     if ((st = ctx.host.reserve(bytes))) return st;
+    eao::Drain drain(ctx.stream);
     EAO_HIP(hipMemcpyAsync(ctx.host.p, h->member.p, bytes, hipMemcpyDeviceToHost, ctx.stream));
-    EAO_HIP(eao::wait_latency(ctx.stream));
+    EAO_HIP(drain.wait(eao::Drain::Latency));
     std::memcpy(image, ctx.host.p, bytes);
     return EAO_OK;
 }

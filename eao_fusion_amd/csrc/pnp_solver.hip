@@ -220,13 +220,7 @@ __global__ __launch_bounds__(kWave) void k_pnp_finish(const Rec* __restrict__ W)
 struct PnpCtx : ThreadStream {
     DevBuf<unsigned char> dev;
     std::vector<unsigned char> host;
-    bool measured = false;      // EAO_PNP_EVENTS=1 (tools/bench_pnp_solver.py): an event before and after each kernel of this thread's calls
-    hipEvent_t ev[kKernels + 1] = {};
-    float ms[kKernels] = {};
-    ~PnpCtx() {
-        for (hipEvent_t e : ev)
-            if (e) (void)hipEventDestroy(e);
-    }
+    KernelClock<kKernels> clock;      // EAO_PNP_EVENTS=1 (tools/bench_pnp_solver.py)
 };
 thread_local PnpCtx g_pnp;
 
@@ -356,31 +350,24 @@ eao_status run_solver(std::vector<Call>& calls) {
         R.best_inlier = d + c.offBest;
     }
     static const bool envEvents = getenv("EAO_PNP_EVENTS") && atoi(getenv("EAO_PNP_EVENTS"));
-    if (envEvents)
-        for (hipEvent_t& e : ctx.ev)
-            if (!e) EAO_HIP(hipEventCreate(&e));
-    auto mark = [&](int k) { if (envEvents) (void)hipEventRecord(ctx.ev[k], ctx.stream); };
+    if (envEvents != ctx.clock.armed()) ctx.clock.arm(envEvents);
     const Rec* dW = (const Rec*)d;
+    Drain drain(ctx.stream);
     EAO_HIP(hipMemcpyAsync(d, h, inEnd, hipMemcpyHostToDevice, ctx.stream));
     EAO_HIP(hipMemsetAsync(d + offOut, 0, outEnd - offOut, ctx.stream));      // slots and hypotheses no kernel writes read as zero
-    mark(0);
+    ctx.clock.mark(0, ctx.stream);
     if (maxEval > 0) hipLaunchKernelGGL(k_pnp_hypotheses, dim3(maxEval, nb), dim3(kWave), 0, ctx.stream, dW);
-    mark(1);
+    ctx.clock.mark(1, ctx.stream);
     hipLaunchKernelGGL(k_pnp_scan, dim3(nb), dim3(kWave), 0, ctx.stream, dW);
-    mark(2);
+    ctx.clock.mark(2, ctx.stream);
     hipLaunchKernelGGL(k_pnp_refine, dim3(maxEval + 1, nb), dim3(kWave), 0, ctx.stream, dW);
-    mark(3);
+    ctx.clock.mark(3, ctx.stream);
     hipLaunchKernelGGL(k_pnp_finish, dim3(nb), dim3(kWave), 0, ctx.stream, dW);
-    mark(4);
-    const hipError_t launchErr = hipGetLastError();
-    if (launchErr != hipSuccess) (void)hipStreamSynchronize(ctx.stream);      // (the upload out of this thread's staging block is enqueued: nothing returns before it ends)
-    EAO_HIP(launchErr);
+    ctx.clock.mark(4, ctx.stream);
+    EAO_HIP(hipGetLastError());
     EAO_HIP(hipMemcpyAsync(h + offOut, d + offOut, outEnd - offOut, hipMemcpyDeviceToHost, ctx.stream));
-    EAO_HIP(wait_latency(ctx.stream));
-    if (envEvents) {
-        for (int k = 0; k < kKernels; k++) EAO_HIP(hipEventElapsedTime(&ctx.ms[k], ctx.ev[k], ctx.ev[k + 1]));
-        ctx.measured = true;
-    }
+    EAO_HIP(drain.wait(Drain::Latency));
+    ctx.clock.collect();
     const Out* outs = (const Out*)(h + offOut);
     for (int b = 0; b < nb; b++) {
         const Call& c = calls[b];
@@ -457,9 +444,7 @@ eao_status eao_pnp_solver_iterate_batch(int32_t n_problems, const eao_pnp_solver
 
 eao_status eao_pnp_solver_last_kernel_ms(float* kernel_ms) {
     EAO_REQUIRE(kernel_ms, "null argument");
-    EAO_REQUIRE(g_pnp.measured, "no measurement on this thread: EAO_PNP_EVENTS=1 and a call of eao_pnp_solver_iterate come first");
-    for (int k = 0; k < kKernels; k++) kernel_ms[k] = g_pnp.ms[k];
-    return EAO_OK;
+    return g_pnp.clock.read(kernel_ms, "no measurement on this thread: EAO_PNP_EVENTS=1 and a call of eao_pnp_solver_iterate come first");
 }
 
 }  // extern "C"

@@ -435,13 +435,14 @@ eao_status run_sim3(const eao_sim3_problem* ps, int nb, eao_sim3_result* rs) {
         R.lastbad = d + offL[b];
         R.out = (Sim3Out*)(d + offOut) + b;
     }
+    Drain drain(c.stream);
     EAO_HIP(hipMemcpyAsync(d, h, inEnd, hipMemcpyHostToDevice, c.stream));
     EAO_HIP(hipEventRecord(c.ev0, c.stream));
     if (nb > 0) hipLaunchKernelGGL(k_optimize_sim3, dim3(nb), dim3(kSim3Threads), 0, c.stream, (const Sim3Rec*)d);
     EAO_HIP(hipGetLastError());
     EAO_HIP(hipEventRecord(c.ev1, c.stream));
     EAO_HIP(hipMemcpyAsync(h + offOut, d + offOut, outEnd - offOut, hipMemcpyDeviceToHost, c.stream));
-    EAO_HIP(hipStreamSynchronize(c.stream));
+    EAO_HIP(drain.wait(Drain::Block));
     EAO_HIP(hipEventElapsedTime(&c.lastMs, c.ev0, c.ev1));
     g_trace.clear();
     g_trace.deviceMs = c.lastMs;

@@ -441,6 +441,7 @@ eao_status run_solver(std::vector<Call>& calls) {
         R.inlier = d + c.offInl;
         R.state = *c.state;
     }
+    Drain drain(ctx.stream);
     EAO_HIP(hipMemcpyAsync(d, h, inEnd, hipMemcpyHostToDevice, ctx.stream));
     if (maxEval > 0) hipLaunchKernelGGL(k_sim3_solver_hypotheses, dim3(maxEval, nb), dim3(kWave), 0, ctx.stream, (const SolverRec*)d);
     EAO_HIP(hipGetLastError());
@@ -448,7 +449,7 @@ eao_status run_solver(std::vector<Call>& calls) {
     EAO_HIP(hipGetLastError());
     EAO_HIP(hipMemcpyAsync(h + offOut, d + offOut, outEnd - offOut, hipMemcpyDeviceToHost, ctx.stream));
     if (inspect && total > hypBegin) EAO_HIP(hipMemcpyAsync(h + hypBegin, d + hypBegin, total - hypBegin, hipMemcpyDeviceToHost, ctx.stream));
-    EAO_HIP(hipStreamSynchronize(ctx.stream));
+    EAO_HIP(drain.wait(Drain::Block));
     const SolverOut* outs = (const SolverOut*)(h + offOut);
     for (int b = 0; b < nb; b++) {
         const Call& c = calls[b];

@@ -303,6 +303,7 @@ eao_status eao_triangulate_matches_batch(const eao_frame_view* K1, const eao_tri
     fill(offs[0], K1, depth1, raw_x1, raw_y1);
     for (int k = 0; k < n_nb; k++) fill(offs[k + 1], K2s[k], depth2s[k], raw_x2s ? raw_x2s[k] : nullptr, raw_y2s ? raw_y2s[k] : nullptr);
     std::memcpy(c.in.p + oTab, match12, 4 * cells);
+    eao::Drain drain(c.stream);
     EAO_HIP(hipMemcpyAsync(c.din.p, c.in.p, inBytes, hipMemcpyHostToDevice, c.stream));
     const eao::tri::Side S1 = side(offs[0], K1);
     for (int p0 = 0; p0 < n_nb; p0 += eao::tri::kMaxProb) {
@@ -315,11 +316,9 @@ eao_status eao_triangulate_matches_batch(const eao_frame_view* K1, const eao_tri
         }
         eao::tri::launch(c.stream, S1, *cam1, ratio_factor, np, P, (int*)c.dout.p + (size_t)p0 * n1, (float*)(c.dout.p + oX) + (size_t)p0 * n1 * 3);
     }
-    const hipError_t launchErr = hipGetLastError();
-    if (launchErr != hipSuccess) (void)hipStreamSynchronize(c.stream);      // (the upload out of this thread's staging block is enqueued: nothing returns before it ends)
-    EAO_HIP(launchErr);
+    EAO_HIP(hipGetLastError());
     EAO_HIP(hipMemcpyAsync(c.out.p, c.dout.p, outBytes, hipMemcpyDeviceToHost, c.stream));
-    EAO_HIP(hipStreamSynchronize(c.stream));
+    EAO_HIP(drain.wait(eao::Drain::Block));
     std::memcpy(verdict, c.out.p, 4 * cells);
     std::memcpy(x3d, c.out.p + oX, 12 * cells);
     return EAO_OK;

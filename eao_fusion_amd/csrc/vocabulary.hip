@@ -359,6 +359,7 @@ eao_status transform(const eao_vocabulary* voc, int nf, const uint8_t* desc, con
 
     if (desc) std::memcpy(h + L.desc, desc, N * 32);
     std::memcpy(h + L.fs, frameStart, ((size_t)nf + 1) * 4);
+    eao::Drain drain(stream);
     EAO_HIP(hipMemcpyAsync(d, h, L.inEnd, hipMemcpyHostToDevice, stream));
     DescendArgs da;
     da.nodeDesc = voc->desc.p;
@@ -393,11 +394,9 @@ eao_status transform(const eao_vocabulary* voc, int nf, const uint8_t* desc, con
         hipLaunchKernelGGL(k_voc_descend, dim3(eao::cdiv(maxn, kDescendBlock / kGroup), nf), dim3(kDescendBlock), 0, stream, da);
         hipLaunchKernelGGL(k_voc_assemble, dim3(nf), dim3(block), lds, stream, aa);
     }
-    const hipError_t launchErr = hipGetLastError();
-    if (launchErr != hipSuccess) (void)hipStreamSynchronize(stream);      // (the upload out of this thread's staging block is enqueued: nothing returns before it ends)
-    EAO_HIP(launchErr);
+    EAO_HIP(hipGetLastError());
     EAO_HIP(hipMemcpyAsync(h + L.outBegin, d + L.outBegin, L.end - L.outBegin, hipMemcpyDeviceToHost, stream));
-    EAO_HIP(eao::wait_latency(stream));
+    EAO_HIP(drain.wait(eao::Drain::Latency));
 
     const int* hdr = (const int*)(h + L.hdr);
     for (int f = 0; f < nf; f++) EAO_REQUIRE(hdr[f * 4 + 3] == 0, "the device-resident count is outside 0 .. cap = %d", frameStart[f + 1] - frameStart[f]);
@@ -523,14 +522,13 @@ eao_status eao_bow_score_l1(int32_t nq, const uint32_t* q_id, const double* q_va
         std::memcpy(h + oDi, db_id + b0, M * 4);
         std::memcpy(h + oDv, db_val + b0, M * 8);
     }
+    eao::Drain drain(ctx.stream);
     EAO_HIP(hipMemcpyAsync(d, h, inEnd, hipMemcpyHostToDevice, ctx.stream));
     hipLaunchKernelGGL(k_bow_score_l1, dim3(eao::cdiv(n_db, 4)), dim3(256), 0, ctx.stream, nq, (const unsigned*)(d + oQi), (const double*)(d + oQv), n_db,
                        (const int*)(d + oSt), (const unsigned*)(d + oDi), (const double*)(d + oDv), (double*)(d + oSc));
-    const hipError_t launchErr = hipGetLastError();
-    if (launchErr != hipSuccess) (void)hipStreamSynchronize(ctx.stream);
-    EAO_HIP(launchErr);
+    EAO_HIP(hipGetLastError());
     EAO_HIP(hipMemcpyAsync(h + oSc, d + oSc, (size_t)n_db * 8, hipMemcpyDeviceToHost, ctx.stream));
-    EAO_HIP(eao::wait_latency(ctx.stream));
+    EAO_HIP(drain.wait(eao::Drain::Latency));
     std::memcpy(scores, h + oSc, (size_t)n_db * 8);
     return EAO_OK;
 }

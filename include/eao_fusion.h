@@ -436,7 +436,8 @@ eao_status eao_kf_create_new_map_points(const eao_keyframe* kf1, const eao_tri_c
                                         const eao_tri_camera* cams2, const float* F12s, const float* exs, const float* eys, int32_t only_stereo,
                                         int32_t check_orientation, float ratio_factor, int32_t* match12, int32_t* nmatches, int32_t* verdict, float* x3d);
 /* Diagnostic (tools/bench_triangulation.py): with EAO_TRI_EVENTS=1 in the environment, the device time in ms of the triangulation launches of this thread's last
- * eao_kf_create_new_map_points, from HIP events on its stream.  EAO_ERR_INVALID when there is no measurement. */
+ * eao_kf_create_new_map_points, from HIP events on its stream.  An event call that fails costs that measurement
+ * (-1 in its slot) and never fails the product call.  EAO_ERR_INVALID when no slot is measured. */
 eao_status eao_kf_last_triangulation_ms(float* ms);
 
 /* ---- f1  Frame glue either side of the matcher ------------------------------------------------------------------ */
@@ -977,7 +978,8 @@ typedef struct {
 eao_status eao_initializer_initialize(const eao_initializer_problem* problem, const int32_t* sets, int32_t iterations, eao_initializer_result* result);
 
 /* Diagnostic (tools/bench_initializer.py): with EAO_INIT_EVENTS=1 in the environment, the device time in ms of each of the five kernels of this thread's last
- * eao_initializer_initialize (hypotheses, scores, selection, CheckRT, final rule), from HIP events on its stream.  EAO_ERR_INVALID when there is no measurement. */
+ * eao_initializer_initialize (hypotheses, scores, selection, CheckRT, final rule), from HIP events on its stream.  An event call that fails costs that measurement
+ * (-1 in its slot) and never fails the product call.  EAO_ERR_INVALID when no slot is measured. */
 eao_status eao_initializer_last_kernel_ms(float* kernel_ms /* 5 */);
 
 /* ------------------------------------------------------------------------------------------------
@@ -1058,7 +1060,8 @@ eao_status eao_pnp_solver_iterate_batch(int32_t n_problems, const eao_pnp_solver
                                         eao_pnp_solver_result* results);
 
 /* Diagnostic (tools/bench_pnp_solver.py): with EAO_PNP_EVENTS=1 in the environment, the device time in ms of each of the four kernels of this thread's last
- * eao_pnp_solver_iterate / _batch (hypotheses, scan, refine, finish), from HIP events on its stream.  EAO_ERR_INVALID when there is no measurement. */
+ * eao_pnp_solver_iterate / _batch (hypotheses, scan, refine, finish), from HIP events on its stream.  An event call that fails costs that measurement
+ * (-1 in its slot) and never fails the product call.  EAO_ERR_INVALID when no slot is measured. */
 eao_status eao_pnp_solver_last_kernel_ms(float* kernel_ms /* 4 */);
 
 /* ------------------------------------------------------------------------------------------------
@@ -1367,7 +1370,8 @@ eao_status eao_iforest_scores_batch(int32_t n_obj, const int32_t* start /* n_obj
 eao_status eao_object_iforest_outliers_batch(int32_t n_obj, const int32_t* start /* n_obj+1 */, const float* xyz, const int32_t* class_id /* n_obj */,
                                              int32_t bi_forest, uint8_t* flags, int32_t* removed /* n_obj */, double* scores);
 /* Diagnostic (tools/bench_isolation_forest.py): after eao_iforest_set_profiling(1) on this thread, the device time in ms of k_iforest_build and k_iforest_score of
- * the thread's last forest call, from HIP events on its stream.  EAO_ERR_INVALID when there is no measurement. */
+ * this thread's last forest call, from HIP events on its stream.  An event call that fails costs that measurement
+ * (-1 in its slot) and never fails the product call.  EAO_ERR_INVALID when no slot is measured. */
 eao_status eao_iforest_set_profiling(int32_t on);
 eao_status eao_iforest_last_kernel_ms(float* kernel_ms /* 2 */);
 /* The same measurement inside k_iforest_build: the mean over the trees of the last call, in microseconds of the device's constant clock, of seeding the
@@ -1422,9 +1426,9 @@ eao_status eao_object_np_association_batch(int32_t n_det, const int32_t* det_sta
  * ascend. */
 eao_status eao_object_project_rects_batch(int32_t n_map, const int32_t* map_start /* n_map+1 */, const float* map_xyz, const float* Tcw /* 16 */, float fx, float fy,
                                           float cx, float cy, int32_t cols, int32_t rows, int32_t* rect /* n_map x 4 */, uint8_t* status /* n_map */, float* uv);
-/* Diagnostic (tools/bench_object_association.py): after eao_object_assoc_set_profiling(1) on this thread, the device time in ms of k_np_counts in the thread's
- * last rank-sum call that reached the device and of k_project_rects in its last rect call, from HIP events on its stream; -1 for a kernel that has not run
- * since.  EAO_ERR_INVALID when there is no measurement at all. */
+/* Diagnostic (tools/bench_object_association.py): after eao_object_assoc_set_profiling(1) on this thread, the device time in ms of k_np_counts in this thread's
+ * last rank-sum call that reached the device and of k_project_rects in its last rect call (-1 for a kernel that has not run since), from HIP events on its stream.  An event call that fails costs that measurement
+ * (-1 in its slot) and never fails the product call.  EAO_ERR_INVALID when no slot is measured. */
 eao_status eao_object_assoc_set_profiling(int32_t on);
 eao_status eao_object_assoc_last_kernel_ms(float* kernel_ms /* 2 */);
 
