@@ -6,7 +6,10 @@
 // 64-wide-wavefront machine and batched over frames so that one launch covers every level of every frame:
 //
 //   k_resize          level l from level l-1, 11-bit fixed-point bilinear, 4 px per lane: three aligned u32 loads per
-//                     source row + v_alignbyte extraction, packed u32 stores
+//                     source row + v_alignbyte extraction, packed u32 stores.  In the chained pyramid (more than 32 frames) a level
+//                     takes k_resize_mfma instead (orb_resize_mfma.hip: the horizontal pass as exact int8 matrix-core products from
+//                     host-built tables, orb_resize_tables.h) wherever its tables allow it; k_resize keeps the levels they refuse, a
+//                     level 1 whose caller's image is not 4-byte aligned, and everything under EAO_ORB_RESIZE_MFMA=0
 //   k_fast_cells      one WAVEFRONT per FAST cell: LDS-staged pixel tile (aligned u32 loads), compass pre-test with
 //                     ballot compaction, branch-free arc score of the survivors (min3/max3 sliding windows), LDS NMS
 //                     that is blind across the cell seam (as upstream's per-cell cv::FAST calls are), ballot-scan
@@ -1329,6 +1332,8 @@ namespace orb {
 
 // EAO_ORB_BLUR_MFMA: 1 (default) = the blur on the matrix cores wherever a level can take it, 0 = the VALU kernel only (A/B runs; no result changes).  Read once.
 static int blur_mfma_mode() { static const int mode = [] { const char* e = getenv("EAO_ORB_BLUR_MFMA"); return e ? atoi(e) : 1; }(); return mode; }
+// EAO_ORB_RESIZE_MFMA: 1 (default) = the chained pyramid's levels on the matrix cores wherever a level can take it, 0 = k_resize only (A/B runs; no result changes).  Read once.
+static int resize_mfma_mode() { static const int mode = [] { const char* e = getenv("EAO_ORB_RESIZE_MFMA"); return e ? atoi(e) : 1; }(); return mode; }
 
 // Enqueue the whole pipeline for `batch` frames on the caller's stream `st`; level 0 is read from `d_img` (device memory).
 // The main chain runs on `st` itself -- no hand-over to a private stream and back, which put two cross-stream event hops (~25 us on
@@ -1485,7 +1490,9 @@ eao_status enqueue(eao_orb* h, const uint8_t* d_img, int pitch0, long long fs0, 
             ra.invX = 1. / ((double)g.L[l].w / g.L[l - 1].w); ra.invY = 1. / ((double)g.L[l].h / g.L[l - 1].h);
             ra.srcIsInput = l == 1; ra.pyrFrameBytes = g.pyrFrameBytes;
             ra.frameAffinity = aff;
-            { eao::Range rg("orb: pyramid"); hipLaunchKernelGGL(k_resize, dim3(eao::cdiv(G4 * eao::cdiv(g.L[l].h, kResizeRows), 64), 1, batch), dim3(64), 0, st, ra, s, 0); }
+            // the level on the matrix cores (k_resize_mfma) where its tables allow it; level 1 reads the caller's image in 16-byte pieces at 4-byte alignment
+            if (h->resizeM[l].ok && (l > 1 || src0Aligned) && resize_mfma_mode()) { eao::Range rg("orb: pyramid"); launch_resize_mfma(h, st, s, l, batch, aff); }
+            else { eao::Range rg("orb: pyramid"); hipLaunchKernelGGL(k_resize, dim3(eao::cdiv(G4 * eao::cdiv(g.L[l].h, kResizeRows), 64), 1, batch), dim3(64), 0, st, ra, s, 0); }
             if (l == mid - 1) {
                 EAO_HIP(hipEventRecord(h->evMid, st));
                 EAO_HIP(hipStreamWaitEvent(ss, h->evMid, 0));

@@ -235,6 +235,26 @@ eao_status build_geometry(eao_orb* h, int W, int H) {
             EAO_HIP(hipMemcpy(h->d_blurTab.p, blob.data(), blob.size(), hipMemcpyHostToDevice));
         }
     }
+    // the matrix-core resize of the chained pyramid (orb_resize_tables.h): strip index | row records | strip tables.  As a SOURCE level 0 is the caller's image
+    // (rows readable up to the next multiple of 4, and only when the call's image is 4-byte aligned -- enqueue() decides that per call), a pyramid level up to its pitch.
+    {
+        std::vector<ResizeMLevelIn> in;
+        for (int l = 0; l < c.nlevels; l++) in.push_back({g.L[l].w, g.L[l].h, l == 0 ? (g.L[l].w + 3) & ~3 : g.L[l].pitch});
+        const ResizeMTables T = resize_m_build(in);
+        EAO_REQUIRE(T.maxPiece <= 127, "resize table piece %d does not fit int8", T.maxPiece);
+        int any = 0;
+        for (int l = 0; l < kMaxLevels; l++) { h->resizeM[l] = l < c.nlevels ? T.level[l] : ResizeMLevel{}; any |= h->resizeM[l].ok; }
+        if (any) {
+            h->resizeMRowsOff = (T.idx.size() * sizeof(int) + 15) & ~(size_t)15;
+            h->resizeMStripsOff = h->resizeMRowsOff + T.rows.size() * sizeof(ResizeMRow);
+            std::vector<uint8_t> blob(h->resizeMStripsOff + T.strips.size(), 0);
+            std::memcpy(blob.data(), T.idx.data(), T.idx.size() * sizeof(int));
+            std::memcpy(blob.data() + h->resizeMRowsOff, T.rows.data(), T.rows.size() * sizeof(ResizeMRow));
+            std::memcpy(blob.data() + h->resizeMStripsOff, T.strips.data(), T.strips.size());
+            { eao_status st = h->d_resizeTab.reserve(blob.size()); if (st) return st; }
+            EAO_HIP(hipMemcpy(h->d_resizeTab.p, blob.data(), blob.size(), hipMemcpyHostToDevice));
+        }
+    }
     { eao_status st = h->d_geom.reserve(1); if (st) return st; }
     EAO_HIP(hipMemcpyAsync(h->d_geom.p, &g, sizeof(Geom), hipMemcpyHostToDevice, h->stream));
     { eao_status st = h->d_cells.reserve(h->cells.size()); if (st) return st; }

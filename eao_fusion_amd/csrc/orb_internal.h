@@ -1,5 +1,6 @@
-// orb_internal.h -- what the three translation units of the ORB extractor share (round 6: orb.hip was one 2 900-line file):
+// orb_internal.h -- what the four translation units of the ORB extractor share (round 6: orb.hip was one 2 900-line file):
 //   orb.hip           the pyramid / FAST / blur / orientation + description / stereo kernels and the enqueue of a call (every launch but the quad-tree's)
+//   orb_resize_mfma.hip  k_resize_mfma (the chained pyramid's levels on the matrix cores) and its launch
 //   orb_quadtree.hip  k_quadtree (DistributeOctTree) and its launch
 //   orb_host.hip      the handle: geometry of a frame size, streams and events, the C API entry points that launch nothing themselves
 // Constants, the geometry records the host fills and the kernels read, the handle, and the functions that cross the files.
@@ -14,6 +15,7 @@
 
 #include "common.h"
 #include "orb_blur_tables.h"
+#include "orb_resize_tables.h"
 
 
 namespace eao {
@@ -105,21 +107,6 @@ constexpr int kQtNodeInts = 2 + 2 + 2 + 4 + 4 + 5;   // per list entry next to i
 constexpr size_t kProfEvents = 10;
 
 
-// the same on the host (k_pyramid_fused reads tables built with it): lrintf rounds to nearest even like v_cvt_i32_f32
-inline void resize_coef_host(int d, double inv, int slimit, bool clampHi, int* ofs, unsigned* wpair) {
-    float fr = (float)(((double)d + 0.5) * inv - 0.5);
-    int o = (int)std::floor(fr);
-    fr -= (float)o;
-    if (clampHi) {
-        if (o < 0) { fr = 0; o = 0; }
-        if (o >= slimit - 1) { fr = 0; o = slimit - 1; }
-    }
-    const int w0 = std::min(std::max((int)std::lrintf((1.f - fr) * 2048.f), -32768), 32767);
-    const int w1 = std::min(std::max((int)std::lrintf(fr * 2048.f), -32768), 32767);
-    *ofs = o;
-    *wpair = ((unsigned)w0 & 0xFFFFu) | ((unsigned)w1 << 16);
-}
-
 // first destination index whose clamped source offset is >= bound (destinations 0 .. dn): the ownership boundary
 __host__ __device__ inline int pyr_src_ofs(int d, double inv, int sn) {
     float fr = (float)(((double)d + 0.5) * inv - 0.5);
@@ -184,6 +171,9 @@ struct eao_orb {
     eao::DevBuf<CellDesc> d_cells;
     eao::DevBuf<uint8_t> d_pyr, d_blur, d_in;
     eao::DevBuf<uint8_t> d_blurTab;        // k_blur7_mfma: table index + operand tables of this geometry (orb_blur_tables.h)
+    eao::DevBuf<uint8_t> d_resizeTab;      // k_resize_mfma: strip index | row records | strip tables of this geometry (orb_resize_tables.h)
+    eao::orb::ResizeMLevel resizeM[eao::orb::kMaxLevels] = {};      // ... per level: whether it takes the kernel, and where its records start
+    size_t resizeMRowsOff = 0, resizeMStripsOff = 0;               // ... byte offsets of the row records and of the strip tables in d_resizeTab
     eao::DevBuf<unsigned> d_cellcand, d_cand, d_levelkps;
     eao::DevBuf<unsigned short> d_nodeof;
     eao::DevBuf<unsigned char> d_qtnodes;   // global node lists (only when they do not fit in LDS)
@@ -236,6 +226,8 @@ eao_status upload_frames(eao_orb* h, const uint8_t* img, int width, int height, 
 // orb.hip
 eao_status enqueue(eao_orb* h, const uint8_t* d_img, int pitch0, long long fs0, int batch, eao_keypoint* d_kps, uint8_t* d_desc, int cap, int* d_n, hipStream_t st);
 eao_status enqueue_pyramid_export(eao_orb* h, int frame, int border);
+// orb_resize_mfma.hip: level l (>= 1, resizeM[l].ok) of `batch` frames from level l - 1 on the matrix cores
+void launch_resize_mfma(const eao_orb* h, hipStream_t str, const ImgSrc& s, int l, int batch, int frameAffinity);
 // orb_quadtree.hip: one workgroup per (frame, level) of levels [lFirst, lFirst + nLev) of nb frames from frame f0 on
 void launch_quadtree(const eao_orb* h, hipStream_t str, int nb, int f0, int lFirst, int nLev);
 eao_status quadtree_reserve_lds(size_t bytes);      // raises the kernels' dynamic LDS limit (process-wide, only ever raised)

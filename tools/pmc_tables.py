@@ -43,9 +43,12 @@ SRC = {rel: sha16(rel) for rel in ("eao_fusion_amd/csrc/orb.hip", "eao_fusion_am
 a, b, h = load(R + "_sq_a"), load(R + "_sq_b"), load(R + "_sq_h")
 c = load(R + "_sq_c")                                    # the matrix pipe of the blur (SQ_VALU_MFMA_BUSY_CYCLES), a pass of its own
 blur_kernel = "k_blur7_mfma" if "k_blur7_mfma" in a else "k_blur7"
+resize_kernel = "k_resize_mfma" if "k_resize_mfma" in a else "k_resize"
 for t in (a, b, c):                                    # the blur stage is k_blur7_mfma unless EAO_ORB_BLUR_MFMA=0: one row, named k_blur7, that says which kernel ran
     if "k_blur7_mfma" in t:
         t["k_blur7"] = dict(t.pop("k_blur7_mfma"))
+    if "k_resize_mfma" in t:                           # ... and the pyramid stage k_resize_mfma unless EAO_ORB_RESIZE_MFMA=0 (bench.py looks the stage up as k_resize)
+        t["k_resize"] = dict(t.pop("k_resize_mfma"))
 fe, wr = load(R + "_fetch"), load(R + "_write")
 batch = int(os.environ.get("EAO_PMC_BATCH", "64"))
 steps = a.get("k_blur7", {}).get("launches", 1)         # one blur launch per bench step (timed and profiled alike)
@@ -66,9 +69,9 @@ for name, row in stage.items():
         d.update({k: v for k, v in rb.items() if k != "launches"})
     # launches per bench step (k_fast_cells<true>: one per PROFILED step, which is where its duration is measured)
     d["launches_per_step"] = 1 if name == "k_fast_cells" else round(ra["launches"] / steps, 2)
-    if name == "k_blur7":
+    if name in ("k_blur7", "k_resize"):
         d.update({k: v for k, v in (pick(c) or {}).items() if k == "SQ_VALU_MFMA_BUSY_CYCLES"})
-        d["kernel"] = blur_kernel
+        d["kernel"] = blur_kernel if name == "k_blur7" else resize_kernel
     sq["kernels"][name] = d
 for k, v in h.items():
     if k.startswith("k_hamming"):
@@ -93,7 +96,7 @@ for st, kn in names.items():
     f_tot = sum(v["FETCH_SIZE"] * v["launches"] for k, v in fe.items() if k.startswith(kn) and "FETCH_SIZE" in v) * 1024
     w_tot = sum(v["WRITE_SIZE"] * v["launches"] for k, v in wr.items() if k.startswith(kn) and "WRITE_SIZE" in v) * 1024
     nl = sum(v["launches"] for k, v in fe.items() if k.startswith(kn))
-    tr["kernels"][st] = {"kernel": blur_kernel if st == "blur" else kn, "launches_per_step": round(nl / steps, 2), "fetch_bytes_per_step": int(f_tot / steps), "write_bytes_per_step": int(w_tot / steps),
+    tr["kernels"][st] = {"kernel": blur_kernel if st == "blur" else resize_kernel if st == "pyramid" else kn, "launches_per_step": round(nl / steps, 2), "fetch_bytes_per_step": int(f_tot / steps), "write_bytes_per_step": int(w_tot / steps),
                          "hbm_bytes_per_step_corrected": int((2 * f_tot + w_tot) / steps)}
 json.dump(tr, open(os.path.join(O, R + "_pmc_traffic.json"), "w"), indent=1)
 print(json.dumps(tr["kernels"], indent=1))

@@ -8,7 +8,7 @@ f = glob.glob(sys.argv[1] + "/**/*kernel_trace.csv", recursive=True)[0]
 nsteps = int(sys.argv[2]) if len(sys.argv) > 2 else 1
 rows = sorted(csv.DictReader(open(f)), key=lambda r: int(r["Start_Timestamp"]))
 name = lambda r: (re.search(r"(k_\w+)", r["Kernel_Name"]) or [None, "?"])[1]
-marks = [(i, name(r)) for i, r in enumerate(rows) if name(r) in ("k_orient_describe", "k_resize", "k_pyramid_fused")]
+marks = [(i, name(r)) for i, r in enumerate(rows) if name(r) in ("k_orient_describe", "k_resize", "k_resize_mfma", "k_pyramid_fused")]
 ends = [i for (i, n), (_, n2) in zip(marks, marks[1:]) if n == "k_orient_describe" and n2 != "k_orient_describe"]   # last description launch of each complete step
 S, E = lambda r: int(r["Start_Timestamp"]), lambda r: int(r["End_Timestamp"])
 for k in range(len(ends) - 1 - nsteps, len(ends) - 1):      # (the trace's last step is left out: its successor is what delimits a step)

@@ -24,8 +24,11 @@ for k in sorted(set(fe) | set(wr)):
               "write_KiB_per_launch": wr.get(k, (0, 0))[0], "launches_write": wr.get(k, (0, 0))[1]}
 json.dump(raw, open(os.path.join(os.environ["O"], "pmc_traffic_raw.json"), "w"), indent=1)
 stage = {"pyramid": "k_resize", "fast": "k_fast_cells", "blur": "k_blur7", "quadtree": "k_quadtree", "orient_describe": "k_orient_describe"}
+for st in ("pyramid", "blur"):      # the matrix-core forms (k_resize_mfma, k_blur7_mfma) stand for their stage wherever they ran
+    if stage[st] + "_mfma" in raw:
+        stage[st] += "_mfma"
 # launches of the kernel per bench step (profiled + timed steps of the run: 1 warmup + 3 steps + 3 profiled calls ...): derive from blur (1 per step)
-steps = raw["k_blur7"]["launches_fetch"]
+steps = raw[stage["blur"]]["launches_fetch"]
 out = {"_note": "rocprofv3 --kernel-trace --pmc FETCH_SIZE / --pmc WRITE_SIZE (two separate passes) -- python3 bench.py --steps 3 --warmup 1 "
                 "--full --no-cpu-baseline --no-extra; bytes = KiB counter * 1024.  RAW counters: HBM bytes = 2 x FETCH_SIZE + WRITE_SIZE "
                 "(MI355X_MICROARCH.md; the factor holds for 1-, 4- and 12-byte loads per lane as well: profiles/r05_fetch_calib.txt).",
