@@ -181,6 +181,11 @@ class PlaneSegPlane(C.Structure):   # eao_plane_seg_plane
                 ("coef", C.c_float * 4), ("kept", C.c_int32), ("cloud_offset", C.c_int32), ("cloud_count", C.c_int32), ("n_pixels", C.c_int32)]
 
 
+class YoloxCfg(C.Structure):   # eao_yolox_cfg
+    _fields_ = [("input_size", C.c_int32), ("num_classes", C.c_int32), ("conf_thresh", C.c_float), ("nms_thresh", C.c_float),
+                ("max_proposals", C.c_int32), ("max_batch", C.c_int32)]
+
+
 # every symbol include/eao_fusion.h declares: (restype, argtypes)
 _P = C.c_void_p
 _I = C.c_int32
@@ -303,6 +308,19 @@ SYMBOLS = {
     "eao_object_project_rects_batch": (_I, [_I, _P, _P, _P] + [C.c_float] * 4 + [_I, _I, _P, _P, _P]),
     "eao_object_assoc_set_profiling": (_I, [_I]),
     "eao_object_assoc_last_kernel_ms": (_I, [_P]),
+    "eao_yolox_cfg_default": (None, [C.POINTER(YoloxCfg)]),
+    "eao_yolox_create": (_I, [C.POINTER(YoloxCfg), C.POINTER(_P)]),
+    "eao_yolox_destroy": (None, [_P]),
+    "eao_yolox_preprocess": (_I, [_P, _P, _I, _I, _I, C.c_int64, _I, _I, _P, _I]),
+    "eao_yolox_preprocess_device": (_I, [_P, _P, _I, _I, _I, C.c_int64, _I, _I, _P, _P, _I, _P]),
+    "eao_yolox_decode": (_I, [_P, _P, _I, _P, _P, _P, _I, _P, _P, _P]),
+    "eao_yolox_decode_device": (_I, [_P, _P, _I, _P, _P, _P, _I, _P, _P, _P, _P]),
+    "eao_yolox_buffers": (_I, [_P, C.POINTER(_P), C.POINTER(_P), C.POINTER(_P)]),
+    "eao_yolox_head": (_I, [_P, _P, _I, _P, _P]),
+    "eao_yolox_blob": (_I, [_P, _I, _P]),
+    "eao_yolox_proposals": (_I, [_P, _I, _P, _I, C.POINTER(_I)]),
+    "eao_yolox_set_profiling": (_I, [_P, _I]),
+    "eao_yolox_last_kernel_ms": (_I, [_P, _P]),
     "eao_bundle_adjustment_plan": (_I, [_I, _I, _P, _P, _I, _P, _P, _P, _I, _P, _I, _P, _I, _P, _I, _P, _I, _P, _I]),
 }
 

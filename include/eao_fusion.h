@@ -1432,6 +1432,88 @@ eao_status eao_object_project_rects_batch(int32_t n_map, const int32_t* map_star
 eao_status eao_object_assoc_set_profiling(int32_t on);
 eao_status eao_object_assoc_last_kernel_ms(float* kernel_ms /* 2 */);
 
+/* ---------------------------------------------------------------------------------------------------
+ * yolox: what YOLOX::Detect (reference src/YOLOX.cc:369-410) does AROUND the network, on the device.  The network itself is the integrator's engine; it reads
+ * the blob and writes the head output in HBM, and nothing of either crosses to the host.
+ *   in front   StaticResize (:51-62): r = min(S / (cols * 1.0), S / (rows * 1.0)) stored as float, unpad = (int)(r * cols) -- a float product truncated: a
+ *              1064-wide frame gives 639 columns -- cv::resize's 8-bit bilinear form into the top-left corner of an S x S canvas of 114;
+ *              BlobFromImage (:211-233): B and R swapped in place, (((float)v) / 255.0f - mean[c]) / std[c] with float mean / std, HWC -> CHW: 3 x S x S floats;
+ *              and, where wanted, the grey image Tracking::GrabImageRGBD makes of the same frame (src/Tracking.cc:324-330; OpenCV 3.x:
+ *              (R 4899 + G 9617 + B 1868 + 8192) >> 14) in a pitched buffer eao_orb_extract_batch_device reads directly.
+ *   behind     DecodeOutputs (:235-274): GenerateGridsAndStride (:64-77, strides 8 / 16 / 32), GenerateYoloxProposals (:166-209, box_prob = objectness * cls
+ *              kept when > conf), the descending sort (:85-130), NmsSortedBboxes (:132-164, class-agnostic, inter / union > nms), the division by `scale` (the
+ *              float r above) and the clip to [0, img_w - 1] x [0, img_h - 1] (:258-272).
+ * Two things are not the reference's own, and the library says when they matter:
+ *   exp        w and h are exp(feat) * stride (:183-184).  That call is glibc's expf, which is not correctly rounded and is chosen by CPU at run time: the
+ *              reference is not pinned there.  The library defines both through the double-precision exponential rounded once to float.
+ *   ties       the reference's quicksort orders proposals of EQUAL prob by its own swaps; the library orders them by proposal index (anchor * classes + class)
+ *              and reports n_tied, the number of proposals that share their prob with another one.  When n_tied > 0 the reference's order may differ;
+ *              include/eaofusion/YOLOX.h then decodes on the host, as it does when a frame has more than max_proposals proposals.
+ * Calls on one handle are serialised; handles are independent (one stream each). */
+#define EAO_YOLOX_INPUT_SIZE 640              /* include/YOLOX.h:71-72 */
+#define EAO_YOLOX_NUM_CLASSES 80              /* src/YOLOX.cc:168 */
+#define EAO_YOLOX_PAD 114                     /* :59 */
+#define EAO_YOLOX_DEFAULT_PROPOSALS 4096
+#define EAO_YOLOX_MAX_PROPOSALS 16384
+#define EAO_YOLOX_MAX_INPUT_SIZE 2048
+#define EAO_YOLOX_MAX_CLASSES 1024
+#define EAO_YOLOX_MAX_BATCH 256
+#define EAO_YOLOX_MAX_IMAGE 16384
+typedef struct eao_yolox eao_yolox;
+typedef struct {
+    int32_t input_size;       /* S: square, a multiple of 32 (the reference's 640) */
+    int32_t num_classes;      /* 80: a head row is 5 + num_classes floats */
+    float conf_thresh;        /* BBOX_CONF_THRESH 0.3 passed on as a float (include/YOLOX.h:34, src/YOLOX.cc:241); >= 0 */
+    float nms_thresh;         /* NMS_THRESH 0.65 as a float (include/YOLOX.h:33, src/YOLOX.cc:247) */
+    int32_t max_proposals;    /* per frame; the reference has no cap: more is EAO_ERR_CAPACITY */
+    int32_t max_batch;        /* frames per call */
+} eao_yolox_cfg;
+typedef struct {
+    float x, y, w, h, prob;   /* Object::rect and prob (include/YOLOX.h:36-46) */
+    int32_t label;
+} eao_yolox_object;
+/* the reference's literals: 640, 80, 0.3f, 0.65f; max_proposals 4096, max_batch 1 */
+void eao_yolox_cfg_default(eao_yolox_cfg* cfg);
+eao_status eao_yolox_create(const eao_yolox_cfg* cfg, eao_yolox** out);
+void eao_yolox_destroy(eao_yolox* h);
+/* StaticResize + BlobFromImage (:51-62, :211-233) of `batch` host frames of interleaved 8-bit colour, rows `stride` bytes apart (>= 3 * width), frames
+ * frame_stride bytes apart: one upload, one kernel.  The blob stays in the handle (eao_yolox_buffers names it, eao_yolox_blob copies it out).  The blob reads
+ * byte 2 - c of a pixel for channel c whatever `rgb` says, as the reference does; rgb (Tracking::mbRGB) only selects RGB2GRAY or BGR2GRAY for the grey image
+ * (:324-330), which is written to `gray` (optional host array, batch x height rows of gray_stride >= width bytes).  A frame without a letterbox (an unpadded
+ * size of 0, where cv::resize asserts) is EAO_ERR_INVALID; every EAO_ERR_INVALID leaves the outputs untouched. */
+eao_status eao_yolox_preprocess(eao_yolox* h, const uint8_t* frames, int32_t width, int32_t height, int32_t stride, int64_t frame_stride, int32_t batch, int32_t rgb,
+                                uint8_t* gray, int32_t gray_stride);
+/* The same over device pointers, asynchronous on `stream` (a hipStream_t; NULL = the null stream): d_blob receives batch x 3 x S x S floats (16-byte
+ * aligned), d_gray (optional, 4-byte aligned) batch x height rows of gray_stride bytes, gray_stride a multiple of 64 -- the bytes of a row behind `width` are
+ * written too (zeros).  One upload of the colour frame feeds the detector and, through d_gray, eao_orb_extract_batch_device on the same stream. */
+eao_status eao_yolox_preprocess_device(eao_yolox* h, const uint8_t* d_frames, int32_t width, int32_t height, int32_t stride, int64_t frame_stride, int32_t batch,
+                                       int32_t rgb, float* d_blob, uint8_t* d_gray, int32_t gray_stride, void* stream);
+/* DecodeOutputs (:235-274) of `batch` head outputs (host array, batch x anchors x (5 + num_classes) floats; anchors = sum of (S / stride)^2) for images of
+ * img_w[f] x img_h[f] pixels (`scale` is their r).  objects: batch x cap records, frame f's at objects + f * cap, in the order the reference leaves them
+ * (descending prob); n[f] of them; n_proposals[f]: the proposals before suppression; n_tied[f]: see above.
+ * EAO_ERR_CAPACITY: a frame has more than max_proposals proposals -- n_proposals holds the true counts of every frame and nothing else is written -- or more
+ * than cap objects -- n and n_proposals hold the counts and no object is written. */
+eao_status eao_yolox_decode(eao_yolox* h, const float* prob, int32_t batch, const int32_t* img_w, const int32_t* img_h, eao_yolox_object* objects, int32_t cap,
+                            int32_t* n, int32_t* n_proposals, int32_t* n_tied);
+/* The same over a head output in HBM, enqueued on `stream` behind whatever wrote it, and waited for: the result arrays are host arrays. */
+eao_status eao_yolox_decode_device(eao_yolox* h, const float* d_prob, int32_t batch, const int32_t* img_w, const int32_t* img_h, eao_yolox_object* objects,
+                                   int32_t cap, int32_t* n, int32_t* n_proposals, int32_t* n_tied, void* stream);
+/* The handle's own device buffers and stream, for an engine that runs between eao_yolox_preprocess and eao_yolox_decode_device (DoInference, :350-366, without its
+ * two copies): d_blob max_batch x 3 x S x S floats, d_prob max_batch x anchors x (5 + num_classes) floats.  Any of the three may be NULL. */
+eao_status eao_yolox_buffers(eao_yolox* h, float** d_blob, float** d_prob, void** stream);
+/* `batch` head outputs at d_prob copied to the host array prob, behind whatever `stream` holds: what the host decode of include/eaofusion/YOLOX.h reads when the
+ * library reports a tie or an overflow. */
+eao_status eao_yolox_head(eao_yolox* h, const float* d_prob, int32_t batch, float* prob, void* stream);
+/* Inspection: the blob of frame `frame` of the last eao_yolox_preprocess (3 x S x S floats), and the sorted proposals of frame `frame` of the last decode that
+ * did not overflow (unscaled boxes x0, y0, w, h of :185-199; proposals may be NULL to ask for the count). */
+eao_status eao_yolox_blob(eao_yolox* h, int32_t frame, float* blob);
+eao_status eao_yolox_proposals(eao_yolox* h, int32_t frame, eao_yolox_object* proposals, int32_t cap, int32_t* n);
+/* Diagnostic (tools/bench_yolox.py): after eao_yolox_set_profiling(h, 1), the device time in ms of k_yolox_pre, k_yolox_proposals, k_yolox_rank, k_yolox_mask and
+ * k_yolox_scan of the handle's last calls (-1 for a kernel that has not run since), from HIP events on the call's stream; eao_yolox_preprocess_device then waits
+ * for its kernel.  An event call that fails costs that measurement and never fails the product call.  EAO_ERR_INVALID when no slot is measured. */
+eao_status eao_yolox_set_profiling(eao_yolox* h, int32_t on);
+eao_status eao_yolox_last_kernel_ms(eao_yolox* h, float* kernel_ms /* 5 */);
+
 /* The value of EAO_ABI_VERSION the library was built with. Bumped whenever an entry point's parameter list or a struct's layout changes (round 3
  * changed eao_tracker_track_local_map and eao_track_result in place); a caller compiled against another version must not call into the library.
  * Result structs are zero-initialised by the caller (`eao_track_result R = {0};`) before their array pointers are set: a pointer member the

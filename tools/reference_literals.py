@@ -37,6 +37,11 @@ _NUMF = r"([0-9.]+f?)"
 _PNP_DEFAULTS = r"double probability = %s, int minInliers = %s , int maxIterations = %s, int minSet = %s, float epsilon = %s," % ((_NUMF,) * 5)
 _PNP_RELOC = r"SetRansacParameters\(%s, %s, %s, %s, %s, %s\);" % ((_NUMF,) * 6)
 
+_YOLOX_MEAN = r"std::vector<float> mean = \{%s, %s, %s\};" % ((_GRP,) * 3)
+_YOLOX_STD = r"std::vector<float> std = \{%s, %s, %s\};" % ((_GRP,) * 3)
+_YOLOX_STRIDES = r"std::vector<int> strides = \{(\d+), (\d+), (\d+)\};"
+_YOLOX_CLASSES = r"if \(" + " && ".join([r"objInfo\.label != (\d+)"] * 14) + r"\)"
+
 # feature -> rows of (name, file, line, the expression around the literal, the capture group that holds it)
 TABLES = {
     # the hot path's thresholds, gates and schedules (tools/gen_ref_constants.py adds a C type and a note to each and emits the two ref_constants.inc)
@@ -197,6 +202,20 @@ TABLES = {
         ("CRITICAL_R2", 943, _R2 % (_NUM, _GRP, _NUM)),
         ("VARIANCE_DIVISOR_R2", 943, _R2 % (_NUM, _NUM, _GRP)),
     ]),
+    # YOLOX::Detect around the network, and what Tracking::GrabImageRGBD keeps of its result
+    "yolox": [
+        ("NMS_THRESH", "include/YOLOX.h", 33, r"#define NMS_THRESH ([0-9.]+)", 1),
+        ("BBOX_CONF_THRESH", "include/YOLOX.h", 34, r"#define BBOX_CONF_THRESH ([0-9.]+)", 1),
+        ("INPUT_W", "include/YOLOX.h", 71, r"const int INPUT_W = (\d+);", 1),
+        ("INPUT_H", "include/YOLOX.h", 72, r"const int INPUT_H = (\d+);", 1),
+        ("PAD", "src/YOLOX.cc", 59, r"cv::Scalar\((\d+), \1, \1\)\);", 1),
+        ("NUM_CLASS", "src/YOLOX.cc", 168, r"const int num_class = (\d+);", 1),
+        ("MEAN_R", "src/YOLOX.cc", 219, _YOLOX_MEAN, 1), ("MEAN_G", "src/YOLOX.cc", 219, _YOLOX_MEAN, 2), ("MEAN_B", "src/YOLOX.cc", 219, _YOLOX_MEAN, 3),
+        ("STD_R", "src/YOLOX.cc", 220, _YOLOX_STD, 1), ("STD_G", "src/YOLOX.cc", 220, _YOLOX_STD, 2), ("STD_B", "src/YOLOX.cc", 220, _YOLOX_STD, 3),
+        ("STRIDE_0", "src/YOLOX.cc", 238, _YOLOX_STRIDES, 1), ("STRIDE_1", "src/YOLOX.cc", 238, _YOLOX_STRIDES, 2), ("STRIDE_2", "src/YOLOX.cc", 238, _YOLOX_STRIDES, 3),
+        ("HALF", "src/YOLOX.cc", 185, r"float x0 = x_center - w \* ([0-9.]+f);", 1),
+        ("TRACKING_MIN_PROB", "src/Tracking.cc", 434, r"if \(objInfo\.prob < ([0-9.]+)\)", 1),
+    ] + [("TRACKING_CLASS_%d" % k, "src/Tracking.cc", 439, _YOLOX_CLASSES, k + 1) for k in range(14)],
 }
 
 
