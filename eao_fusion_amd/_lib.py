@@ -181,6 +181,11 @@ class PlaneSegPlane(C.Structure):   # eao_plane_seg_plane
                 ("coef", C.c_float * 4), ("kept", C.c_int32), ("cloud_offset", C.c_int32), ("cloud_count", C.c_int32), ("n_pixels", C.c_int32)]
 
 
+class DetnetDesc(C.Structure):   # eao_detnet_desc
+    _fields_ = [("classes", C.c_int32), ("anchors", C.c_int32), ("tensors", C.c_int32), ("ops", C.c_int32), ("input_size", C.c_int32), ("max_batch", C.c_int32),
+                ("weight_bytes", C.c_int64), ("activation_bytes", C.c_int64), ("flops", C.c_double)]
+
+
 class YoloxCfg(C.Structure):   # eao_yolox_cfg
     _fields_ = [("input_size", C.c_int32), ("num_classes", C.c_int32), ("conf_thresh", C.c_float), ("nms_thresh", C.c_float),
                 ("max_proposals", C.c_int32), ("max_batch", C.c_int32)]
@@ -321,6 +326,15 @@ SYMBOLS = {
     "eao_yolox_proposals": (_I, [_P, _I, _P, _I, C.POINTER(_I)]),
     "eao_yolox_set_profiling": (_I, [_P, _I]),
     "eao_yolox_last_kernel_ms": (_I, [_P, _P]),
+    "eao_detnet_create": (_I, [_P, C.c_int64, _I, _I, C.POINTER(_P)]),
+    "eao_detnet_create_from_file": (_I, [C.c_char_p, _I, _I, C.POINTER(_P)]),
+    "eao_detnet_destroy": (None, [_P]),
+    "eao_detnet_info": (_I, [_P, C.POINTER(DetnetDesc)]),
+    "eao_detnet_forward": (_I, [_P, _P, _P, _I, _P]),
+    "eao_detnet_tensor": (_I, [_P, _I, _I, _P]),
+    "eao_detnet_set_tensor": (_I, [_P, _I, _I, _P]),
+    "eao_detnet_set_profiling": (_I, [_P, _I]),
+    "eao_detnet_last_op_ms": (_I, [_P, _P, _I]),
     "eao_bundle_adjustment_plan": (_I, [_I, _I, _P, _P, _I, _P, _P, _P, _I, _P, _I, _P, _I, _P, _I, _P, _I, _P, _I]),
 }
 

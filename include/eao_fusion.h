@@ -1514,6 +1514,49 @@ eao_status eao_yolox_proposals(eao_yolox* h, int32_t frame, eao_yolox_object* pr
 eao_status eao_yolox_set_profiling(eao_yolox* h, int32_t on);
 eao_status eao_yolox_last_kernel_ms(eao_yolox* h, float* kernel_ms /* 5 */);
 
+/* ---- The detector network: the engine YOLOX::YOLOX deserialises (src/System.cc:112, src/YOLOX.cc:7-48) and DoInference runs (:331-367) ---------------------------
+ * The reference's engine is a TensorRT blob.  Here the network is a graph of convolutions read from a model file (csrc/detnet_internal.h states the format, the
+ * checks and the arithmetic; eao_fusion_amd/detnet.py writes it, tools/export_detnet.py makes it from a torch module): FOCUS, CONV (k 1 or 3, stride 1 or 2, bias,
+ * none / SiLU / sigmoid, optional residual), MAXPOOL and UPSAMPLE2 over channel ranges of NHWC tensors.  The prediction convolutions write straight into the head
+ * output eao_yolox_decode_device reads: anchors x (5 + classes) floats, strides 8, 16, 32 in that order (:64-77, :166-209).
+ * A convolution is DEFINED as acc = bias, then acc = fmaf(x, w, acc) over ky, kx, ci ascending with +0.0f outside the map; sigmoid as
+ * 1.0f / (1.0f + exp(-x)) with the exponential of the eao_yolox_* section.  The f32-input MFMA of gfx950 computes exactly that chain, so the output is the
+ * host walk's (tools/detnet_walk.cpp), bit for bit.  Grouped and depthwise convolutions (YOLOX-nano, YOLOX-tiny) are refused.
+ * Arguments and the file are checked before the device is touched: a bad file is EAO_ERR_INVALID with a message and never an out-of-range read.
+ * Calls on one handle are serialised; handles are independent. */
+typedef struct eao_detnet eao_detnet;
+typedef struct {
+    int32_t classes, anchors;         /* a head row is 5 + classes floats; anchors = sum of (S / stride)^2, 0 for a model without a head */
+    int32_t tensors, ops;
+    int32_t input_size, max_batch;
+    int64_t weight_bytes;             /* on the device */
+    int64_t activation_bytes;         /* the one allocation all intermediate tensors of max_batch frames live in */
+    double flops;                     /* of one frame: 2 per multiply-add of the convolutions */
+} eao_detnet_desc;
+/* YOLOX::YOLOX (src/YOLOX.cc:7-48) over a model in memory (`bytes` bytes; it is not referenced after the call) for an input of input_size x input_size (a
+ * multiple of 32: tensors are sized by their downscale, one file serves every size) and up to max_batch frames per call. */
+eao_status eao_detnet_create(const void* model, int64_t bytes, int32_t input_size, int32_t max_batch, eao_detnet** out);
+/* The same from a file, as the reference's constructor reads its engine file (:9-20). */
+eao_status eao_detnet_create_from_file(const char* path, int32_t input_size, int32_t max_batch, eao_detnet** out);
+/* YOLOX::~YOLOX (include/YOLOX.h:92, src/YOLOX.cc:43-49). */
+void eao_detnet_destroy(eao_detnet* net);
+/* What DoInference asks its engine (:333-347: the bindings, their types, getMaxBatchSize) and what the caller sizes d_prob by (output_size, src/YOLOX.cc:34-39). */
+eao_status eao_detnet_info(const eao_detnet* net, eao_detnet_desc* info);
+/* DoInference (:331-367) without its two copies: `batch` blobs of 3 x S x S floats at d_blob -> batch head outputs at d_prob, both in HBM; a sequence of
+ * launches on `stream` (a hipStream_t; NULL = the null stream), asynchronous unless profiling is on.  d_prob may be NULL for a model without a head.
+ * The handle's activations are written by the launches: a forward on another stream has to be ordered behind the previous one by the caller. */
+eao_status eao_detnet_forward(eao_detnet* net, const float* d_blob, float* d_prob, int32_t batch, void* stream);
+/* Inspection (the per-layer tests; the reference has no counterpart, its engine is opaque behind context->enqueue, :359): tensor `tensor` of frame `frame` of the
+ * last forward, H x W x C floats (NHWC); waits for the device.  eao_detnet_set_tensor fills one: the
+ * caller's input tensors of a single-op graph, or the channels of a tensor no op writes (they keep what they are given). */
+eao_status eao_detnet_tensor(eao_detnet* net, int32_t tensor, int32_t frame, float* out);
+eao_status eao_detnet_set_tensor(eao_detnet* net, int32_t tensor, int32_t frame, const float* in);
+/* Diagnostic (tools/bench_detnet.py): after eao_detnet_set_profiling(net, 1) a forward records a HIP event around every op and waits; eao_detnet_last_op_ms
+ * gives the device time in ms of each op of the last forward (cap >= ops; -1 where not measured).  An event call that fails costs that measurement and never
+ * fails the product call (the reference runs context->enqueue, :359, untimed).  EAO_ERR_INVALID when nothing is measured. */
+eao_status eao_detnet_set_profiling(eao_detnet* net, int32_t on);
+eao_status eao_detnet_last_op_ms(eao_detnet* net, float* op_ms, int32_t cap);
+
 /* The value of EAO_ABI_VERSION the library was built with. Bumped whenever an entry point's parameter list or a struct's layout changes (round 3
  * changed eao_tracker_track_local_map and eao_track_result in place); a caller compiled against another version must not call into the library.
  * Result structs are zero-initialised by the caller (`eao_track_result R = {0};`) before their array pointers are set: a pointer member the
