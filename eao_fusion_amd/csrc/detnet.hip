@@ -7,7 +7,7 @@
 //                         LDS in stages of 64 or 128, both operands k-major with an odd row pitch.  The accumulator starts as the bias and one accumulator carries the
 //                         whole chain of an output element, so the result is the fmaf chain of detnet_internal.h bit for bit.  Behind K (and only there) A is padded
 //                         with +0.0f and B with -0.0f: their product -0.0f changes no accumulator, not even -0.0f.  Bias, activation, residual and the strided
-//                         store are the epilogue.
+//                         store are the epilogue.  Which form an op takes is conv_form() of detnet_internal.h.
 //   k_detnet_focus, k_detnet_maxpool, k_detnet_upsample2   one lane per output element.
 // A forward pass is a sequence of launches on the caller's stream: no capture, no stream of its own, no host hop.
 #include <cmath>
@@ -179,8 +179,6 @@ __global__ __launch_bounds__(256) void k_detnet_upsample2(MapArgs A) {
     A.dst[n * A.dstFrame + ((long long)y * A.Wo + x) * A.dstC + A.dstC0 + c] = A.src[n * A.srcFrame + ((long long)(y >> 1) * A.Wi + (x >> 1)) * A.srcC + A.srcC0 + c];
 }
 
-constexpr int kFillBlocks = 256;      // a 32 x 32 x 2 grid below one block per compute unit leaves units idle: the 16 x 16 x 4 tiles are a quarter of the size
-
 }  // namespace
 
 struct eao_detnet {
@@ -216,12 +214,17 @@ eao_status launch_op(eao_detnet* h, const Op& op, const float* dBlob, float* dPr
         A.resC = r.res >= 0 ? net.tensors[(size_t)r.res].C : 0; A.resC0 = (int)r.res_c0;
         A.Hi = Ts.H; A.Wi = Ts.W; A.Ho = Ho; A.Wo = Wo; A.Ci = (int)r.src_c; A.Co = (int)r.dst_c; A.k = (int)r.k; A.stride = (int)r.stride; A.act = (int)r.act;
         A.M = batch * Ho * Wo; A.K = (int)(r.k * r.k * r.src_c);
-        if (A.Co <= 16)
+        switch (conv_form(A.M, A.Co)) {
+        case FORM_16x16x4_ONE:
             hipLaunchKernelGGL((k_detnet_conv<16, 1>), dim3((unsigned)eao::cdiv(A.M, 64), 1), dim3(256), 0, s, A);
-        else if ((long long)eao::cdiv(A.M, 128) * eao::cdiv(A.Co, 64) >= kFillBlocks)
+            break;
+        case FORM_32x32x2:
             hipLaunchKernelGGL((k_detnet_conv<32, 2>), dim3((unsigned)eao::cdiv(A.M, 128), (unsigned)eao::cdiv(A.Co, 64)), dim3(256), 0, s, A);
-        else
+            break;
+        case FORM_16x16x4_TWO:
             hipLaunchKernelGGL((k_detnet_conv<16, 2>), dim3((unsigned)eao::cdiv(A.M, 64), (unsigned)eao::cdiv(A.Co, 32)), dim3(256), 0, s, A);
+            break;
+        }
     } else {
         MapArgs A;
         A.src = src; A.dst = dst; A.srcFrame = srcFrame; A.dstFrame = dstFrame;

@@ -95,6 +95,18 @@ EAO_YOLOX_HD inline float pool_max(float a, float b) {
 }
 constexpr uint32_t kNegInfBits = 0xff800000u;
 
+// ---------------------------------------------------------------- the tile form of a convolution (which instantiation of k_detnet_conv launch_op takes)
+// All three give the same bits; the rule is stated here so that the host (tools/detnet_walk.cpp `forms`) can say which kernel a test ran.
+enum ConvForm : int { FORM_16x16x4_ONE = 0, FORM_16x16x4_TWO = 1, FORM_32x32x2 = 2 };      // 64 x 16, 64 x 32 and 128 x 64 outputs per block
+constexpr int kFillBlocks = 256;      // a 32 x 32 x 2 grid below one block per compute unit leaves units idle: the 16 x 16 x 4 tiles are a quarter of the size
+inline const char* conv_form_name(ConvForm f) { return f == FORM_32x32x2 ? "32x32x2" : f == FORM_16x16x4_TWO ? "16x16x4x2" : "16x16x4x1"; }
+// M: the output pixels over the batch
+inline ConvForm conv_form(long long M, int Cout) {
+    if (Cout <= 16) return FORM_16x16x4_ONE;
+    if (((M + 127) / 128) * ((Cout + 63) / 64) >= kFillBlocks) return FORM_32x32x2;
+    return FORM_16x16x4_TWO;
+}
+
 // ---------------------------------------------------------------- the loader
 struct Fail {
     std::string msg;

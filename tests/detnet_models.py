@@ -44,9 +44,10 @@ def blob(S, seed, batch=None):
     return rng.uniform(-2.0, 2.5, (3, S, S) if batch is None else (batch, 3, S, S)).astype(F)
 
 
-def single_conv(x, w, b, stride=1, act=D.NONE, res=None, src_total=None, src_c0=0, dst_total=None, dst_c0=0):
+def single_conv(x, w, b, stride=1, act=D.NONE, res=None, src_total=None, src_c0=0, dst_total=None, dst_c0=0, res_total=None, res_c0=0):
     """one convolution over a fixed map.  x: (H, W, Cin); the source is the channel range src_c0 .. of a caller's tensor of src_total channels, the destination the
-    range dst_c0 .. of a tensor of dst_total channels.  Returns dict(model, inputs {tensor: array}, src, dst, res, out_shape)."""
+    range dst_c0 .. of a tensor of dst_total channels, the residual (Ho, Wo, Cout) the range res_c0 .. of a caller's tensor of res_total channels with 777.0 around
+    it.  Returns dict(model, inputs {tensor: array}, src, dst, res, out_shape)."""
     H, W, ci = x.shape
     co, k = w.shape[0], w.shape[1]
     p = (k - 1) // 2
@@ -60,26 +61,32 @@ def single_conv(x, w, b, stride=1, act=D.NONE, res=None, src_total=None, src_c0=
     inputs = {ts: full}
     tr = None
     if res is not None:
-        tr = m.fixed(co, Ho, Wo, caller_input=True)
-        inputs[tr] = np.asarray(res, F)
-    m.conv((ts, src_c0, ci), (td, dst_c0, co), w, b, stride=stride, act=act, res=None if tr is None else (tr, 0))
+        res_total = res_total or co
+        tr = m.fixed(res_total, Ho, Wo, caller_input=True)
+        inputs[tr] = np.full((Ho, Wo, res_total), F(777.0))
+        inputs[tr][:, :, res_c0:res_c0 + co] = res
+    m.conv((ts, src_c0, ci), (td, dst_c0, co), w, b, stride=stride, act=act, res=None if tr is None else (tr, res_c0))
     return dict(model=m, inputs=inputs, src=ts, dst=td, res=tr, out_shape=(Ho, Wo, dst_total), S=32)
 
 
-def single_map_op(kind, x, k=0):
-    """MAXPOOL or UPSAMPLE2 over a fixed map x: (H, W, C)"""
+def single_map_op(kind, x, k=0, src_total=None, src_c0=0, dst_total=None, dst_c0=0):
+    """MAXPOOL or UPSAMPLE2 over a fixed map x: (H, W, C), read as the channel range src_c0 .. of a caller's tensor of src_total channels (777.0 around it) and
+    written to the range dst_c0 .. of a tensor of dst_total channels"""
     H, W, c = x.shape
+    src_total, dst_total = src_total or c, dst_total or c
     m = D.Model(1)
-    ts = m.fixed(c, H, W, caller_input=True)
+    ts = m.fixed(src_total, H, W, caller_input=True)
+    full = np.full((H, W, src_total), F(777.0))
+    full[:, :, src_c0:src_c0 + c] = x
     if kind == D.MAXPOOL:
-        td = m.fixed(c, H, W)
-        m.maxpool((ts, 0, c), (td, 0, c), k)
-        shape = (H, W, c)
+        td = m.fixed(dst_total, H, W)
+        m.maxpool((ts, src_c0, c), (td, dst_c0, c), k)
+        shape = (H, W, dst_total)
     else:
-        td = m.fixed(c, 2 * H, 2 * W)
-        m.upsample2((ts, 0, c), (td, 0, c))
-        shape = (2 * H, 2 * W, c)
-    return dict(model=m, inputs={ts: np.asarray(x, F)}, src=ts, dst=td, out_shape=shape, S=32)
+        td = m.fixed(dst_total, 2 * H, 2 * W)
+        m.upsample2((ts, src_c0, c), (td, dst_c0, c))
+        shape = (2 * H, 2 * W, dst_total)
+    return dict(model=m, inputs={ts: full}, src=ts, dst=td, out_shape=shape, S=32)
 
 
 def focus_only():
@@ -227,6 +234,27 @@ def walk_run(exe, model, S, blob_=None, inputs=None):
     tensors = {t: act[off:off + int(np.prod(shape))].reshape(shape).copy() for t, (kind, off, shape) in lay.items() if kind in (D.SCALED, D.FIXED, D.FIXED_INPUT)}
     head = prob.reshape(-1, 5 + model.classes) if prob.size else None
     return tensors, head
+
+
+def walk_forms(exe, model, S, batch):
+    """`detnet_walk forms`: one dict per op -- kind (a word), M, Cout, k, stride, res, src_c0, dst_c0, head and, for a convolution, form (the tile form the device
+    takes at this batch: "32x32x2", "16x16x4x2" or "16x16x4x1"; None for the other ops)"""
+    with tempfile.TemporaryDirectory() as d:
+        p = os.path.join(d, "m.bin")
+        open(p, "wb").write(model if isinstance(model, bytes) else model.tobytes())
+        r = subprocess.run([exe, "forms", p, str(S), str(batch)], capture_output=True, text=True)
+    assert r.returncode == 0 and not r.stderr and r.stdout.startswith("ok"), (r.returncode, r.stdout[-400:], r.stderr[-2000:])
+    ops = []
+    for line in r.stdout.splitlines()[1:]:
+        q = line.split()
+        f = dict(zip(q[2::2], q[3::2]))
+        ops.append({k: (v if k in ("kind", "form") else int(v)) for k, v in f.items()})
+        ops[-1].setdefault("form", None)
+        assert int(q[1]) == len(ops) - 1
+    return ops
+
+
+LARGE = "32x32x2"
 
 
 def same_bits(a, b):

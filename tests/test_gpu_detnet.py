@@ -109,6 +109,11 @@ def test_convolution(DN, n):
         assert M.same_bits(got[f], want), "%r frame %d" % (c, f)
 
 
+def large_form(sc, batch=1):
+    """whether the device runs the scene's convolution on the 32 x 32 x 2 form (all forms give the same bits: only the rule itself can say)"""
+    return M.walk_forms(M.walk_binary(("-O2",)), sc["model"], 32, batch)[0]["form"] == M.LARGE
+
+
 def test_convolution_takes_the_large_tile_form(DN):
     """128 x 128 outputs over 80 channels: 256 blocks of 128 x 64, the threshold at which the 32 x 32 x 2 form is chosen.  A = the identity (pixel m reads 1 at
     channel m % 64) with an asymmetric B: output (m, co) is W[co][m % 64] = 100 co + m % 64, so a swapped row and column map shows.  Then ordinary values with
@@ -118,14 +123,17 @@ def test_convolution_takes_the_large_tile_form(DN):
     x[np.arange(H * W), np.arange(H * W) % 64] = 1
     w = (100 * np.arange(80)[:, None] + np.arange(64)[None, :]).astype(F).reshape(80, 1, 1, 64)
     sc = M.single_conv(x.reshape(H, W, 64), w, np.zeros(80, F))
+    assert large_form(sc)
     got = run_graph(DN, sc)[0].reshape(H * W, 80)
     assert np.array_equal(got, w.reshape(80, 64).T[np.arange(H * W) % 64])
     rng = np.random.default_rng(77)
     sc = M.single_conv(rng.standard_normal((H, W, 3)).astype(F), rng.standard_normal((80, 3, 3, 3)).astype(F), rng.standard_normal(80).astype(F), 1, 1)
+    assert large_form(sc)
     want = M.walk_run(M.walk_binary(("-O2",)), sc["model"], 32, inputs=sc["inputs"])[0][sc["dst"]]
     assert M.same_bits(run_graph(DN, sc)[0], want)
     # K = 65: one tap behind the 64-deep stage of this form
     sc = M.single_conv(rng.standard_normal((H, W, 65)).astype(F), rng.standard_normal((80, 1, 1, 65)).astype(F), rng.standard_normal(80).astype(F), 1, 2)
+    assert large_form(sc)
     want = M.walk_run(M.walk_binary(("-O2",)), sc["model"], 32, inputs=sc["inputs"])[0][sc["dst"]]
     assert M.same_bits(run_graph(DN, sc)[0], want)
 
@@ -152,8 +160,9 @@ def test_planted_values(DN, name):
         assert (np.abs(want[want != 0]) < F(1.2e-38)).any(), "the scene is meant to produce subnormal outputs"
 
 
-def test_minus_zero_bias_on_every_tile_form(DN):
-    """the -0.0f chain for K = 1, 3, 5, 31, 33 and Cout on both sides of 16: behind K the kernels pad with (+0) * (-0)"""
+def test_minus_zero_bias_on_the_two_small_tile_forms(DN):
+    """the -0.0f chain for K = 1, 3, 5, 31, 33 and Cout on both sides of 16: behind K the kernels pad with (+0) * (-0).  A 3 x 3 map (M = 9) stays on the two
+    16 x 16 x 4 forms; the 32 x 32 x 2 form has test_minus_zero_bias_on_the_large_form (tests/test_gpu_detnet_forms.py)."""
     rng = np.random.default_rng(3)
     for ci in (1, 3, 5, 31, 33):
         for co in (2, 33):

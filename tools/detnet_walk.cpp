@@ -9,6 +9,8 @@
 //     detnet_walk run <model> <S> <blob> <out> [<act>]  one frame: <blob> holds 3 x S x S floats ("-" for zeros), <act> the activation block to start from (the
 //                                                       caller's input tensors); writes <out>.act (the activation block) and <out>.prob (the head)
 //     detnet_walk bench <model> <S> <reps>              times the forward pass of one frame on one thread: prints the median in ms
+//     detnet_walk forms <model> <S> <batch>             one line per op: its kind, M (the output pixels over the batch), Cout, k, stride, residual tensor, channel
+//                                                       offsets and, for a convolution, the tile form conv_form() gives the device at this batch
 #include <algorithm>
 #include <chrono>
 #include <cstdio>
@@ -91,6 +93,26 @@ int main(int argc, char** argv) {
         std::printf("host_walk_ms %.3f\n", ms[ms.size() / 2]);
         return 0;
     }
-    std::fprintf(stderr, "usage: detnet_walk fma|check|run|bench ... (see the head of tools/detnet_walk.cpp)\n");
+    if (cmd == "forms" && argc == 5) {
+        const int S = std::atoi(argv[3]), batch = std::atoi(argv[4]);
+        std::vector<char> file;
+        Net net;
+        if (batch < 1) { std::printf("refused: batch = %d\n", batch); return 0; }
+        if (!load_model(argv[2], S, file, net)) return 0;
+        std::printf("ok ops %zu\n", net.ops.size());
+        static const char* const kinds[] = {"focus", "conv", "maxpool", "upsample2"};
+        for (size_t i = 0; i < net.ops.size(); i++) {
+            const OpRec& r = net.ops[i].r;
+            const Tensor &Ts = net.tensors[r.src], &Td = net.tensors[r.dst];
+            const bool head = Td.kind == HEAD;
+            const long long M = (long long)batch * (head ? Ts.H : Td.H) * (head ? Ts.W : Td.W);
+            std::printf("op %zu kind %s M %lld Cout %u k %u stride %u res %d src_c0 %u dst_c0 %u head %d", i, kinds[r.kind], M, r.dst_c, r.k, r.stride, r.res, r.src_c0,
+                        r.dst_c0, head ? 1 : 0);
+            if (r.kind == CONV) std::printf(" form %s", conv_form_name(conv_form(M, (int)r.dst_c)));
+            std::printf("\n");
+        }
+        return 0;
+    }
+    std::fprintf(stderr, "usage: detnet_walk fma|check|run|bench|forms ... (see the head of tools/detnet_walk.cpp)\n");
     return 2;
 }
