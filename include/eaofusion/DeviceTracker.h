@@ -24,7 +24,7 @@
 #include <unordered_map>
 #include <vector>
 
-#include "../eao_fusion.h"
+#include "adapter_detail.h"
 #include "Frame.h"
 #include "OptimizerImpl.h"      // collect_planes / store_planes: the frame's associated map planes as PoseOptimization's adapter reads them
 
@@ -77,8 +77,8 @@ public:
             if (p) index_.emplace((void*)p, (int)i);          // (a point listed twice keeps its first slot, like upstream's first visit)
             active[i] = (p && !p->isBad()) ? 1 : 0;
             if (!active[i]) continue;
-            const cv::Mat P = p->GetWorldPos(), Pn = p->GetNormal(), D = p->GetDescriptor();
-            for (int a = 0; a < 3; a++) { Xw[3 * i + a] = P.template at<float>(a); nrm[3 * i + a] = Pn.template at<float>(a); }
+            detail::read3(p->GetWorldPos(), &Xw[3 * i]); detail::read3(p->GetNormal(), &nrm[3 * i]);
+            const cv::Mat D = p->GetDescriptor();
             dmin[i] = p->GetMinDistanceInvariance(); dmax[i] = p->GetMaxDistanceInvariance(); draw[i] = detail::MaxDistanceOf<MapPointT>::get(p);
             std::memcpy(&desc[32 * i], D.template ptr<unsigned char>(0), 32);
         }
@@ -120,12 +120,10 @@ public:
             if (it != index_.end()) { prior[k] = it->second; continue; }
             prior[k] = -2;
             if (priorXw.empty()) priorXw.assign(3 * (size_t)cap_, 0.f);
-            const cv::Mat P = pMP->GetWorldPos();
-            for (int a = 0; a < 3; a++) priorXw[3 * (size_t)k + a] = P.template at<float>(a);
+            detail::read3(pMP->GetWorldPos(), &priorXw[3 * (size_t)k]);
         }
         float T[16];
-        for (int r = 0; r < 4; r++)
-            for (int c = 0; c < 4; c++) T[4 * r + c] = F.mTcw.template at<float>(r, c);
+        detail::read44(F.mTcw, T);
         eao_track_result R = {};      // (zero first: a member this header does not set reads as "not wanted", include/eao_fusion.h EAO_ABI_VERSION)
         R.kp_map_point = kpMp.data(); R.kp_outlier = outl.data(); R.kp_u_right = ur.data(); R.kp_depth = dz.data(); R.map_in_view = inView.data();
         PlaneEdges pe;
@@ -146,10 +144,7 @@ public:
             if (kpMp[k] >= 0 && !F.mvpMapPoints[k]) F.mvpMapPoints[k] = static_cast<MapPointT*>(map_[kpMp[k]]);
             F.mvbOutlier[k] = outl[k] != 0;
         }
-        cv::Mat pose(4, 4, CV_32F);
-        for (int r = 0; r < 4; r++)
-            for (int c = 0; c < 4; c++) pose.template at<float>(r, c) = R.Tcw[4 * r + c];
-        F.SetPose(pose);
+        F.SetPose(detail::mat_of(R.Tcw, 4, 4));
         if (R.n_edges >= 3) store_planes(&F, pe, pout);      // mvbPlaneOutlier (upstream resets / sets them behind the "< 3 correspondences" test only)
         return R.n_inliers;
     }
@@ -181,13 +176,12 @@ public:
             oct[i] = Last.mvKeys[i].octave; ang[i] = Last.mvKeysUn[i].angle;
             if (!pMP || Last.mvbOutlier[i]) continue;
             valid[i] = 1;
-            const cv::Mat P = pMP->GetWorldPos(), D = pMP->GetDescriptor();
-            for (int a = 0; a < 3; a++) Xw[3 * i + a] = P.template at<float>(a);
+            detail::read3(pMP->GetWorldPos(), &Xw[3 * i]);
+            const cv::Mat D = pMP->GetDescriptor();
             std::memcpy(&desc[32 * i], D.template ptr<unsigned char>(0), 32);
         }
         float Tc[16], Tl[16];
-        for (int r = 0; r < 4; r++)
-            for (int c = 0; c < 4; c++) { Tc[4 * r + c] = Cur.mTcw.template at<float>(r, c); Tl[4 * r + c] = Last.mTcw.template at<float>(r, c); }
+        detail::read44(Cur.mTcw, Tc); detail::read44(Last.mTcw, Tl);
         std::vector<int32_t> kpMp(cap_, -1);
         std::vector<uint8_t> outl(cap_, 0);
         std::vector<float> ur(cap_), dz(cap_);
@@ -206,10 +200,7 @@ public:
             if (nmatchesMap) *nmatchesMap = 0;
             return R.n_matches;
         }
-        cv::Mat pose(4, 4, CV_32F);
-        for (int r = 0; r < 4; r++)
-            for (int c = 0; c < 4; c++) pose.template at<float>(r, c) = R.Tcw[4 * r + c];
-        Cur.SetPose(pose);
+        Cur.SetPose(detail::mat_of(R.Tcw, 4, 4));
         if (R.n_edges >= 3) store_planes(&Cur, pe, pout);
         int nmatches = R.n_matches, nMap = 0;
         for (int k = 0; k < R.n_keypoints; k++) {      // "Discard outliers", src/Tracking.cc:2188-2207
@@ -252,14 +243,12 @@ public:
             MapPointT* pMP = vpKF[i];
             if (!pMP || pMP->isBad()) continue;
             valid[i] = 1;
-            const cv::Mat P = pMP->GetWorldPos();
-            for (int a = 0; a < 3; a++) Xw[3 * i + a] = P.template at<float>(a);
+            detail::read3(pMP->GetWorldPos(), &Xw[3 * i]);
         }
-        FeatVec fk, fc;
-        const eao_feature_vector fvK = flatten(pRefKF->mFeatVec, fk), fvC = flatten(Cur.mFeatVec, fc);
+        detail::FeatVecArrays fk, fc;
+        const eao_feature_vector fvK = detail::flatten(pRefKF->mFeatVec, fk), fvC = detail::flatten(Cur.mFeatVec, fc);
         float Tl[16];
-        for (int r = 0; r < 4; r++)
-            for (int c = 0; c < 4; c++) Tl[4 * r + c] = lastTcw.template at<float>(r, c);
+        detail::read44(lastTcw, Tl);
         std::vector<int32_t> kpMp(cap_, -1);
         std::vector<uint8_t> outl(cap_, 0);
         std::vector<float> ur(cap_), dz(cap_);
@@ -275,10 +264,7 @@ public:
         Cur.mvuRight.assign(ur.begin(), ur.begin() + R.n_keypoints);
         Cur.mvDepth.assign(dz.begin(), dz.begin() + R.n_keypoints);
         if (R.n_matches < minMatches) return 0;      // "if (nmatches < 10) return false" (:1580-1581): nothing optimised, nothing touched
-        cv::Mat pose(4, 4, CV_32F);
-        for (int r = 0; r < 4; r++)
-            for (int c = 0; c < 4; c++) pose.template at<float>(r, c) = R.Tcw[4 * r + c];
-        Cur.SetPose(pose);
+        Cur.SetPose(detail::mat_of(R.Tcw, 4, 4));
         if (R.n_edges >= 3) store_planes(&Cur, pe, pout);
         int nMap = 0;
         for (int k = 0; k < R.n_keypoints; k++) {      // "Discard outliers", src/Tracking.cc:1593-1612
@@ -312,19 +298,6 @@ private:
         O.min_matches = minMatches; O.n_planes = M;
         O.plane_world = M ? pe.world.data() : nullptr; O.plane_obs = M ? pe.obs.data() : nullptr; O.plane_seen = M ? pe.seen.data() : nullptr; O.plane_outlier = pout.data();
         detail::check(eao_tracker_set_options(h_, &O), "eao_tracker_set_options");
-    }
-    struct FeatVec { std::vector<uint32_t> id, index; std::vector<int32_t> start; };
-    template <class FeatVecT>
-    static eao_feature_vector flatten(const FeatVecT& fv, FeatVec& a) {      // DBoW2::FeatureVector = std::map<node id, std::vector<keypoint index>>
-        a.id.clear(); a.index.clear(); a.start.assign(1, 0);
-        for (typename FeatVecT::const_iterator it = fv.begin(); it != fv.end(); ++it) {
-            a.id.push_back((uint32_t)it->first);
-            for (size_t k = 0; k < it->second.size(); k++) a.index.push_back((uint32_t)it->second[k]);
-            a.start.push_back((int32_t)a.index.size());
-        }
-        eao_feature_vector f;
-        f.n_nodes = (int32_t)a.id.size(); f.node_id = a.id.data(); f.node_start = a.start.data(); f.index = a.index.data();
-        return f;
     }
     eao_tracker* h_ = nullptr;
     int cap_, capMp_;

@@ -20,8 +20,7 @@
 #include <utility>
 #include <vector>
 
-#include "../eao_fusion.h"
-#include "cv_compat.h"
+#include "adapter_detail.h"
 
 namespace eaofusion {
 namespace detail {
@@ -33,9 +32,6 @@ template <class MapPointT>
 struct MaxDistanceOf : MapPointT {
     static float get(MapPointT* p) { return p->*(&MaxDistanceOf::mfMaxDistance); }
 };
-inline void check(eao_status st, const char* what) {
-    if (st != EAO_OK) throw std::runtime_error(std::string(what) + ": " + eao_last_error());
-}
 // mDistCoef of the frame as the C-ABI takes it (k1, k2, p1, p2[, k3]: src/Tracking.cc:90-101); a Frame class without the member (a stand-in) is distortion-free.
 template <class FrameT, class = void>
 struct DistCoefOf { static int get(const FrameT&, float*) { return 0; } };
@@ -89,18 +85,16 @@ int IsInFrustum(FrameT& F, const std::vector<MapPointT*>& vpMPs, float viewingCo
     std::vector<float> Xw(3 * (size_t)n), nrm(3 * (size_t)n), dmin(n), dmax(n), draw(n);
     for (int k = 0; k < n; k++) {
         MapPointT* p = vpMPs[idx[k]];
-        const cv::Mat P = p->GetWorldPos(), Pn = p->GetNormal();
-        for (int a = 0; a < 3; a++) { Xw[3 * (size_t)k + a] = P.template at<float>(a); nrm[3 * (size_t)k + a] = Pn.template at<float>(a); }
+        detail::read3(p->GetWorldPos(), &Xw[3 * (size_t)k]); detail::read3(p->GetNormal(), &nrm[3 * (size_t)k]);
         dmin[k] = p->GetMinDistanceInvariance(); dmax[k] = p->GetMaxDistanceInvariance(); draw[k] = detail::MaxDistanceOf<MapPointT>::get(p);
     }
     eao_frustum_frame fr;
     // upstream's isInFrustum reads the private mRcw / mtcw / mOw; they are copies of blocks of the public mTcw
     // (Frame::UpdatePoseMatrices, src/Frame.cc:624-636) and mOw is what the public GetCameraCenter() returns
-    const cv::Mat Ow = F.GetCameraCenter();
-    for (int r = 0; r < 3; r++) {
+    detail::read3(F.GetCameraCenter(), fr.Ow);
+    for (int r = 0; r < 3; r++) {      // (the last row is written, not read)
         for (int c = 0; c < 4; c++) fr.Tcw[4 * r + c] = F.mTcw.template at<float>(r, c);
         fr.Tcw[12 + r] = 0.f;
-        fr.Ow[r] = Ow.template at<float>(r);
     }
     fr.Tcw[15] = 1.f;
     fr.fx = FrameT::fx; fr.fy = FrameT::fy; fr.cx = FrameT::cx; fr.cy = FrameT::cy; fr.mbf = F.mbf;

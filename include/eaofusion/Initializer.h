@@ -23,8 +23,7 @@
 #include <utility>
 #include <vector>
 
-#include "../eao_fusion.h"
-#include "cv_compat.h"
+#include "adapter_detail.h"
 
 namespace eaofusion {
 
@@ -73,7 +72,7 @@ public:
         RandomT::SeedRandOnce(0);
         for (int it = 0; it < mMaxIterations; it++) {
             vAvailableIndices = vAllIndices;
-            // Select a minimum set
+            // Select a minimum set (the drawn POSITION is overwritten and popped: no repeats -- not the draw of PnPsolver / Sim3Solver, detail::draw_sets)
             for (size_t j = 0; j < 8; j++) {
                 int randi = RandomT::RandomInt(0, (int)vAvailableIndices.size() - 1);
                 int idx = (int)vAvailableIndices[randi];
@@ -94,7 +93,9 @@ public:
         p.n1 = (int32_t)mvKeys1.size(); p.n2 = (int32_t)mvKeys2.size();
         p.keys1_xy = k1.data(); p.keys2_xy = k2.data();
         p.n_matches = N; p.matches12 = m12.data();
-        p.fx = mK.template at<float>(0, 0); p.fy = mK.template at<float>(1, 1); p.cx = mK.template at<float>(0, 2); p.cy = mK.template at<float>(1, 2);
+        float K[4];
+        detail::read_intrinsics(mK, K);
+        p.fx = K[0]; p.fy = K[1]; p.cx = K[2]; p.cy = K[3];
         p.sigma = mSigma;
         p.min_parallax = kInitializerMinParallax;
         p.min_triangulated = kInitializerMinTriangulated;
@@ -103,21 +104,15 @@ public:
         eao_initializer_result r = eao_initializer_result();
         r.p3d = p3d.data();
         r.triangulated = tri.data();
-        const eao_status st = eao_initializer_initialize(&p, sets.data(), mMaxIterations, &r);
-        if (st != EAO_OK) throw std::runtime_error(std::string("eao_initializer_initialize: ") + eao_last_error());
+        detail::check(eao_initializer_initialize(&p, sets.data(), mMaxIterations, &r), "eao_initializer_initialize");
         mResult = r;
         mResult.p3d = nullptr;
         mResult.triangulated = nullptr;
         if (r.no_model) return false;                                          // (upstream throws here)
         if (r.branch == EAO_INIT_BRANCH_F) { R21 = cv::Mat(); t21 = cv::Mat(); }     // ReconstructF :501-502; ReconstructH leaves them alone unless it returns true
         if (!r.returned) return false;
-        cv::Mat R(3, 3, CV_32F), t(3, 1, CV_32F);
-        for (int i = 0; i < 3; i++) {
-            for (int j = 0; j < 3; j++) R.template at<float>(i, j) = r.R21[3 * i + j];
-            t.template at<float>(i, 0) = r.t21[i];
-        }
-        R.copyTo(R21);
-        t.copyTo(t21);
+        detail::mat_of(r.R21, 3, 3).copyTo(R21);
+        detail::mat_of(r.t21, 3, 1).copyTo(t21);
         vP3D.resize(mvKeys1.size());
         vbTriangulated = std::vector<bool>(mvKeys1.size(), false);
         for (size_t i = 0; i < mvKeys1.size(); i++) {

@@ -25,7 +25,7 @@
 #include <string>
 #include <vector>
 
-#include "../eao_fusion.h"
+#include "adapter_detail.h"
 
 namespace eaofusion {
 
@@ -33,7 +33,7 @@ template <class KeyFrameT, class FrameT, class VocabularyT>
 class KeyFrameDatabaseT {
 public:
     explicit KeyFrameDatabaseT(const VocabularyT& voc) : mpVoc(&voc) {      // :33-37
-        check(eao_keyframe_db_create((int32_t)voc.size(), &mHandle), "eao_keyframe_db_create");
+        detail::check(eao_keyframe_db_create((int32_t)voc.size(), &mHandle), "eao_keyframe_db_create");
     }
     ~KeyFrameDatabaseT() {
         if (mHandle) eao_keyframe_db_destroy(mHandle);
@@ -46,7 +46,7 @@ public:
         std::vector<uint32_t> id;
         std::vector<double> val;
         pack(pKF->mBowVec, id, val);
-        check(eao_keyframe_db_add(mHandle, (uint64_t)pKF->mnId, (int32_t)id.size(), id.data(), val.data()), "eao_keyframe_db_add");
+        detail::check(eao_keyframe_db_add(mHandle, (uint64_t)pKF->mnId, (int32_t)id.size(), id.data(), val.data()), "eao_keyframe_db_add");
         mKeyFrames[(uint64_t)pKF->mnId] = pKF;
     }
 
@@ -54,13 +54,13 @@ public:
         std::unique_lock<std::mutex> lock(mMutex);
         auto it = mKeyFrames.find((uint64_t)pKF->mnId);
         if (it == mKeyFrames.end() || it->second != pKF) return;
-        check(eao_keyframe_db_erase(mHandle, (uint64_t)pKF->mnId), "eao_keyframe_db_erase");
+        detail::check(eao_keyframe_db_erase(mHandle, (uint64_t)pKF->mnId), "eao_keyframe_db_erase");
         mKeyFrames.erase(it);
     }
 
     void clear() {      // :68-72
         std::unique_lock<std::mutex> lock(mMutex);
-        check(eao_keyframe_db_clear(mHandle), "eao_keyframe_db_clear");
+        detail::check(eao_keyframe_db_clear(mHandle), "eao_keyframe_db_clear");
         mKeyFrames.clear();
     }
 
@@ -75,10 +75,6 @@ public:
     }
 
 private:
-    static void check(eao_status st, const char* what) {
-        if (st != EAO_OK) throw std::runtime_error(std::string(what) + ": " + eao_last_error());
-    }
-
     template <class BowVectorT>
     static void pack(const BowVectorT& v, std::vector<uint32_t>& id, std::vector<double>& val) {
         id.reserve(v.size());
@@ -113,7 +109,7 @@ private:
         s.sharing_words = sharingWords.data();
         s.scored_id = scoredId.data();
         s.scored_score = scoredScore.data();
-        check(eao_keyframe_db_query_scores(mHandle, &q, cap, &s), "eao_keyframe_db_query_scores");
+        detail::check(eao_keyframe_db_query_scores(mHandle, &q, cap, &s), "eao_keyframe_db_query_scores");
         if (s.n_scored == 0) return std::vector<KeyFrameT*>();      // :106, :140 / :223, :254
         // GetBestCovisibilityKeyFrames(10) of every scored keyframe (:150, :264) as a CSR over ids; a neighbour need not be held by the database
         std::map<uint64_t, KeyFrameT*> seen;
@@ -130,9 +126,9 @@ private:
         }
         std::vector<uint64_t> candId((size_t)s.n_scored);
         int32_t nCand = 0, usedUnset = 0;
-        check(eao_keyframe_db_candidates(mHandle, kind, queryId, s.min_common_words, minScore, s.n_scored, scoredId.data(), scoredScore.data(), nbStart.data(),
-                                         nbId.data(), candId.data(), &nCand, nullptr, nullptr, &usedUnset),
-              "eao_keyframe_db_candidates");
+        detail::check(eao_keyframe_db_candidates(mHandle, kind, queryId, s.min_common_words, minScore, s.n_scored, scoredId.data(), scoredScore.data(), nbStart.data(),
+                                                 nbId.data(), candId.data(), &nCand, nullptr, nullptr, &usedUnset),
+                      "eao_keyframe_db_candidates");
         std::vector<KeyFrameT*> out;
         out.reserve((size_t)nCand);
         for (int32_t i = 0; i < nCand; i++) out.push_back(seen.at(candId[i]));

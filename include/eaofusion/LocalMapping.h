@@ -18,6 +18,7 @@
 #include <vector>
 
 #include "ORBmatcher.h"
+#include "adapter_detail.h"
 
 namespace eaofusion {
 
@@ -63,8 +64,8 @@ public:
         }
         std::vector<int32_t> verdict(nb * (size_t)v1.n, 0);
         std::vector<float> x3d(3 * nb * (size_t)v1.n, 0.f);
-        check(eao_triangulate_matches_batch(&v1, &c1, da1.depth.data(), da1.rx.data(), da1.ry.data(), (int)nb, pv.data(), c2.data(), dp.data(), rx.data(), ry.data(),
-                                            m12.data(), RATIO_FACTOR_BASE * pKF1->mfScaleFactor, verdict.data(), x3d.data()), "eao_triangulate_matches_batch");
+        detail::check(eao_triangulate_matches_batch(&v1, &c1, da1.depth.data(), da1.rx.data(), da1.ry.data(), (int)nb, pv.data(), c2.data(), dp.data(), rx.data(), ry.data(),
+                                                    m12.data(), RATIO_FACTOR_BASE * pKF1->mfScaleFactor, verdict.data(), x3d.data()), "eao_triangulate_matches_batch");
         return accepted(nb, v1.n, m12, verdict, x3d);
     }
 
@@ -84,23 +85,15 @@ public:
         const cv::Mat Cw = pKF1->GetCameraCenter();
         for (size_t q = 0; q < nb; q++) {
             KeyFrameT* pKF2 = vpNeighKFs[q];
-            const cv::Mat R2w = pKF2->GetRotation(), t2w = pKF2->GetTranslation();      // the epipole in the second image, as in the single call (src/ORBmatcher.cc:663-670)
-            float C2[3];
-            for (int r = 0; r < 3; r++) {
-                double acc = 0;
-                for (int k = 0; k < 3; k++) acc += (double)R2w.template at<float>(r, k) * (double)Cw.template at<float>(k);
-                C2[r] = (float)(acc + (double)t2w.template at<float>(r));
-            }
-            const float invz = 1.0f / C2[2];
-            ex[q] = pKF2->fx * C2[0] * invz + pKF2->cx; ey[q] = pKF2->fy * C2[1] * invz + pKF2->cy;
-            for (int r = 0; r < 3; r++) for (int c = 0; c < 3; c++) Fm[9 * q + r * 3 + c] = vF12[q].template at<float>(r, c);
+            detail::epipole(Cw, pKF2->GetRotation(), pKF2->GetTranslation(), pKF2->fx, pKF2->fy, pKF2->cx, pKF2->cy, ex[q], ey[q]);      // as in the single call (src/ORBmatcher.cc:663-670)
+            detail::read33(vF12[q], &Fm[9 * q]);
             c2[q] = camera_of(*pKF2);
         }
         const int n1 = eao_keyframe_size(h1);
         std::vector<int32_t> m12(nb * (size_t)n1, -1), nm(nb, 0), verdict(nb * (size_t)n1, 0);
         std::vector<float> x3d(3 * nb * (size_t)n1, 0.f);
-        check(eao_kf_create_new_map_points(h1, &c1, (int)nb, h2s.data(), c2.data(), Fm.data(), ex.data(), ey.data(), bOnlyStereo ? 1 : 0, mbCheckOrientation ? 1 : 0,
-                                           RATIO_FACTOR_BASE * pKF1->mfScaleFactor, m12.data(), nm.data(), verdict.data(), x3d.data()), "eao_kf_create_new_map_points");
+        detail::check(eao_kf_create_new_map_points(h1, &c1, (int)nb, h2s.data(), c2.data(), Fm.data(), ex.data(), ey.data(), bOnlyStereo ? 1 : 0, mbCheckOrientation ? 1 : 0,
+                                                   RATIO_FACTOR_BASE * pKF1->mfScaleFactor, m12.data(), nm.data(), verdict.data(), x3d.data()), "eao_kf_create_new_map_points");
         if (vvMatchedPairs)
             for (size_t q = 0; q < nb; q++) {
                 (*vvMatchedPairs)[q].reserve(nm[q]);
@@ -114,7 +107,7 @@ public:
     static eao_tri_camera camera_of(KeyFrameT& K) {
         eao_tri_camera c;
         const cv::Mat R = K.GetRotation(), t = K.GetTranslation(), O = K.GetCameraCenter();
-        for (int r = 0; r < 3; r++) { for (int k = 0; k < 3; k++) c.Rcw[r * 3 + k] = R.template at<float>(r, k); c.tcw[r] = t.template at<float>(r); c.Ow[r] = O.template at<float>(r); }
+        detail::read33(R, c.Rcw); detail::read3(t, c.tcw); detail::read3(O, c.Ow);
         c.fx = K.fx; c.fy = K.fy; c.cx = K.cx; c.cy = K.cy; c.invfx = K.invfx; c.invfy = K.invfy; c.mb = K.mb; c.mbf = K.mbf;
         return c;
     }
@@ -140,8 +133,7 @@ private:
                 served[i] = 1;
                 NewMapPoint p;
                 p.idx1 = (size_t)i; p.idx2 = (size_t)m12[q * n1 + i]; p.verdict = v;
-                p.x3D = cv::Mat(3, 1, CV_32F);
-                for (int k = 0; k < 3; k++) p.x3D.at<float>(k) = x3d[3 * (q * n1 + i) + k];
+                p.x3D = detail::mat_of(&x3d[3 * (q * n1 + i)], 3, 1);
                 out[q].push_back(p);
             }
         return out;

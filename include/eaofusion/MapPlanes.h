@@ -28,8 +28,7 @@
 #include <string>
 #include <vector>
 
-#include "../eao_fusion.h"
-#include "cv_compat.h"
+#include "adapter_detail.h"
 
 namespace eaofusion {
 
@@ -39,7 +38,7 @@ public:
     float mfDisTh = EAO_PLANE_MAP_DIS_TH;        // Map::Map, src/Map.cc:22
     float mfAngleTh = EAO_PLANE_MAP_ANGLE_TH;    // :23
 
-    MapPlanesT() { check(eao_plane_map_create(&mHandle), "eao_plane_map_create"); }
+    MapPlanesT() { detail::check(eao_plane_map_create(&mHandle), "eao_plane_map_create"); }
     ~MapPlanesT() {
         if (mHandle) eao_plane_map_destroy(mHandle);
     }
@@ -52,33 +51,33 @@ public:
         std::vector<float> xyz;
         pack(pRefKF->mvBoundaryPoints[idx], xyz);
         float w[4], T[16];
-        vec4(pMP->GetWorldPos(), w);
-        mat4(pRefKF->GetPose(), T);
-        check(eao_plane_map_add(mHandle, (uint64_t)pMP->mnId, w, (int32_t)(xyz.size() / 3), xyz.data(), T), "eao_plane_map_add");
+        detail::read4(pMP->GetWorldPos(), w);
+        detail::read44(pRefKF->GetPose(), T);
+        detail::check(eao_plane_map_add(mHandle, (uint64_t)pMP->mnId, w, (int32_t)(xyz.size() / 3), xyz.data(), T), "eao_plane_map_add");
     }
     void BoundaryUpdated(MapPlaneT* pMP, const FrameT& pF, int id) {      // src/MapPlane.cc:150-153
         std::vector<float> xyz;
         pack(pF.mvBoundaryPoints[id], xyz);
         float T[16];
-        mat4(pF.mTcw, T);
-        check(eao_plane_map_update_boundary(mHandle, (uint64_t)pMP->mnId, (int32_t)(xyz.size() / 3), xyz.data(), T), "eao_plane_map_update_boundary");
+        detail::read44(pF.mTcw, T);
+        detail::check(eao_plane_map_update_boundary(mHandle, (uint64_t)pMP->mnId, (int32_t)(xyz.size() / 3), xyz.data(), T), "eao_plane_map_update_boundary");
     }
     void WorldPosSet(MapPlaneT* pMP) {      // src/MapPlane.cc:137-142
         float w[4];
-        vec4(pMP->GetWorldPos(), w);
-        check(eao_plane_map_set_world_pos(mHandle, (uint64_t)pMP->mnId, w), "eao_plane_map_set_world_pos");
+        detail::read4(pMP->GetWorldPos(), w);
+        detail::check(eao_plane_map_set_world_pos(mHandle, (uint64_t)pMP->mnId, w), "eao_plane_map_set_world_pos");
     }
-    void Erased(MapPlaneT* pMP) { check(eao_plane_map_erase(mHandle, (uint64_t)pMP->mnId), "eao_plane_map_erase"); }      // src/Map.cc:147-153
-    void Cleared() { check(eao_plane_map_clear(mHandle), "eao_plane_map_clear"); }                                         // src/Map.cc:131-133
+    void Erased(MapPlaneT* pMP) { detail::check(eao_plane_map_erase(mHandle, (uint64_t)pMP->mnId), "eao_plane_map_erase"); }      // src/Map.cc:147-153
+    void Cleared() { detail::check(eao_plane_map_clear(mHandle), "eao_plane_map_clear"); }                                         // src/Map.cc:131-133
 
-    // ---------------------------------------------------------------------------------------- Map::AssociatePlanesByBoundary, src/Map.cc:155-215
-    template <class MapT>
-    void AssociatePlanesByBoundary(MapT& map, FrameT& pF, bool /*out*/ = false) {
-        pF.mbNewPlane = false;      // :160
+            // ---------------------------------------------------------------------------------------- Map::AssociatePlanesByBoundary, src/Map.cc:155-215
+            template <class MapT>
+            void AssociatePlanesByBoundary(MapT& map, FrameT& pF, bool /*out*/ = false) {
+                pF.mbNewPlane = false;      // :160
         std::vector<MapPlaneT*> cand(map.mspMapPlanes.begin(), map.mspMapPlanes.end());      // the std::set's order, :175
         std::vector<int32_t> match;
         float M[16];
-        mat4(pF.mTcw, M);
+        detail::read44(pF.mTcw, M);
         const int32_t start[2] = {0, pF.mnPlaneNum};
         associate(1, M, start, pF.mvPlaneCoefficients, cand, match);
         for (int i = 0; i < pF.mnPlaneNum; ++i)
@@ -92,7 +91,7 @@ public:
         vpMatched = std::vector<MapPlaneT*>(pKF->mnPlaneNum, static_cast<MapPlaneT*>(nullptr));      // :253
         std::vector<int32_t> match;
         float M[16];
-        mat4(Scw, M);
+        detail::read44(Scw, M);
         const int32_t start[2] = {0, pKF->mnPlaneNum};
         associate(1, M, start, pKF->mvPlaneCoefficients, vpPlanes, match);
         for (int i = 0; i < pKF->mnPlaneNum; ++i)
@@ -110,7 +109,7 @@ public:
         std::vector<int32_t> start(1, 0);
         std::vector<cv::Mat> coef;
         for (int k = 0; k < n; k++) {
-            mat4(vScw[k], &M[16 * (size_t)k]);
+            detail::read44(vScw[k], &M[16 * (size_t)k]);
             for (int i = 0; i < vpKFs[k]->mnPlaneNum; ++i) coef.push_back(vpKFs[k]->mvPlaneCoefficients[i]);
             start.push_back((int32_t)coef.size());
         }
@@ -125,16 +124,6 @@ public:
     }
 
 private:
-    static void check(eao_status st, const char* what) {
-        if (st != EAO_OK) throw std::runtime_error(std::string(what) + ": " + eao_last_error());
-    }
-    static void vec4(const cv::Mat& m, float out[4]) {
-        for (int i = 0; i < 4; i++) out[i] = m.at<float>(i, 0);
-    }
-    static void mat4(const cv::Mat& m, float out[16]) {
-        for (int i = 0; i < 4; i++)
-            for (int j = 0; j < 4; j++) out[i * 4 + j] = m.at<float>(i, j);
-    }
     template <class CloudT>
     static void pack(const CloudT& cloud, std::vector<float>& xyz) {
         xyz.clear();
@@ -150,15 +139,15 @@ private:
                    std::vector<int32_t>& match) {
         const int32_t rows = start[nSets];
         std::vector<float> coef((size_t)rows * 4);
-        for (int32_t i = 0; i < rows; i++) vec4(coefficients[i], &coef[4 * (size_t)i]);
+        for (int32_t i = 0; i < rows; i++) detail::read4(coefficients[i], &coef[4 * (size_t)i]);
         std::vector<uint64_t> ids;
         ids.reserve(cand.size());
         for (MapPlaneT* p : cand) ids.push_back((uint64_t)p->mnId);
         match.assign((size_t)rows, -1);
         std::vector<float> dis((size_t)rows);
-        check(eao_plane_map_associate(mHandle, nSets, M, start, coef.data(), (int32_t)ids.size(), ids.data(), mfDisTh, mfAngleTh, match.data(), dis.data(), nullptr,
-                                      nullptr, nullptr),
-              "eao_plane_map_associate");
+        detail::check(eao_plane_map_associate(mHandle, nSets, M, start, coef.data(), (int32_t)ids.size(), ids.data(), mfDisTh, mfAngleTh, match.data(), dis.data(), nullptr,
+                                              nullptr, nullptr),
+                      "eao_plane_map_associate");
     }
 
     eao_plane_map* mHandle = nullptr;

@@ -33,8 +33,7 @@
 #include <string>
 #include <vector>
 
-#include "../eao_fusion.h"
-#include "cv_compat.h"
+#include "adapter_detail.h"
 
 namespace eaofusion {
 
@@ -134,8 +133,7 @@ public:
         r.node_id = nodeId.data();
         r.node_start = nodeStart.data();
         r.index = index.data();
-        const eao_status st = eao_vocabulary_transform(mHandle, desc.data(), n, levelsup, &r);
-        if (st != EAO_OK) throw std::runtime_error(std::string("eao_vocabulary_transform: ") + eao_last_error());
+        detail::check(eao_vocabulary_transform(mHandle, desc.data(), n, levelsup, &r), "eao_vocabulary_transform");
         for (int k = 0; k < r.n_words; k++) v.insert(v.end(), typename BowVectorT::value_type(wordId[k], wordValue[k]));
         for (int k = 0; k < r.n_fv_nodes; k++) {
             auto it = fv.insert(fv.end(), typename FeatureVectorT::value_type(nodeId[k], typename FeatureVectorT::mapped_type()));
@@ -182,8 +180,7 @@ public:
             start[j + 1] = (int32_t)dId.size();
         }
         std::vector<double> out(stored.size());
-        const eao_status st = eao_bow_score_l1((int32_t)qId.size(), qId.data(), qVal.data(), (int32_t)stored.size(), start.data(), dId.data(), dVal.data(), out.data());
-        if (st != EAO_OK) throw std::runtime_error(std::string("eao_bow_score_l1: ") + eao_last_error());
+        detail::check(eao_bow_score_l1((int32_t)qId.size(), qId.data(), qVal.data(), (int32_t)stored.size(), start.data(), dId.data(), dVal.data(), out.data()), "eao_bow_score_l1");
         return out;
     }
 

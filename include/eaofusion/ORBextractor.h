@@ -18,8 +18,7 @@
 #include <string>
 #include <vector>
 
-#include "../eao_fusion.h"
-#include "cv_compat.h"
+#include "adapter_detail.h"
 
 namespace ORB_SLAM2 {
 
@@ -30,12 +29,12 @@ public:
     ORBextractor(int nfeatures_, float scaleFactor_, int nlevels_, int iniThFAST_, int minThFAST_)
         : nfeatures(nfeatures_), scaleFactor(scaleFactor_), nlevels(nlevels_), iniThFAST(iniThFAST_), minThFAST(minThFAST_) {
         eao_orb_cfg cfg = {nfeatures_, scaleFactor_, nlevels_, iniThFAST_, minThFAST_};
-        check(eao_orb_create(&cfg, &h_), "eao_orb_create");
+        eaofusion::detail::check(eao_orb_create(&cfg, &h_), "eao_orb_create");
         mvScaleFactor.resize(nlevels); mvInvScaleFactor.resize(nlevels);
         mvLevelSigma2.resize(nlevels); mvInvLevelSigma2.resize(nlevels);
         mnFeaturesPerLevel.resize(nlevels);
-        check(eao_orb_tables(h_, mvScaleFactor.data(), mvInvScaleFactor.data(), mvLevelSigma2.data(), mvInvLevelSigma2.data(),
-                             mnFeaturesPerLevel.data()), "eao_orb_tables");
+        eaofusion::detail::check(eao_orb_tables(h_, mvScaleFactor.data(), mvInvScaleFactor.data(), mvLevelSigma2.data(), mvInvLevelSigma2.data(),
+                                                mnFeaturesPerLevel.data()), "eao_orb_tables");
         mvImagePyramid.resize(nlevels);
     }
     ~ORBextractor() { eao_orb_destroy(h_); }
@@ -50,13 +49,13 @@ public:
         assert(image.type() == CV_8UC1);
         static_assert(sizeof(cv::KeyPoint) == sizeof(eao_keypoint), "cv::KeyPoint must be the 28-byte POD the ABI mirrors");
         if (keepPyramid != keptPyramid_) {
-            check(eao_orb_set_keep_pyramid(h_, keepPyramid ? 19 : -1), "eao_orb_set_keep_pyramid");      // EDGE_THRESHOLD, src/ORBextractor.cc:67
+            eaofusion::detail::check(eao_orb_set_keep_pyramid(h_, keepPyramid ? 19 : -1), "eao_orb_set_keep_pyramid");      // EDGE_THRESHOLD, src/ORBextractor.cc:67
             keptPyramid_ = keepPyramid;
         }
         const eao_keypoint* kp = nullptr;
         const uint8_t* desc = nullptr;
         int n = 0;
-        check(eao_orb_extract_ref(h_, image.ptr(0), image.cols, image.rows, (int)image.step, &kp, &desc, &n), "eao_orb_extract_ref");
+        eaofusion::detail::check(eao_orb_extract_ref(h_, image.ptr(0), image.cols, image.rows, (int)image.step, &kp, &desc, &n), "eao_orb_extract_ref");
         keypoints.resize((size_t)n);
         if (n == 0) {
             descriptors_.release();
@@ -80,7 +79,7 @@ public:
     std::vector<cv::Mat>& ImagePyramid() {
         if (pyramidStale_) {
             eao_orb_level_view lv[16];
-            check(eao_orb_pyramid(h_, 0, 19, lv), "eao_orb_pyramid");
+            eaofusion::detail::check(eao_orb_pyramid(h_, 0, 19, lv), "eao_orb_pyramid");
             for (int l = 0; l < nlevels; l++) mvImagePyramid[l] = cv::Mat(lv[l].height, lv[l].width, CV_8UC1, lv[l].data, (size_t)lv[l].step);
             pyramidStale_ = false;
         }
@@ -103,10 +102,6 @@ public:
     bool keepPyramid = true;
 
 protected:
-    static void check(eao_status st, const char* what) {
-        if (st != EAO_OK) throw std::runtime_error(std::string(what) + ": " + eao_last_error());
-    }
-
     int nfeatures;
     double scaleFactor;
     int nlevels;
@@ -140,11 +135,10 @@ void ComputeStereoMatches(FrameT& F) {
     F.mvuRight = std::vector<float>(N, -1.0f);
     F.mvDepth = std::vector<float>(N, -1.0f);
     if (N == 0 || Nr == 0) return;
-    const eao_status st = eao_compute_stereo_matches(F.mpORBextractorLeft->handle(), F.mpORBextractorRight->handle(), 0, N,
-                                                     reinterpret_cast<const eao_keypoint*>(F.mvKeys.data()), F.mDescriptors.ptr(0), Nr,
-                                                     reinterpret_cast<const eao_keypoint*>(F.mvKeysRight.data()), F.mDescriptorsRight.ptr(0),
-                                                     F.mb, F.mbf, F.mvuRight.data(), F.mvDepth.data());
-    if (st != EAO_OK) throw std::runtime_error(std::string("eao_compute_stereo_matches: ") + eao_last_error());
+    detail::check(eao_compute_stereo_matches(F.mpORBextractorLeft->handle(), F.mpORBextractorRight->handle(), 0, N,
+                                             reinterpret_cast<const eao_keypoint*>(F.mvKeys.data()), F.mDescriptors.ptr(0), Nr,
+                                             reinterpret_cast<const eao_keypoint*>(F.mvKeysRight.data()), F.mDescriptorsRight.ptr(0),
+                                             F.mb, F.mbf, F.mvuRight.data(), F.mvDepth.data()), "eao_compute_stereo_matches");
 }
 
 }  // namespace eaofusion

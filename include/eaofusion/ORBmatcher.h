@@ -25,8 +25,7 @@
 #include <utility>
 #include <vector>
 
-#include "../eao_fusion.h"
-#include "cv_compat.h"
+#include "adapter_detail.h"
 
 namespace eaofusion {
 
@@ -41,14 +40,14 @@ public:
     // DistinctiveDescriptor() below, Frame::ComputeStereoMatches (src/Frame.cc:914) to eaofusion::ComputeStereoMatches.
     static int DescriptorDistance(const cv::Mat& a, const cv::Mat& b) {
         uint16_t d = 0;
-        check(eao_hamming_matrix(a.ptr(0), 1, b.ptr(0), 1, &d), "eao_hamming_matrix");
+        detail::check(eao_hamming_matrix(a.ptr(0), 1, b.ptr(0), 1, &d), "eao_hamming_matrix");
         return d;
     }
 
     // D[i * nb + j] for descriptor matrices (rows of 32 bytes, continuous)
     static void DistanceMatrix(const cv::Mat& A, const cv::Mat& B, std::vector<uint16_t>& D) {
         D.resize((size_t)A.rows * B.rows);
-        if (A.rows && B.rows) check(eao_hamming_matrix(A.ptr(0), A.rows, B.ptr(0), B.rows, D.data()), "eao_hamming_matrix");
+        if (A.rows && B.rows) detail::check(eao_hamming_matrix(A.ptr(0), A.rows, B.ptr(0), B.rows, D.data()), "eao_hamming_matrix");
     }
 
     // per query row: best / second-best distance and their train indices over the candidates allowed by `mask`
@@ -56,7 +55,7 @@ public:
     // "if(dist<bestDist){bestDist2=bestDist;bestDist=dist;bestIdx=idx;} else if(dist<bestDist2) bestDist2=dist;" (:102-114).
     static void BestTwo(const cv::Mat& A, const cv::Mat& B, const unsigned char* mask, std::vector<eao_best2>& out) {
         out.resize(A.rows);
-        if (A.rows && B.rows) check(eao_hamming_best2(A.ptr(0), A.rows, B.ptr(0), B.rows, mask, out.data()), "eao_hamming_best2");
+        if (A.rows && B.rows) detail::check(eao_hamming_best2(A.ptr(0), A.rows, B.ptr(0), B.rows, mask, out.data()), "eao_hamming_best2");
     }
 
     // ---- guided searches of the per-frame tracking loop.  Templates over the reference's Frame / MapPoint classes (same
@@ -80,8 +79,8 @@ public:
         }
         const eao_frame_view v = view(F, fa);
         int nm = 0;
-        check(eao_search_by_projection_points(&v, M, px.data(), py.data(), pxr.data(), vc.data(), lvl.data(), desc.data(), skip.data(),
-                                              th, mfNNratio, match.data(), &nm), "eao_search_by_projection_points");
+        detail::check(eao_search_by_projection_points(&v, M, px.data(), py.data(), pxr.data(), vc.data(), lvl.data(), desc.data(), skip.data(),
+                                                      th, mfNNratio, match.data(), &nm), "eao_search_by_projection_points");
         for (int i = 0; i < M; i++) if (match[i] >= 0) F.mvpMapPoints[match[i]] = vpMapPoints[i];
         return nm;
     }
@@ -100,18 +99,17 @@ public:
             valid[i] = (pMP && !LastFrame.mvbOutlier[i]) ? 1 : 0;
             oct[i] = LastFrame.mvKeys[i].octave; ang[i] = LastFrame.mvKeysUn[i].angle;
             if (!valid[i]) continue;
-            const cv::Mat X = pMP->GetWorldPos();
-            for (int k = 0; k < 3; k++) Xw[(size_t)i * 3 + k] = X.template at<float>(k);
+            detail::read3(pMP->GetWorldPos(), &Xw[(size_t)i * 3]);
             const cv::Mat d = pMP->GetDescriptor();
             std::memcpy(&desc[(size_t)i * 32], d.ptr(0), 32);
         }
         float Tc[16], Tl[16];
-        for (int r = 0; r < 4; r++) for (int c = 0; c < 4; c++) { Tc[r * 4 + c] = CurrentFrame.mTcw.template at<float>(r, c); Tl[r * 4 + c] = LastFrame.mTcw.template at<float>(r, c); }
+        detail::read44(CurrentFrame.mTcw, Tc); detail::read44(LastFrame.mTcw, Tl);
         const eao_frame_view v = view(CurrentFrame, fa);
         int nm = 0;
-        check(eao_search_by_projection_frames(&v, Tc, Tl, NL, valid.data(), Xw.data(), desc.data(), oct.data(), ang.data(), CurrentFrame.fx,
-                                              CurrentFrame.fy, CurrentFrame.cx, CurrentFrame.cy, CurrentFrame.mbf, CurrentFrame.mb, th, bMono ? 1 : 0,
-                                              mbCheckOrientation ? 1 : 0, cm.data(), &nm), "eao_search_by_projection_frames");
+        detail::check(eao_search_by_projection_frames(&v, Tc, Tl, NL, valid.data(), Xw.data(), desc.data(), oct.data(), ang.data(), CurrentFrame.fx,
+                                                      CurrentFrame.fy, CurrentFrame.cx, CurrentFrame.cy, CurrentFrame.mbf, CurrentFrame.mb, th, bMono ? 1 : 0,
+                                                      mbCheckOrientation ? 1 : 0, cm.data(), &nm), "eao_search_by_projection_frames");
         for (int k = 0; k < CurrentFrame.N; k++) if (cm[k] >= 0) CurrentFrame.mvpMapPoints[k] = LastFrame.mvpMapPoints[cm[k]];
         return nm;
     }
@@ -132,10 +130,10 @@ public:
         eao_frame_view v = kfview(*pKF, fa);
         for (int k = 0; k < v.n; k++) fa.occ[k] = vpMatched[k] ? 1 : 0;
         float S[16];
-        mat44(Scw, S);
+        detail::read44(Scw, S);
         std::vector<int32_t> km(v.n, -1);
         int nm = 0;
-        check(eao_search_by_projection_sim3(&v, S, pKF->fx, pKF->fy, pKF->cx, pKF->cy, &mp, th, km.data(), &nm), "eao_search_by_projection_sim3");
+        detail::check(eao_search_by_projection_sim3(&v, S, pKF->fx, pKF->fy, pKF->cx, pKF->cy, &mp, th, km.data(), &nm), "eao_search_by_projection_sim3");
         for (int k = 0; k < v.n; k++) if (km[k] >= 0) vpMatched[k] = vpPoints[km[k]];
         return nm;
     }
@@ -153,11 +151,11 @@ public:
         for (int k = 0; k < v.n; k++) fa.occ[k] = CurrentFrame.mvpMapPoints[k] ? 1 : 0;
         v.log_scale_factor = CurrentFrame.mfLogScaleFactor;
         float T[16];
-        mat44(CurrentFrame.mTcw, T);
+        detail::read44(CurrentFrame.mTcw, T);
         std::vector<int32_t> cm(v.n, -1);
         int nm = 0;
-        check(eao_search_by_projection_kf(&v, T, CurrentFrame.fx, CurrentFrame.fy, CurrentFrame.cx, CurrentFrame.cy, &mp, ang.data(), th, ORBdist,
-                                          mbCheckOrientation ? 1 : 0, cm.data(), &nm), "eao_search_by_projection_kf");
+        detail::check(eao_search_by_projection_kf(&v, T, CurrentFrame.fx, CurrentFrame.fy, CurrentFrame.cx, CurrentFrame.cy, &mp, ang.data(), th, ORBdist,
+                                                  mbCheckOrientation ? 1 : 0, cm.data(), &nm), "eao_search_by_projection_kf");
         for (int k = 0; k < v.n; k++) if (cm[k] >= 0) CurrentFrame.mvpMapPoints[k] = vpMPs[cm[k]];
         return nm;
     }
@@ -179,11 +177,11 @@ public:
         for (int j = 0; j < n2; j++) a2[j] = F.mvKeys[j].angle;
         const uint8_t* p1 = rows32(pKF->mDescriptors, n1, d1);
         const uint8_t* p2 = rows32(F.mDescriptors, n2, d2);
-        const eao_feature_vector fv1 = flatten(pKF->mFeatVec, f1), fv2 = flatten(F.mFeatVec, f2);
+        const eao_feature_vector fv1 = detail::flatten(pKF->mFeatVec, f1), fv2 = detail::flatten(F.mFeatVec, f2);
         std::vector<int32_t> m12(n1, -1);
         int nm = 0;
-        check(eao_search_by_bow(0, n1, p1, a1.data(), valid1.data(), &fv1, n2, p2, a2.data(), nullptr, &fv2, mfNNratio,
-                                mbCheckOrientation ? 1 : 0, m12.data(), &nm), "eao_search_by_bow");
+        detail::check(eao_search_by_bow(0, n1, p1, a1.data(), valid1.data(), &fv1, n2, p2, a2.data(), nullptr, &fv2, mfNNratio,
+                                        mbCheckOrientation ? 1 : 0, m12.data(), &nm), "eao_search_by_bow");
         for (int i = 0; i < n1; i++) if (m12[i] >= 0) vpMapPointMatches[m12[i]] = vpMapPointsKF[i];
         return nm;
     }
@@ -207,11 +205,11 @@ public:
             std::memcpy(&d2[(size_t)j * 32], pKF2->mDescriptors.ptr(j), 32);
         }
         FeatVecArrays f1, f2;
-        const eao_feature_vector fv1 = flatten(pKF1->mFeatVec, f1), fv2 = flatten(pKF2->mFeatVec, f2);
+        const eao_feature_vector fv1 = detail::flatten(pKF1->mFeatVec, f1), fv2 = detail::flatten(pKF2->mFeatVec, f2);
         std::vector<int32_t> m12(n1, -1);
         int nm = 0;
-        check(eao_search_by_bow(1, n1, d1.data(), a1.data(), v1.data(), &fv1, n2, d2.data(), a2.data(), v2.data(), &fv2, mfNNratio,
-                                mbCheckOrientation ? 1 : 0, m12.data(), &nm), "eao_search_by_bow");
+        detail::check(eao_search_by_bow(1, n1, d1.data(), a1.data(), v1.data(), &fv1, n2, d2.data(), a2.data(), v2.data(), &fv2, mfNNratio,
+                                        mbCheckOrientation ? 1 : 0, m12.data(), &nm), "eao_search_by_bow");
         for (int i = 0; i < n1; i++) if (m12[i] >= 0) vpMatches12[i] = vpMapPoints2[m12[i]];
         return nm;
     }
@@ -220,28 +218,21 @@ public:
     template <class KeyFrameT>
     int SearchForTriangulation(KeyFrameT* pKF1, KeyFrameT* pKF2, cv::Mat F12, std::vector<std::pair<size_t, size_t> >& vMatchedPairs,
                                const bool bOnlyStereo) {
-        // epipole in the second image (:663-670): C2 = R2w * Cw + t2w with cv::gemm's double accumulation
-        const cv::Mat Cw = pKF1->GetCameraCenter(), R2w = pKF2->GetRotation(), t2w = pKF2->GetTranslation();
-        float C2[3];
-        for (int r = 0; r < 3; r++) {
-            double acc = 0;
-            for (int k = 0; k < 3; k++) acc += (double)R2w.template at<float>(r, k) * (double)Cw.template at<float>(k);
-            C2[r] = (float)(acc + (double)t2w.template at<float>(r));
-        }
-        const float invz = 1.0f / C2[2];
-        const float ex = pKF2->fx * C2[0] * invz + pKF2->cx, ey = pKF2->fy * C2[1] * invz + pKF2->cy;
+        // epipole in the second image (:663-670)
+        float ex, ey;
+        detail::epipole(pKF1->GetCameraCenter(), pKF2->GetRotation(), pKF2->GetTranslation(), pKF2->fx, pKF2->fy, pKF2->cx, pKF2->cy, ex, ey);
         FrameArrays fa1, fa2;
         eao_frame_view v1 = kfview(*pKF1, fa1), v2 = kfview(*pKF2, fa2);
         for (int k = 0; k < v1.n; k++) fa1.occ[k] = pKF1->GetMapPoint(k) ? 1 : 0;
         for (int k = 0; k < v2.n; k++) fa2.occ[k] = pKF2->GetMapPoint(k) ? 1 : 0;
         FeatVecArrays f1, f2;
-        const eao_feature_vector fv1 = flatten(pKF1->mFeatVec, f1), fv2 = flatten(pKF2->mFeatVec, f2);
+        const eao_feature_vector fv1 = detail::flatten(pKF1->mFeatVec, f1), fv2 = detail::flatten(pKF2->mFeatVec, f2);
         float Fm[9];
-        for (int r = 0; r < 3; r++) for (int c = 0; c < 3; c++) Fm[r * 3 + c] = F12.template at<float>(r, c);
+        detail::read33(F12, Fm);
         std::vector<int32_t> m12(v1.n, -1);
         int nm = 0;
-        check(eao_search_for_triangulation(&v1, &fv1, &v2, &fv2, Fm, ex, ey, bOnlyStereo ? 1 : 0, mbCheckOrientation ? 1 : 0, m12.data(), &nm),
-              "eao_search_for_triangulation");
+        detail::check(eao_search_for_triangulation(&v1, &fv1, &v2, &fv2, Fm, ex, ey, bOnlyStereo ? 1 : 0, mbCheckOrientation ? 1 : 0, m12.data(), &nm),
+                      "eao_search_for_triangulation");
         vMatchedPairs.clear();
         vMatchedPairs.reserve(nm);
         for (size_t i = 0; i < m12.size(); i++) if (m12[i] >= 0) vMatchedPairs.push_back(std::make_pair(i, (size_t)m12[i]));
@@ -263,8 +254,8 @@ public:
         FrameArrays fa;
         const eao_frame_view v2 = view(F2, fa);
         int nm = 0;
-        check(eao_search_for_initialization(n1, oct.data(), ang.data(), d1.data(), &v2, pm.data(), windowSize, mfNNratio, mbCheckOrientation ? 1 : 0,
-                                            m12.data(), &nm), "eao_search_for_initialization");
+        detail::check(eao_search_for_initialization(n1, oct.data(), ang.data(), d1.data(), &v2, pm.data(), windowSize, mfNNratio, mbCheckOrientation ? 1 : 0,
+                                                    m12.data(), &nm), "eao_search_for_initialization");
         vnMatches12.assign(m12.begin(), m12.end());
         for (int i = 0; i < n1; i++) { vbPrevMatched[i].x = pm[2 * i]; vbPrevMatched[i].y = pm[2 * i + 1]; }
         return nm;
@@ -283,7 +274,7 @@ public:
         eao_frame_view v1 = kfview(*pKF1, fa1);
         for (int k = 0; k < v1.n; k++) fa1.occ[k] = pKF1->GetMapPoint(k) ? 1 : 0;
         FeatVecArrays f1;
-        const eao_feature_vector fv1 = flatten(pKF1->mFeatVec, f1);
+        const eao_feature_vector fv1 = detail::flatten(pKF1->mFeatVec, f1);
         std::vector<FrameArrays> fa2(nb);
         std::vector<FeatVecArrays> f2(nb);
         std::vector<eao_frame_view> v2(nb);
@@ -294,24 +285,16 @@ public:
         const cv::Mat Cw = pKF1->GetCameraCenter();
         for (size_t q = 0; q < nb; q++) {
             KeyFrameT* pKF2 = vpNeighKFs[q];
-            const cv::Mat R2w = pKF2->GetRotation(), t2w = pKF2->GetTranslation();      // the epipole in the second image, as in the single call (:663-670)
-            float C2[3];
-            for (int r = 0; r < 3; r++) {
-                double acc = 0;
-                for (int k = 0; k < 3; k++) acc += (double)R2w.template at<float>(r, k) * (double)Cw.template at<float>(k);
-                C2[r] = (float)(acc + (double)t2w.template at<float>(r));
-            }
-            const float invz = 1.0f / C2[2];
-            ex[q] = pKF2->fx * C2[0] * invz + pKF2->cx; ey[q] = pKF2->fy * C2[1] * invz + pKF2->cy;
+            detail::epipole(Cw, pKF2->GetRotation(), pKF2->GetTranslation(), pKF2->fx, pKF2->fy, pKF2->cx, pKF2->cy, ex[q], ey[q]);      // as in the single call (:663-670)
             v2[q] = kfview(*pKF2, fa2[q]);
             for (int k = 0; k < v2[q].n; k++) fa2[q].occ[k] = pKF2->GetMapPoint(k) ? 1 : 0;
-            fv2[q] = flatten(pKF2->mFeatVec, f2[q]);
+            fv2[q] = detail::flatten(pKF2->mFeatVec, f2[q]);
             pv[q] = &v2[q]; pf[q] = &fv2[q];
-            for (int r = 0; r < 3; r++) for (int c = 0; c < 3; c++) Fm[9 * q + r * 3 + c] = vF12[q].template at<float>(r, c);
+            detail::read33(vF12[q], &Fm[9 * q]);
         }
         std::vector<int32_t> m12(nb * (size_t)v1.n, -1), nm(nb, 0);
-        check(eao_search_for_triangulation_batch(&v1, &fv1, (int)nb, pv.data(), pf.data(), Fm.data(), ex.data(), ey.data(), bOnlyStereo ? 1 : 0,
-                                                 mbCheckOrientation ? 1 : 0, m12.data(), nm.data()), "eao_search_for_triangulation_batch");
+        detail::check(eao_search_for_triangulation_batch(&v1, &fv1, (int)nb, pv.data(), pf.data(), Fm.data(), ex.data(), ey.data(), bOnlyStereo ? 1 : 0,
+                                                         mbCheckOrientation ? 1 : 0, m12.data(), nm.data()), "eao_search_for_triangulation_batch");
         for (size_t q = 0; q < nb; q++) {
             vvMatchedPairs[q].reserve(nm[q]);
             for (int i = 0; i < v1.n; i++) if (m12[q * v1.n + i] >= 0) vvMatchedPairs[q].push_back(std::make_pair((size_t)i, (size_t)m12[q * v1.n + i]));
@@ -330,21 +313,13 @@ public:
         const cv::Mat Cw = pKF1->GetCameraCenter();
         for (size_t q = 0; q < nb; q++) {
             KeyFrameT* pKF2 = vpNeighKFs[q];
-            const cv::Mat R2w = pKF2->GetRotation(), t2w = pKF2->GetTranslation();      // the epipole in the second image, as in the single call (:663-670)
-            float C2[3];
-            for (int r = 0; r < 3; r++) {
-                double acc = 0;
-                for (int k = 0; k < 3; k++) acc += (double)R2w.template at<float>(r, k) * (double)Cw.template at<float>(k);
-                C2[r] = (float)(acc + (double)t2w.template at<float>(r));
-            }
-            const float invz = 1.0f / C2[2];
-            ex[q] = pKF2->fx * C2[0] * invz + pKF2->cx; ey[q] = pKF2->fy * C2[1] * invz + pKF2->cy;
-            for (int r = 0; r < 3; r++) for (int c = 0; c < 3; c++) Fm[9 * q + r * 3 + c] = vF12[q].template at<float>(r, c);
+            detail::epipole(Cw, pKF2->GetRotation(), pKF2->GetTranslation(), pKF2->fx, pKF2->fy, pKF2->cx, pKF2->cy, ex[q], ey[q]);      // as in the single call (:663-670)
+            detail::read33(vF12[q], &Fm[9 * q]);
         }
         const int n1 = eao_keyframe_size(h1);
         std::vector<int32_t> m12(nb * (size_t)n1, -1), nm(nb, 0);
-        check(eao_kf_search_for_triangulation(h1, (int)nb, h2s.data(), Fm.data(), ex.data(), ey.data(), bOnlyStereo ? 1 : 0, mbCheckOrientation ? 1 : 0, m12.data(), nm.data()),
-              "eao_kf_search_for_triangulation");
+        detail::check(eao_kf_search_for_triangulation(h1, (int)nb, h2s.data(), Fm.data(), ex.data(), ey.data(), bOnlyStereo ? 1 : 0, mbCheckOrientation ? 1 : 0, m12.data(), nm.data()),
+                      "eao_kf_search_for_triangulation");
         for (size_t q = 0; q < nb; q++) {
             vvMatchedPairs[q].reserve(nm[q]);
             for (int i = 0; i < n1; i++) if (m12[q * n1 + i] >= 0) vvMatchedPairs[q].push_back(std::make_pair((size_t)i, (size_t)m12[q * n1 + i]));
@@ -362,10 +337,10 @@ public:
         const eao_frame_view v = kfview(*pKF, fa);
         const cv::Mat Rcw = pKF->GetRotation(), tcw = pKF->GetTranslation(), Ow = pKF->GetCameraCenter();
         float pose[15];
-        for (int r = 0; r < 3; r++) { for (int c = 0; c < 3; c++) pose[r * 3 + c] = Rcw.template at<float>(r, c); pose[9 + r] = tcw.template at<float>(r); pose[12 + r] = Ow.template at<float>(r); }
+        detail::read33(Rcw, pose); detail::read3(tcw, pose + 9); detail::read3(Ow, pose + 12);
         std::vector<int32_t> best(vpMapPoints.size(), -1);
         int n = 0;
-        check(eao_fuse_search(&v, 0, pose, pKF->fx, pKF->fy, pKF->cx, pKF->cy, pKF->mbf, &mp, th, best.data(), &n), "eao_fuse_search");
+        detail::check(eao_fuse_search(&v, 0, pose, pKF->fx, pKF->fy, pKF->cx, pKF->cy, pKF->mbf, &mp, th, best.data(), &n), "eao_fuse_search");
         int nFused = 0;
         for (size_t i = 0; i < vpMapPoints.size(); i++) {
             if (best[i] < 0) continue;
@@ -411,7 +386,7 @@ public:
             if (!handles) { v[q] = kfview(*pKF, fa[q]); pv[q] = &v[q]; }
             const cv::Mat Rcw = pKF->GetRotation(), tcw = pKF->GetTranslation(), Ow = pKF->GetCameraCenter();
             float* pose = &poses[15 * q];
-            for (int r = 0; r < 3; r++) { for (int c = 0; c < 3; c++) pose[r * 3 + c] = Rcw.template at<float>(r, c); pose[9 + r] = tcw.template at<float>(r); pose[12 + r] = Ow.template at<float>(r); }
+            detail::read33(Rcw, pose); detail::read3(tcw, pose + 9); detail::read3(Ow, pose + 12);
         }
         KeyFrameT* k0 = vpTargetKFs[0];
         // search `pts` against targets q0 .. nk-1; row q - q0 of `out` = target q
@@ -422,9 +397,9 @@ public:
             out.assign(nt * pts.size(), -1);
             std::vector<int32_t> nf(nt, 0);
             if (handles)
-                check(eao_kf_fuse_search((int)nt, handles->data() + q0, 0, &poses[15 * q0], k0->fx, k0->fy, k0->cx, k0->cy, k0->mbf, &mp, th, out.data(), nf.data()), "eao_kf_fuse_search");
+                detail::check(eao_kf_fuse_search((int)nt, handles->data() + q0, 0, &poses[15 * q0], k0->fx, k0->fy, k0->cx, k0->cy, k0->mbf, &mp, th, out.data(), nf.data()), "eao_kf_fuse_search");
             else
-                check(eao_fuse_search_batch((int)nt, pv.data() + q0, 0, &poses[15 * q0], k0->fx, k0->fy, k0->cx, k0->cy, k0->mbf, &mp, th, out.data(), nf.data()), "eao_fuse_search_batch");
+                detail::check(eao_fuse_search_batch((int)nt, pv.data() + q0, 0, &poses[15 * q0], k0->fx, k0->fy, k0->cx, k0->cy, k0->mbf, &mp, th, out.data(), nf.data()), "eao_fuse_search_batch");
         };
         std::vector<int32_t> best;
         search(vpMapPoints, 0, best);
@@ -475,10 +450,10 @@ public:
         FrameArrays fa;
         const eao_frame_view v = kfview(*pKF, fa);
         float S[16];
-        mat44(Scw, S);
+        detail::read44(Scw, S);
         std::vector<int32_t> best(vpPoints.size(), -1);
         int n = 0;
-        check(eao_fuse_search(&v, 1, S, pKF->fx, pKF->fy, pKF->cx, pKF->cy, 0.f, &mp, th, best.data(), &n), "eao_fuse_search");
+        detail::check(eao_fuse_search(&v, 1, S, pKF->fx, pKF->fy, pKF->cx, pKF->cy, 0.f, &mp, th, best.data(), &n), "eao_fuse_search");
         int nFused = 0;
         for (size_t i = 0; i < vpPoints.size(); i++) {
             if (best[i] < 0) continue;
@@ -518,13 +493,13 @@ public:
         FrameArrays fa1, fa2;
         const eao_frame_view v1 = kfview(*pKF1, fa1), v2 = kfview(*pKF2, fa2);
         float T1[16], T2[16], R[9], t[3];
-        pose44(pKF1->GetRotation(), pKF1->GetTranslation(), T1);
-        pose44(pKF2->GetRotation(), pKF2->GetTranslation(), T2);
-        for (int r = 0; r < 3; r++) { for (int c = 0; c < 3; c++) R[r * 3 + c] = R12.template at<float>(r, c); t[r] = t12.template at<float>(r); }
+        detail::read_pose(pKF1->GetRotation(), pKF1->GetTranslation(), T1);
+        detail::read_pose(pKF2->GetRotation(), pKF2->GetTranslation(), T2);
+        detail::read33(R12, R); detail::read3(t12, t);
         std::vector<int32_t> m12(N1, -1);
         int nf = 0;
-        check(eao_search_by_sim3(&v1, T1, &mp1, &v2, T2, &mp2, pKF1->fx, pKF1->fy, pKF1->cx, pKF1->cy, s12, R, t, th, m12.data(), &nf),
-              "eao_search_by_sim3");
+        detail::check(eao_search_by_sim3(&v1, T1, &mp1, &v2, T2, &mp2, pKF1->fx, pKF1->fy, pKF1->cx, pKF1->cy, s12, R, t, th, m12.data(), &nf),
+                      "eao_search_by_sim3");
         for (int i = 0; i < N1; i++) if (m12[i] >= 0) vpMatches12[i] = vpMapPoints2[m12[i]];
         return nf;
     }
@@ -545,7 +520,7 @@ public:
             start[s + 1] = (int32_t)(flat.size() / 32);
         }
         if (!descriptors.empty())
-            check(eao_distinctive_descriptors((int32_t)descriptors.size(), start.data(), flat.data(), best.data()), "eao_distinctive_descriptors");
+            detail::check(eao_distinctive_descriptors((int32_t)descriptors.size(), start.data(), flat.data(), best.data()), "eao_distinctive_descriptors");
         return std::vector<int>(best.begin(), best.end());
     }
     static int DistinctiveDescriptor(const std::vector<cv::Mat>& vDescriptors) {
@@ -583,7 +558,7 @@ public:
 protected:
     struct FrameArrays { std::vector<float> x, y, ang, ur, sf, s2, is2; std::vector<int32_t> oct; std::vector<uint8_t> occ, desc; };
     struct PointArrays { std::vector<uint8_t> active, desc; std::vector<float> Xw, normal, dmin, dmax, draw; };
-    struct FeatVecArrays { std::vector<uint32_t> id, index; std::vector<int32_t> start; };
+    typedef detail::FeatVecArrays FeatVecArrays;
     // mfMaxDistance is what PredictScale divides (src/MapPoint.cc:385-394); upstream exposes it only through
     // GetMaxDistanceInvariance() = 1.2f * mfMaxDistance, which does not round-trip in float.  A derived class may name
     // the protected member of its base, and the resulting pointer-to-member applies to any MapPoint: an exact read
@@ -603,7 +578,7 @@ protected:
             if (!active(p)) continue;
             a.active[i] = 1;
             const cv::Mat X = p->GetWorldPos(), Nn = p->GetNormal(), d = p->GetDescriptor();
-            for (int k = 0; k < 3; k++) { a.Xw[i * 3 + k] = X.template at<float>(k); a.normal[i * 3 + k] = Nn.template at<float>(k); }
+            detail::read3(X, &a.Xw[i * 3]); detail::read3(Nn, &a.normal[i * 3]);
             a.dmin[i] = p->GetMinDistanceInvariance(); a.dmax[i] = p->GetMaxDistanceInvariance(); a.draw[i] = MaxDistance<MapPointT>::of(p);
             std::memcpy(&a.desc[i * 32], d.ptr(0), 32);
         }
@@ -611,18 +586,6 @@ protected:
         m.n = (int32_t)n; m.active = a.active.data(); m.Xw = a.Xw.data(); m.normal = a.normal.data(); m.min_dist_inv = a.dmin.data();
         m.max_dist_inv = a.dmax.data(); m.max_dist = a.draw.data(); m.desc = a.desc.data();
         return m;
-    }
-    template <class FeatVecT>
-    static eao_feature_vector flatten(const FeatVecT& fv, FeatVecArrays& a) {
-        a.id.clear(); a.index.clear(); a.start.assign(1, 0);
-        for (typename FeatVecT::const_iterator it = fv.begin(); it != fv.end(); ++it) {
-            a.id.push_back((uint32_t)it->first);
-            for (size_t k = 0; k < it->second.size(); k++) a.index.push_back((uint32_t)it->second[k]);
-            a.start.push_back((int32_t)a.index.size());
-        }
-        eao_feature_vector f;
-        f.n_nodes = (int32_t)a.id.size(); f.node_id = a.id.data(); f.node_start = a.start.data(); f.index = a.index.data();
-        return f;
     }
     // n rows of 32 descriptor bytes as ONE block: the matrix itself when its rows are contiguous (Frame / KeyFrame::mDescriptors come out of one
     // create(n, 32, CV_8U)), a packed copy in `pack` otherwise
@@ -632,13 +595,6 @@ protected:
         pack.resize((size_t)n * 32);
         for (int i = 0; i < n; i++) std::memcpy(&pack[(size_t)i * 32], D.ptr(i), 32);
         return pack.data();
-    }
-    static void mat44(const cv::Mat& M, float* out) {
-        for (int r = 0; r < 4; r++) for (int c = 0; c < 4; c++) out[r * 4 + c] = M.at<float>(r, c);
-    }
-    static void pose44(const cv::Mat& R, const cv::Mat& t, float* out) {
-        for (int r = 0; r < 3; r++) { for (int c = 0; c < 3; c++) out[r * 4 + c] = R.at<float>(r, c); out[r * 4 + 3] = t.at<float>(r); }
-        out[12] = out[13] = out[14] = 0.f; out[15] = 1.f;
     }
     // KeyFrame flavour of view(): per-keyframe grid bounds (const members, include/KeyFrame.h:193-194,255-262), no
     // occupancy (each search defines its own), level sigmas and the log scale factor
@@ -686,9 +642,6 @@ protected:
         v.log_scale_factor = 0.f; v.level_sigma2 = nullptr; v.inv_level_sigma2 = nullptr;
         return v;
     }
-    static void check(eao_status st, const char* what) {
-        if (st != EAO_OK) throw std::runtime_error(std::string(what) + ": " + eao_last_error());
-    }
     float mfNNratio;
     bool mbCheckOrientation;
 };
@@ -711,9 +664,9 @@ public:
         ORBmatcher::FeatVecArrays fv;
         eao_frame_view v = ORBmatcher::kfview(*pKF, fa);
         for (int k = 0; k < v.n; k++) fa.occ[k] = pKF->GetMapPoint(k) ? 1 : 0;
-        const eao_feature_vector f = ORBmatcher::flatten(pKF->mFeatVec, fv);
+        const eao_feature_vector f = detail::flatten(pKF->mFeatVec, fv);
         eao_keyframe* h = nullptr;
-        ORBmatcher::check(eao_keyframe_create(&v, &f, &h), "eao_keyframe_create");
+        detail::check(eao_keyframe_create(&v, &f, &h), "eao_keyframe_create");
         map_[(const void*)pKF] = h;
         send_depth(pKF, h, 0);
         return h;
@@ -725,7 +678,7 @@ public:
         const int n = eao_keyframe_size(it->second);
         std::vector<uint8_t> occ(n > 0 ? n : 1, 0);
         for (int k = 0; k < n; k++) occ[k] = pKF->GetMapPoint(k) ? 1 : 0;
-        ORBmatcher::check(eao_keyframe_update_points(it->second, occ.data()), "eao_keyframe_update_points");
+        detail::check(eao_keyframe_update_points(it->second, occ.data()), "eao_keyframe_update_points");
     }
     template <class KeyFrameT>
     void erase(KeyFrameT* pKF) {
@@ -744,7 +697,7 @@ private:
         std::vector<float> d(pKF->mvDepth.begin(), pKF->mvDepth.end()), rx(n > 0 ? n : 1), ry(n > 0 ? n : 1);
         d.resize(n > 0 ? n : 1, -1.f);
         for (int i = 0; i < n; i++) { rx[i] = pKF->mvKeys[i].pt.x; ry[i] = pKF->mvKeys[i].pt.y; }
-        ORBmatcher::check(eao_keyframe_set_depth(h, d.data(), rx.data(), ry.data()), "eao_keyframe_set_depth");
+        detail::check(eao_keyframe_set_depth(h, d.data(), rx.data(), ry.data()), "eao_keyframe_set_depth");
     }
     template <class KeyFrameT>
     static void send_depth(KeyFrameT*, eao_keyframe*, long) {}

@@ -23,28 +23,22 @@
 // fx, fy, cx, cy, mnId.
 #pragma once
 
+#include <cstddef>
 #include <cstdint>
 #include <vector>
 
-#include "../eao_fusion.h"
+#include "adapter_detail.h"
 
 namespace eaofusion {
 
 namespace object_association_detail {
-
-template <class PosT>
-void push_pos(const PosT& pos, std::vector<float>& xyz) {
-    xyz.push_back(pos.template at<float>(0));
-    xyz.push_back(pos.template at<float>(1));
-    xyz.push_back(pos.template at<float>(2));
-}
 
 // the points upstream counts and compares: not isBad() and not out_point (:737, :751, :787, :815, :846), in vector order
 template <class VecT>
 void gather_good(const VecT& points, std::vector<float>& xyz) {
     for (size_t i = 0; i < points.size(); i++) {
         if (points[i]->isBad() || points[i]->out_point) continue;
-        push_pos(points[i]->GetWorldPos(), xyz);
+        detail::push3(points[i]->GetWorldPos(), xyz);
     }
 }
 
@@ -88,12 +82,11 @@ int project(const std::vector<ObjMapT*>& objs, const FrameT& frame, int cols, in
     std::vector<int32_t> start(1, 0);
     for (ObjMapT* obj : objs) {
         for (size_t j = 0; j < obj->mvpMapObjectMappoints.size(); j++)      // (:1612: every point, bad ones included)
-            push_pos(obj->mvpMapObjectMappoints[j]->GetWorldPos(), xyz);
+            detail::push3(obj->mvpMapObjectMappoints[j]->GetWorldPos(), xyz);
         start.push_back((int32_t)(xyz.size() / 3));
     }
     float Tcw[16];
-    for (int r = 0; r < 4; r++)
-        for (int c = 0; c < 4; c++) Tcw[4 * r + c] = frame.mTcw.template at<float>(r, c);
+    detail::read44(frame.mTcw, Tcw);
     std::vector<int32_t> rect(4 * objs.size(), 0);
     std::vector<uint8_t> status(objs.size(), 0);
     if (eao_object_project_rects_batch((int32_t)objs.size(), start.data(), xyz.data(), Tcw, frame.fx, frame.fy, frame.cx, frame.cy, (int32_t)cols, (int32_t)rows,

@@ -19,11 +19,12 @@
 // value with at<float>(0..2) (cv::Mat 3x1 CV_32F upstream).
 #pragma once
 
+#include <cstddef>
 #include <cstdint>
 #include <mutex>
 #include <vector>
 
-#include "../eao_fusion.h"
+#include "adapter_detail.h"
 
 namespace eaofusion {
 
@@ -41,12 +42,7 @@ bool runs(const ObjT& obj, bool biForest) {
 // :1259-1269: GetWorldPos() of the points in vector order
 template <class ObjT>
 void gather(const ObjT& obj, std::vector<float>& xyz) {
-    for (size_t i = 0; i < obj.mvpMapObjectMappoints.size(); i++) {
-        const auto pos = obj.mvpMapObjectMappoints[i]->GetWorldPos();
-        xyz.push_back(pos.template at<float>(0));
-        xyz.push_back(pos.template at<float>(1));
-        xyz.push_back(pos.template at<float>(2));
-    }
+    for (size_t i = 0; i < obj.mvpMapObjectMappoints.size(); i++) detail::push3(obj.mvpMapObjectMappoints[i]->GetWorldPos(), xyz);
 }
 
 // :1311-1347 with the flags the library returned for the points gathered above

@@ -30,8 +30,7 @@
 #include <utility>
 #include <vector>
 
-#include "../eao_fusion.h"
-#include "cv_compat.h"
+#include "adapter_detail.h"
 
 namespace eaofusion {
 
@@ -189,16 +188,14 @@ EssentialGraphWalk WalkEssentialGraph(const std::vector<KeyFrameT*>& vpKFs, cons
     for (size_t i = 0, iend = vpMPs.size(); i < iend; i++) {
         MapPointT* pMP = vpMPs[i];
         if (pMP->isBad()) continue;
-        const auto P3Dw = pMP->GetWorldPos();
-        for (int k = 0; k < 3; k++) w.Xw.push_back(P3Dw.template at<float>(k));
+        detail::push3(pMP->GetWorldPos(), w.Xw);
         w.ref.push_back(reference_of(pMP));
         w.point_index.push_back((int)i);
     }
     for (size_t i = 0, iend = vpMPlanes.size(); i < iend; i++) {
         MapPlaneT* pMP = vpMPlanes[i];
         if (pMP->isBad()) continue;
-        const auto P3Dw = pMP->GetWorldPos();      // (four coefficients; the fork's loop reads the first three through Converter::toVector3d)
-        for (int k = 0; k < 3; k++) w.Xw.push_back(P3Dw.template at<float>(k));
+        detail::push3(pMP->GetWorldPos(), w.Xw);      // (four coefficients; the fork's loop reads the first three through Converter::toVector3d)
         w.ref.push_back(reference_of(pMP));
         w.plane_index.push_back((int)i);
     }
@@ -220,30 +217,23 @@ void OptimizeEssentialGraph(MapT* pMap, KeyFrameT* pLoopKF, KeyFrameT* pCurKF, c
     std::vector<float> Tiw(w.ids.size() * 16), Xc(w.ref.size() * 3 + 3);
     eao_essential_graph_result r = eao_essential_graph_result();
     r.Scw = Scw.data(); r.Tiw = Tiw.data(); r.Xw_corrected = Xc.data();
-    const eao_status st = eao_optimize_essential_graph(&p, &r);
-    if (st != EAO_OK) throw std::runtime_error(std::string("eao_optimize_essential_graph: ") + eao_last_error());
+    detail::check(eao_optimize_essential_graph(&p, &r), "eao_optimize_essential_graph");
     std::unique_lock<std::mutex> lock(pMap->mMutexMapUpdate);
     // SE3 Pose Recovering. Sim3:[sR t;0 1] -> SE3:[R t/s;0 1]
     for (size_t v = 0; v < w.ids.size(); v++) {
-        cv::Mat T(4, 4, CV_32F);
-        for (int k = 0; k < 16; k++) T.at<float>(k / 4, k % 4) = Tiw[v * 16 + k];
-        vpKFs[w.kf_index[v]]->SetPose(T);
+        vpKFs[w.kf_index[v]]->SetPose(detail::mat_of(&Tiw[v * 16], 4, 4));
     }
     // Correct points
     for (size_t k = 0; k < w.point_index.size(); k++) {
         MapPointT* pMP = vpMPs[w.point_index[k]];
-        cv::Mat X(3, 1, CV_32F);
-        for (int c = 0; c < 3; c++) X.at<float>(c) = Xc[k * 3 + c];
-        pMP->SetWorldPos(X);
+        pMP->SetWorldPos(detail::mat_of(&Xc[k * 3], 3, 1));
         pMP->UpdateNormalAndDepth();
     }
     // Correct planes
     const size_t base = w.point_index.size();
     for (size_t k = 0; k < w.plane_index.size(); k++) {
         MapPlaneT* pMP = vpMPlanes[w.plane_index[k]];
-        cv::Mat X(3, 1, CV_32F);
-        for (int c = 0; c < 3; c++) X.at<float>(c) = Xc[(base + k) * 3 + c];
-        pMP->SetWorldPos(X);
+        pMP->SetWorldPos(detail::mat_of(&Xc[(base + k) * 3], 3, 1));
     }
 }
 

@@ -20,6 +20,7 @@
 #include <list>
 #include <cstdint>
 #include <cstring>
+#include <exception>
 #include <map>
 #include <mutex>
 #include <stdexcept>
@@ -30,14 +31,9 @@
 #include <utility>
 #include <vector>
 
-#include "../eao_fusion.h"
-#include "cv_compat.h"
+#include "adapter_detail.h"
 
 namespace eaofusion {
-
-inline void check(eao_status st, const char* what) {
-    if (st != EAO_OK) throw std::runtime_error(std::string(what) + ": " + eao_last_error());
-}
 
 // Frame classes with associated map planes (upstream's include/Frame.h: mnPlaneNum, mvpMapPlanes, ...)
 template <class F, class = void> struct has_planes : std::false_type {};
@@ -57,7 +53,7 @@ typename std::enable_if<has_planes<FrameT>::value>::type collect_planes(FrameT* 
         const cv::Mat w = pMP->GetWorldPos();
         const cv::Mat& c = pFrame->mvPlaneCoefficients[i];
         pe.slot.push_back(i);
-        for (int k = 0; k < 4; k++) { pe.world.push_back(w.template at<float>(k, 0)); pe.obs.push_back(c.template at<float>(k, 0)); }
+        detail::push4(w, pe.world); detail::push4(c, pe.obs);
         pe.seen.push_back(pMP->mbSeen ? 1 : 0);
     }
 }
@@ -76,8 +72,7 @@ template <class MP, class = void> struct HasWorldPosOut : std::false_type {};
 template <class MP> struct HasWorldPosOut<MP, decltype(std::declval<MP&>().GetWorldPos(static_cast<float*>(nullptr)), void())> : std::true_type {};
 template <class MP> void world_pos(MP* mp, float* xyz, std::true_type) { mp->GetWorldPos(xyz); }
 template <class MP> void world_pos(MP* mp, float* xyz, std::false_type) {
-    const cv::Mat P = mp->GetWorldPos();
-    for (int k = 0; k < 3; k++) xyz[k] = P.template at<float>(k);
+    read3(mp->GetWorldPos(), xyz);
 }
 }  // namespace detail
 
@@ -115,8 +110,7 @@ bool gather_pose(FrameT* pFrame, PoseJob& j) {
     }
     j.n = (int)j.slot.size();
     if (j.n < 3) return false;   // pose untouched, as upstream
-    cv::Mat Tcw = pFrame->mTcw;
-    for (int r = 0; r < 4; r++) for (int c = 0; c < 4; c++) j.T[r * 4 + c] = Tcw.template at<float>(r, c);
+    detail::read44(pFrame->mTcw, j.T);
     collect_planes(pFrame, j.pe);     // added after the "< 3 correspondences" test, as upstream (:453-456)
     const int M = (int)j.pe.slot.size();
     j.P = eao_pose_problem{j.n, j.T, j.Xw.data(), j.obs.data(), j.inv.data(), pFrame->fx, pFrame->fy, pFrame->cx, pFrame->cy, pFrame->mbf,
@@ -132,9 +126,7 @@ template <class FrameT>
 int store_pose(FrameT* pFrame, const PoseJob& j) {
     for (int k = 0; k < j.n; k++) pFrame->mvbOutlier[j.slot[k]] = j.outl[k] != 0;
     store_planes(pFrame, j.pe, j.pout);
-    cv::Mat pose(4, 4, CV_32F);
-    for (int r = 0; r < 4; r++) for (int c = 0; c < 4; c++) pose.template at<float>(r, c) = j.R.Tcw[r * 4 + c];
-    pFrame->SetPose(pose);
+    pFrame->SetPose(detail::mat_of(j.R.Tcw, 4, 4));
     return j.R.n_inliers;
 }
 
@@ -143,7 +135,7 @@ int PoseOptimization(FrameT* pFrame) {
     static thread_local PoseJob j;      // (its vectors keep their capacity: nothing is allocated per frame after the first)
     j.slot.clear(); j.Xw.clear(); j.obs.clear(); j.inv.clear(); j.pe.slot.clear(); j.pe.world.clear(); j.pe.obs.clear(); j.pe.seen.clear();
     if (!gather_pose<MapPointT>(pFrame, j)) return 0;
-    check(eao_pose_optimization(&j.P, &j.R), "eao_pose_optimization");
+    detail::check(eao_pose_optimization(&j.P, &j.R), "eao_pose_optimization");
     return store_pose(pFrame, j);
 }
 
@@ -159,7 +151,7 @@ std::vector<int> PoseOptimizationBatch(const std::vector<FrameT*>& frames) {
     std::vector<eao_pose_problem> P(live.size());
     std::vector<eao_pose_result> R(live.size());
     for (size_t q = 0; q < live.size(); q++) { P[q] = jobs[live[q]].P; R[q] = jobs[live[q]].R; }
-    check(eao_pose_optimization_batch(P.data(), (int32_t)live.size(), R.data()), "eao_pose_optimization_batch");
+    detail::check(eao_pose_optimization_batch(P.data(), (int32_t)live.size(), R.data()), "eao_pose_optimization_batch");
     for (size_t q = 0; q < live.size(); q++) {
         jobs[live[q]].R = R[q];
         ret[live[q]] = store_pose(frames[live[q]], jobs[live[q]]);
@@ -332,8 +324,7 @@ void LocalBundleAdjustment(KeyFrameT* pKF, bool* pbStopFlag, MapT* pMap) {
     for (size_t i = 0; i < nC; i++) {
         KeyFrameT* kf = S.cams[i].kf;
         S.camBad[i] = kf->isBad() ? 1 : 0;
-        const cv::Mat T = kf->GetPose();
-        for (int r = 0; r < 4; r++) for (int c = 0; c < 4; c++) S.camT[i * 16 + r * 4 + c] = T.template at<float>(r, c);
+        detail::read44(kf->GetPose(), &S.camT[i * 16]);
         S.camFixed[i] = S.cams[i].fixed ? 1 : 0;
         // upstream copies the intrinsics into every edge from ITS keyframe (e->fx = pKFi->fx ..., src/Optimizer.cc:858-898); the
         // C-ABI carries one set per window, which is what this fork's single-camera Frame / KeyFrame statics amount to --
@@ -371,7 +362,7 @@ void LocalBundleAdjustment(KeyFrameT* pKF, bool* pbStopFlag, MapT* pMap) {
     eao_ba_result R;
     R.cam_Tcw = S.camOut.data(); R.points = S.xyzOut.data(); R.edge_outlier = S.erase.data();
     static_assert(sizeof(bool) == 1, "bool* abort flag is polled as a byte");
-    check(eao_local_ba(&P, reinterpret_cast<const volatile uint8_t*>(pbStopFlag), &R), "eao_local_ba");
+    detail::check(eao_local_ba(&P, reinterpret_cast<const volatile uint8_t*>(pbStopFlag), &R), "eao_local_ba");
     if (R.aborted) return;
 
     std::unique_lock<std::mutex> lock(pMap->mMutexMapUpdate);
@@ -386,11 +377,11 @@ void LocalBundleAdjustment(KeyFrameT* pKF, bool* pbStopFlag, MapT* pMap) {
     cv::Mat pose(4, 4, CV_32F), pos(3, 1, CV_32F);      // (SetPose / SetWorldPos copy their argument, src/KeyFrame.cc:74-86, src/MapPoint.cc:68-73)
     for (size_t i = 0; i < nC; i++) {
         if (!S.cams[i].local) continue;   // only local keyframes are written back
-        for (int r = 0; r < 4; r++) for (int c = 0; c < 4; c++) pose.template at<float>(r, c) = S.camOut[i * 16 + r * 4 + c];
+        detail::write44(pose, &S.camOut[i * 16]);
         S.cams[i].kf->SetPose(pose);
     }
     for (size_t i = 0; i < nP; i++) {
-        for (int k = 0; k < 3; k++) pos.template at<float>(k) = S.xyzOut[i * 3 + k];
+        detail::write_vec(pos, &S.xyzOut[i * 3], 3);
         S.pts[i]->SetWorldPos(pos);
         S.pts[i]->UpdateNormalAndDepth();
     }
@@ -432,8 +423,7 @@ void BundleAdjustment(const std::vector<KeyFrameT*>& vpKFs, const std::vector<Ma
     std::vector<uint8_t> camFixed(cams.size()), included(pts.size(), 0);
     std::vector<int32_t> eCam, ePt;
     for (size_t i = 0; i < cams.size(); i++) {
-        const cv::Mat T = cams[i]->GetPose();
-        for (int r = 0; r < 4; r++) for (int c = 0; c < 4; c++) camT[i * 16 + r * 4 + c] = T.template at<float>(r, c);
+        detail::read44(cams[i]->GetPose(), &camT[i * 16]);
         camFixed[i] = cams[i]->mnId == 0 ? 1 : 0;                       // :91
     }
     // The read side of the walk -- a lock, a position and a std::map of observations per map point, a keypoint per observation: pointer chasing through the whole map,
@@ -448,7 +438,7 @@ void BundleAdjustment(const std::vector<KeyFrameT*>& vpKFs, const std::vector<Ma
     const int nWalk = (int)std::max<size_t>(1, std::min<size_t>(std::min<size_t>(16, std::thread::hardware_concurrency() / 2), nPts / 4096));      // (a thread per 4096 points: starting one costs ~50 us)
     std::vector<Part> parts((size_t)nWalk);
     const Scratch* const table = &S;      // (S is thread_local: a helper thread must look the keyframes up in the CALLER's table, not in its own empty one)
-    auto walk = [&, table](int t) {
+    auto walk_range = [&, table](int t) {
         Part& Q = parts[(size_t)t];
         const size_t i0 = nPts * (size_t)t / (size_t)nWalk, i1 = nPts * (size_t)(t + 1) / (size_t)nWalk;
         Q.eCam.reserve((i1 - i0) * 7); Q.ePt.reserve((i1 - i0) * 7); Q.obs.reserve((i1 - i0) * 21); Q.inv.reserve((i1 - i0) * 7);
@@ -471,17 +461,23 @@ void BundleAdjustment(const std::vector<KeyFrameT*>& vpKFs, const std::vector<Ma
             }
         }
     };
-    if (nWalk == 1) walk(0);
-    else {
+    // What a range's walk throws (an accessor of the reference, bad_alloc) is kept per part and rethrown below on the calling thread, behind the joins: an
+    // exception that left a helper's function would end the process, and so would one that unwound past a joinable std::thread.
+    std::vector<std::exception_ptr> failed((size_t)nWalk);
+    auto walk = [&](int t) {
+        try { walk_range(t); } catch (...) { failed[(size_t)t] = std::current_exception(); }
+    };
+    {
         std::vector<std::thread> helpers;
+        struct JoinAll { std::vector<std::thread>& h; ~JoinAll() { for (std::thread& t : h) t.join(); } } joinAll = {helpers};
         int started = 1;
         for (; started < nWalk; started++) {
             try { helpers.emplace_back(walk, started); } catch (const std::system_error&) { break; }      // (no thread to be had: the caller walks the remaining ranges itself)
         }
         walk(0);
         for (int t = started; t < nWalk; t++) walk(t);
-        for (std::thread& h : helpers) h.join();
     }
+    for (const std::exception_ptr& e : failed) if (e) std::rethrow_exception(e);      // the first in part order
     if (nWalk == 1) { eCam.swap(parts[0].eCam); ePt.swap(parts[0].ePt); obs.swap(parts[0].obs); inv.swap(parts[0].inv); }
     else {
         size_t nE = 0;
@@ -500,8 +496,7 @@ void BundleAdjustment(const std::vector<KeyFrameT*>& vpKFs, const std::vector<Ma
     std::vector<float> plWorld(planes.size() * 4), plObs;
     std::vector<int32_t> plEdgePlane, plEdgeCam;
     for (size_t i = 0; i < planes.size(); i++) {
-        const cv::Mat W = planes[i]->GetWorldPos();
-        for (int k = 0; k < 4; k++) plWorld[i * 4 + k] = W.template at<float>(k);
+        detail::read4(planes[i]->GetWorldPos(), &plWorld[i * 4]);
         const auto seenBy = planes[i]->GetObservations();           // map<KeyFrame*, int>
         for (const auto& ob : seenBy) {
             KeyFrameT* kf = ob.first;
@@ -510,7 +505,7 @@ void BundleAdjustment(const std::vector<KeyFrameT*>& vpKFs, const std::vector<Ma
             if (ci < 0) continue;                                       // optimizer.vertex(pKFi->mnId) == NULL, :234-235
             const cv::Mat& c = kf->mvPlaneCoefficients[ob.second];
             plEdgePlane.push_back((int32_t)i); plEdgeCam.push_back(ci);
-            for (int k = 0; k < 4; k++) plObs.push_back(c.template at<float>(k));
+            detail::push4(c, plObs);
         }
     }
     eao_ba_problem P;
@@ -526,11 +521,11 @@ void BundleAdjustment(const std::vector<KeyFrameT*>& vpKFs, const std::vector<Ma
     eao_ba_result R;
     R.cam_Tcw = camOut.data(); R.points = xyzOut.data(); R.edge_outlier = nullptr;
     static_assert(sizeof(bool) == 1, "bool* abort flag is polled as a byte");
-    check(eao_bundle_adjustment_planes(&P, planes.empty() ? nullptr : &PL, bRobust ? 1 : 0, reinterpret_cast<const volatile uint8_t*>(pbStopFlag), &R,
-                                       plOut.data()), "eao_bundle_adjustment_planes");
+    detail::check(eao_bundle_adjustment_planes(&P, planes.empty() ? nullptr : &PL, bRobust ? 1 : 0, reinterpret_cast<const volatile uint8_t*>(pbStopFlag), &R,
+                                               plOut.data()), "eao_bundle_adjustment_planes");
     cv::Mat T(4, 4, CV_32F), X(3, 1, CV_32F);                           // (SetPose / SetWorldPos / copyTo copy their argument)
     for (size_t i = 0; i < cams.size(); i++) {                          // :258-275
-        for (int r = 0; r < 4; r++) for (int c = 0; c < 4; c++) T.template at<float>(r, c) = camOut[i * 16 + r * 4 + c];
+        detail::write44(T, &camOut[i * 16]);
         if (nLoopKF == 0) {
             cams[i]->SetPose(T);
         } else {
@@ -541,7 +536,7 @@ void BundleAdjustment(const std::vector<KeyFrameT*>& vpKFs, const std::vector<Ma
     }
     for (size_t i = 0; i < pts.size(); i++) {                           // :277-300
         if (!included[i]) continue;
-        for (int k = 0; k < 3; k++) X.template at<float>(k) = xyzOut[i * 3 + k];
+        detail::write_vec(X, &xyzOut[i * 3], 3);
         if (nLoopKF == 0) {
             pts[i]->SetWorldPos(X);
             pts[i]->UpdateNormalAndDepth();
@@ -552,8 +547,7 @@ void BundleAdjustment(const std::vector<KeyFrameT*>& vpKFs, const std::vector<Ma
         }
     }
     for (size_t i = 0; i < planes.size(); i++) {                        // :303-322
-        cv::Mat C4(4, 1, CV_32F);
-        for (int k = 0; k < 4; k++) C4.template at<float>(k) = plOut[i * 4 + k];
+        const cv::Mat C4 = detail::mat_of(&plOut[i * 4], 4, 1);
         if (nLoopKF == 0) {
             planes[i]->SetWorldPos(C4);
         } else {

@@ -23,8 +23,7 @@
 #include <utility>
 #include <vector>
 
-#include "../eao_fusion.h"
-#include "cv_compat.h"
+#include "adapter_detail.h"
 
 namespace eaofusion {
 
@@ -52,30 +51,16 @@ struct Sim3Walk {
     }
 };
 
-namespace sim3_detail {
-template <class M> inline void pose_of(const M& R, const M& t, std::vector<float>& T) {   // GetRotation() / GetTranslation() -> row-major 4x4
-    T.assign(16, 0.f);
-    for (int r = 0; r < 3; r++) {
-        for (int c = 0; c < 3; c++) T[r * 4 + c] = R.template at<float>(r, c);
-        T[r * 4 + 3] = t.template at<float>(r);
-    }
-    T[15] = 1.f;
-}
-template <class M> inline void intrinsics_of(const M& K, float* out) {
-    out[0] = K.template at<float>(0, 0); out[1] = K.template at<float>(1, 1);
-    out[2] = K.template at<float>(0, 2); out[3] = K.template at<float>(1, 2);
-}
-}  // namespace sim3_detail
-
 // The host walk of src/Optimizer.cc:1486-1561: a correspondence gets an edge pair when vpMatches1[i] and GetMapPointMatches()[i] are both
 // set, neither isBad(), and pMP2->GetIndexInKeyFrame(pKF2) >= 0; every other entry is skipped and left as it is.
 template <class MapPointT, class KeyFrameT, class Sim3T>
 Sim3Walk WalkSim3(KeyFrameT* pKF1, KeyFrameT* pKF2, const std::vector<MapPointT*>& vpMatches1, const Sim3T& g2oS12, float th2, bool bFixScale) {
     Sim3Walk w;
-    sim3_detail::intrinsics_of(pKF1->mK, w.K1);
-    sim3_detail::intrinsics_of(pKF2->mK, w.K2);
-    sim3_detail::pose_of(pKF1->GetRotation(), pKF1->GetTranslation(), w.T1w);
-    sim3_detail::pose_of(pKF2->GetRotation(), pKF2->GetTranslation(), w.T2w);
+    detail::read_intrinsics(pKF1->mK, w.K1);
+    detail::read_intrinsics(pKF2->mK, w.K2);
+    w.T1w.resize(16); w.T2w.resize(16);
+    detail::read_pose(pKF1->GetRotation(), pKF1->GetTranslation(), w.T1w.data());
+    detail::read_pose(pKF2->GetRotation(), pKF2->GetTranslation(), w.T2w.data());
     w.q[0] = g2oS12.rotation().x(); w.q[1] = g2oS12.rotation().y(); w.q[2] = g2oS12.rotation().z(); w.q[3] = g2oS12.rotation().w();
     for (int k = 0; k < 3; k++) w.t[k] = g2oS12.translation()[k];
     w.s = g2oS12.scale();
@@ -90,9 +75,8 @@ Sim3Walk WalkSim3(KeyFrameT* pKF1, KeyFrameT* pKF2, const std::vector<MapPointT*
         const int i2 = pMP2->GetIndexInKeyFrame(pKF2);
         if (!pMP1 || !pMP2) continue;
         if (pMP1->isBad() || pMP2->isBad() || i2 < 0) continue;
-        const auto P1 = pMP1->GetWorldPos();
-        const auto P2 = pMP2->GetWorldPos();
-        for (int k = 0; k < 3; k++) { w.Xw1.push_back(P1.template at<float>(k)); w.Xw2.push_back(P2.template at<float>(k)); }
+        detail::push3(pMP1->GetWorldPos(), w.Xw1);
+        detail::push3(pMP2->GetWorldPos(), w.Xw2);
         const auto& kp1 = pKF1->mvKeysUn[i];
         const auto& kp2 = pKF2->mvKeysUn[i2];
         w.obs1.push_back(kp1.pt.x); w.obs1.push_back(kp1.pt.y);
@@ -120,8 +104,7 @@ int OptimizeSim3(KeyFrameT* pKF1, KeyFrameT* pKF2, std::vector<MapPointT*>& vpMa
     std::vector<uint8_t> removed(w.index.size() + 1, 0);
     eao_sim3_result r;
     r.removed = removed.data();
-    const eao_status st = eao_optimize_sim3(&p, &r);
-    if (st != EAO_OK) throw std::runtime_error(std::string("eao_optimize_sim3: ") + eao_last_error());
+    detail::check(eao_optimize_sim3(&p, &r), "eao_optimize_sim3");
     for (size_t k = 0; k < w.index.size(); k++)
         if (removed[k]) vpMatches1[w.index[k]] = static_cast<MapPointT*>(nullptr);
     if (r.early_exit) return 0;

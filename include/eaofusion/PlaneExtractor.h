@@ -25,8 +25,7 @@
 #include <type_traits>
 #include <vector>
 
-#include "../eao_fusion.h"
-#include "cv_compat.h"
+#include "adapter_detail.h"
 
 namespace eaofusion {
 
@@ -45,11 +44,11 @@ public:
         if (imDepth.empty() || imDepth.type() != CV_32F) throw std::runtime_error("PlaneExtractor: imDepth must be a CV_32F image");
         ready(imDepth.cols, imDepth.rows, F.fx, F.fy, F.cx, F.cy);
         mHaveFrame = false;
-        check(eao_plane_seg_run(mHandle, imDepth.ptr<float>(0), (int32_t)(imDepth.step / sizeof(float))), "eao_plane_seg_run");
+        detail::check(eao_plane_seg_run(mHandle, imDepth.ptr<float>(0), (int32_t)(imDepth.step / sizeof(float))), "eao_plane_seg_run");
         int32_t n = 0;
-        check(eao_plane_seg_planes(mHandle, 0, nullptr, &n), "eao_plane_seg_planes");
+        detail::check(eao_plane_seg_planes(mHandle, 0, nullptr, &n), "eao_plane_seg_planes");
         std::vector<eao_plane_seg_plane> planes((size_t)n);
-        if (n > 0) check(eao_plane_seg_planes(mHandle, n, planes.data(), &n), "eao_plane_seg_planes");
+        if (n > 0) detail::check(eao_plane_seg_planes(mHandle, n, planes.data(), &n), "eao_plane_seg_planes");
         F.plane_num_ = (int)n;      // :410
         mKept.clear();
         std::vector<float> xyz;
@@ -57,15 +56,14 @@ public:
             if (!planes[i].kept) continue;      // :447-450
             xyz.resize((size_t)planes[i].cloud_count * 3);
             int32_t m = 0;
-            check(eao_plane_seg_cloud(mHandle, i, planes[i].cloud_count, xyz.data(), &m), "eao_plane_seg_cloud");
+            detail::check(eao_plane_seg_cloud(mHandle, i, planes[i].cloud_count, xyz.data(), &m), "eao_plane_seg_cloud");
             typename std::remove_reference<decltype(F.mvBoundaryPoints)>::type::value_type cloud;
             for (int32_t k = 0; k < m; k++) {
                 typename std::remove_reference<decltype(cloud.points)>::type::value_type p = {};
                 p.x = xyz[3 * (size_t)k]; p.y = xyz[3 * (size_t)k + 1]; p.z = xyz[3 * (size_t)k + 2];
                 cloud.points.push_back(p);
             }
-            cv::Mat coef(4, 1, CV_32F);
-            for (int k = 0; k < 4; k++) coef.at<float>(k, 0) = planes[i].coef[k];
+            const cv::Mat coef = detail::mat_of(planes[i].coef, 4, 1);
             F.mvBoundaryPoints.push_back(cloud);      // :453-455
             F.mvPlanePoints.push_back(cloud);
             F.mvPlaneCoefficients.push_back(coef);
@@ -80,29 +78,21 @@ public:
     template <class MapPlanesT_, class MapPlaneT>
     void Constructed(MapPlanesT_& planes, MapPlaneT* pMP, uint64_t frameId, int idx, const cv::Mat& Tcw) {
         float w[4], T[16];
-        const cv::Mat pos = pMP->GetWorldPos();
-        for (int i = 0; i < 4; i++) w[i] = pos.at<float>(i, 0);
-        mat4(Tcw, T);
-        check(eao_plane_map_add_from_seg(planes.handle(), (uint64_t)pMP->mnId, w, mHandle, segPlane(frameId, idx), T), "eao_plane_map_add_from_seg");
+        detail::read4(pMP->GetWorldPos(), w);
+        detail::read44(Tcw, T);
+        detail::check(eao_plane_map_add_from_seg(planes.handle(), (uint64_t)pMP->mnId, w, mHandle, segPlane(frameId, idx), T), "eao_plane_map_add_from_seg");
     }
     // MapPlane::UpdateBoundary (src/MapPlane.cc:150-153): in place of planes.BoundaryUpdated(pMP, F, id)
     template <class MapPlanesT_, class MapPlaneT>
     void BoundaryUpdated(MapPlanesT_& planes, MapPlaneT* pMP, uint64_t frameId, int idx, const cv::Mat& Tcw) {
         float T[16];
-        mat4(Tcw, T);
-        check(eao_plane_map_update_boundary_from_seg(planes.handle(), (uint64_t)pMP->mnId, mHandle, segPlane(frameId, idx), T), "eao_plane_map_update_boundary_from_seg");
+        detail::read44(Tcw, T);
+        detail::check(eao_plane_map_update_boundary_from_seg(planes.handle(), (uint64_t)pMP->mnId, mHandle, segPlane(frameId, idx), T), "eao_plane_map_update_boundary_from_seg");
     }
     // true while the handle still holds the clouds of frame frameId
     bool Holds(uint64_t frameId) const { return mHaveFrame && mFrameId == frameId; }
 
 private:
-    static void check(eao_status st, const char* what) {
-        if (st != EAO_OK) throw std::runtime_error(std::string(what) + ": " + eao_last_error());
-    }
-    static void mat4(const cv::Mat& m, float out[16]) {
-        for (int i = 0; i < 4; i++)
-            for (int j = 0; j < 4; j++) out[i * 4 + j] = m.at<float>(i, j);
-    }
     // frame plane idx (an index into the frame's mvBoundaryPoints as this extractor filled it) -> the plane of the handle's table
     int32_t segPlane(uint64_t frameId, int idx) const {
         if (!Holds(frameId)) throw std::runtime_error("PlaneExtractor: the handle no longer holds that frame's clouds");
@@ -115,7 +105,7 @@ private:
         eao_plane_seg_cfg cfg;
         eao_plane_seg_cfg_default(&cfg, width, height, fx, fy, cx, cy);      // PlaneFitter() and ParamSet() as written: plane_filter is never configured upstream
         eao_plane_seg* h = nullptr;
-        check(eao_plane_seg_create(&cfg, &h), "eao_plane_seg_create");
+        detail::check(eao_plane_seg_create(&cfg, &h), "eao_plane_seg_create");
         if (mHandle) eao_plane_seg_destroy(mHandle);
         mHandle = h;
         mCfg = cfg;

@@ -16,9 +16,8 @@
 // The draw stream.  iterate draws all min_set * passes indices FIRST, through the draw source Sim3SolverT uses, and makes one library call.  When that call
 // returns at chunk position k, the draws of the rest of the chunk have been consumed; upstream would not have made them (Sim3Solver.h).
 //
-// The sampling loop is restated WITH its quirk: vAvailableIndices[idx] = vAvailableIndices.back() uses the drawn VALUE idx, not the drawn position randi
-// (:199), so a set with a repeated index is reachable upstream and here.  Where idx is past the shrunken size upstream's write lands in the vector's spare
-// capacity and is never read; the buffer below keeps its capacity N, so that write stays in bounds.
+// The sampling loop is restated WITH its quirk (detail::draw_sets, adapter_detail.h): vAvailableIndices[idx] = vAvailableIndices.back() uses the drawn VALUE
+// idx, not the drawn position randi (:199), so a set with a repeated index is reachable upstream and here.
 //
 // SetRansacParameters is restated as written, with the float / int conversions of :134-152.  One guard: with N < mRansacMinInliers the epsilon exceeds 1, the
 // logarithm is a NaN and its conversion to int is undefined upstream; iterate leaves through N < mRansacMinInliers before the value matters.  Here a value
@@ -33,8 +32,7 @@
 #include <string>
 #include <vector>
 
-#include "../eao_fusion.h"
-#include "cv_compat.h"
+#include "adapter_detail.h"
 
 namespace eaofusion {
 
@@ -53,8 +51,7 @@ public:
                     mvP2D.push_back(kp.pt.x);
                     mvP2D.push_back(kp.pt.y);
                     mvSigma2.push_back(F.mvLevelSigma2[kp.octave]);
-                    const auto Pos = pMP->GetWorldPos();
-                    for (int k = 0; k < 3; k++) mvP3Dw.push_back(Pos.template at<float>(k));
+                    detail::push3(pMP->GetWorldPos(), mvP3Dw);
                     mvKeyPointIndices.push_back(i);
                 }
             }
@@ -111,8 +108,7 @@ public:
         std::vector<uint8_t> inlier((size_t)N + 1, 0);
         eao_pnp_solver_result r = eao_pnp_solver_result();
         r.inlier = inlier.data();
-        const eao_status st = eao_pnp_solver_iterate(&p, mRansacMinInliers, mRansacMaxIts, mRansacMinSet, &mState, sets.data(), nHyp, &r);
-        if (st != EAO_OK) throw std::runtime_error(std::string("eao_pnp_solver_iterate: ") + eao_last_error());
+        detail::check(eao_pnp_solver_iterate(&p, mRansacMinInliers, mRansacMaxIts, mRansacMinSet, &mState, sets.data(), nHyp, &r), "eao_pnp_solver_iterate");
         return collect(r, inlier, bNoMore, vbInliers, nInliers);
     }
 
@@ -121,18 +117,7 @@ public:
     int draw(int nIterations, std::vector<int32_t>& sets) {
         const int nHyp = std::max(nIterations, mRansacMaxIts - mState.iterations);      // the || of :182
         sets.assign((size_t)std::max(nHyp, 0) * mRansacMinSet, 0);
-        std::vector<size_t> vAvailableIndices((size_t)N);
-        for (int h = 0; h < nHyp; h++) {
-            for (int i = 0; i < N; i++) vAvailableIndices[i] = (size_t)i;      // = mvAllIndices
-            size_t size = (size_t)N;
-            for (short i = 0; i < mRansacMinSet; ++i) {
-                const int randi = RandomT::RandomInt(0, (int)size - 1);
-                const int idx = (int)vAvailableIndices[randi];
-                sets[(size_t)h * mRansacMinSet + i] = idx;
-                vAvailableIndices[idx] = vAvailableIndices[size - 1];           // the drawn VALUE as position: upstream's quirk, kept
-                size--;
-            }
-        }
+        detail::draw_sets<RandomT>(N, mRansacMinSet, nHyp, sets.data());
         return std::max(nHyp, 0);
     }
     cv::Mat collect(const eao_pnp_solver_result& r, const std::vector<uint8_t>& inlier, bool& bNoMore, std::vector<bool>& vbInliers, int& nInliers) {
@@ -144,10 +129,7 @@ public:
         vbInliers = std::vector<bool>(mnMatches, false);
         for (int i = 0; i < N; i++)
             if (inlier[i]) vbInliers[mvKeyPointIndices[i]] = true;
-        cv::Mat m(4, 4, CV_32F);
-        for (int a = 0; a < 4; a++)
-            for (int b = 0; b < 4; b++) m.at<float>(a, b) = r.Tcw[a * 4 + b];
-        return m;
+        return detail::mat_of(r.Tcw, 4, 4);
     }
     eao_pnp_solver_problem problem() const {
         eao_pnp_solver_problem p;

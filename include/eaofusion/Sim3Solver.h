@@ -17,10 +17,9 @@
 // count of the host loop back; it is not offered.  The note of OptimizerSim3.h on running ComputeSim3's candidates together stays true: the
 // round-robin over candidates is the caller's (src/LoopClosing.cc:286-311), one iterate(5) per candidate and round.
 //
-// The sampling loop is restated WITH its quirk: upstream writes vAvailableIndices[idx] = back() with idx the drawn VALUE, not the drawn
-// position randi.  After the first draw position a holds N-1; drawing position a again yields N-1, and a third time N-1 again -- triples
-// with a repeated index are reachable upstream and here.  The buffer below keeps its capacity N, so the write that lands one past the
-// shrunken size upstream stays in bounds.
+// The sampling loop is restated WITH its quirk (detail::draw_sets, adapter_detail.h): upstream writes vAvailableIndices[idx] = back() with
+// idx the drawn VALUE, not the drawn position randi.  After the first draw position a holds N-1; drawing position a again yields N-1, and
+// a third time N-1 again -- triples with a repeated index are reachable upstream and here.
 #pragma once
 
 #include <algorithm>
@@ -30,8 +29,7 @@
 #include <string>
 #include <vector>
 
-#include "../eao_fusion.h"
-#include "cv_compat.h"
+#include "adapter_detail.h"
 
 namespace eaofusion {
 
@@ -46,8 +44,9 @@ public:
         mpKF2 = pKF2;
         const std::vector<MapPointT*> vpKeyFrameMP1 = pKF1->GetMapPointMatches();
         mN1 = (int)vpMatched12.size();
-        pose_of(pKF1->GetRotation(), pKF1->GetTranslation(), mT1w);
-        pose_of(pKF2->GetRotation(), pKF2->GetTranslation(), mT2w);
+        mT1w.resize(16); mT2w.resize(16);
+        detail::read_pose(pKF1->GetRotation(), pKF1->GetTranslation(), mT1w.data());
+        detail::read_pose(pKF2->GetRotation(), pKF2->GetTranslation(), mT2w.data());
         for (int i1 = 0; i1 < mN1; i1++) {
             if (!vpMatched12[i1]) continue;
             MapPointT* pMP1 = vpKeyFrameMP1[i1];
@@ -62,12 +61,11 @@ public:
             mvSigma2_1.push_back(pKF1->mvLevelSigma2[kp1.octave]);
             mvSigma2_2.push_back(pKF2->mvLevelSigma2[kp2.octave]);
             mvnIndices1.push_back((size_t)i1);
-            const auto X3D1w = pMP1->GetWorldPos();
-            const auto X3D2w = pMP2->GetWorldPos();
-            for (int k = 0; k < 3; k++) { mvXw1.push_back(X3D1w.template at<float>(k)); mvXw2.push_back(X3D2w.template at<float>(k)); }
+            detail::push3(pMP1->GetWorldPos(), mvXw1);
+            detail::push3(pMP2->GetWorldPos(), mvXw2);
         }
-        intrinsics_of(pKF1->mK, mK1);
-        intrinsics_of(pKF2->mK, mK2);
+        detail::read_intrinsics(pKF1->mK, mK1);
+        detail::read_intrinsics(pKF2->mK, mK2);
         SetRansacParameters();
     }
 
@@ -103,34 +101,22 @@ public:
         // every draw of the chunk first (see the header comment), then one call
         const int nHyp = std::max(0, std::min(nIterations, mRansacMaxIts - mState.iterations));
         std::vector<int32_t> triples((size_t)nHyp * 3);
-        std::vector<size_t> vAvailableIndices((size_t)N);
-        for (int h = 0; h < nHyp; h++) {
-            for (int i = 0; i < N; i++) vAvailableIndices[i] = (size_t)i;      // = mvAllIndices
-            size_t size = (size_t)N;
-            for (short i = 0; i < 3; ++i) {
-                const int randi = RandomT::RandomInt(0, (int)size - 1);
-                const int idx = (int)vAvailableIndices[randi];
-                triples[(size_t)h * 3 + i] = idx;
-                vAvailableIndices[idx] = vAvailableIndices[size - 1];           // the drawn VALUE as position: upstream's quirk, kept
-                size--;
-            }
-        }
+        detail::draw_sets<RandomT>(N, 3, nHyp, triples.data());
         const eao_sim3_solver_problem p = problem();
         std::vector<uint8_t> inlier((size_t)N + 1, 0);
         eao_sim3_solver_result r = eao_sim3_solver_result();
         r.inlier = inlier.data();
-        const eao_status st = eao_sim3_solver_iterate(&p, mRansacMinInliers, mRansacMaxIts, &mState, triples.data(), nHyp, &r);
-        if (st != EAO_OK) throw std::runtime_error(std::string("eao_sim3_solver_iterate: ") + eao_last_error());
+        detail::check(eao_sim3_solver_iterate(&p, mRansacMinInliers, mRansacMaxIts, &mState, triples.data(), nHyp, &r), "eao_sim3_solver_iterate");
         bNoMore = r.no_more != 0;
         if (r.returned < 0) return cv::Mat();
         nInliers = r.n_inliers;
         for (int i = 0; i < N; i++)
             if (inlier[i]) vbInliers[mvnIndices1[i]] = true;
-        return mat_of(r.T12, 4, 4);
+        return detail::mat_of(r.T12, 4, 4);
     }
 
-    cv::Mat GetEstimatedRotation() { return mat_of(mState.best_R, 3, 3); }
-    cv::Mat GetEstimatedTranslation() { return mat_of(mState.best_t, 3, 1); }
+    cv::Mat GetEstimatedRotation() { return detail::mat_of(mState.best_R, 3, 3); }
+    cv::Mat GetEstimatedTranslation() { return detail::mat_of(mState.best_t, 3, 1); }
     float GetEstimatedScale() { return mState.best_s; }
 
     // what the flattened problem holds (not part of the reference's interface)
@@ -149,25 +135,6 @@ public:
     int Iterations() const { return mState.iterations; }
 
 protected:
-    template <class M> static void pose_of(const M& R, const M& t, std::vector<float>& T) {   // GetRotation() / GetTranslation() -> row-major 4x4
-        T.assign(16, 0.f);
-        for (int r = 0; r < 3; r++) {
-            for (int c = 0; c < 3; c++) T[r * 4 + c] = R.template at<float>(r, c);
-            T[r * 4 + 3] = t.template at<float>(r);
-        }
-        T[15] = 1.f;
-    }
-    template <class M> static void intrinsics_of(const M& K, float* out) {
-        out[0] = K.template at<float>(0, 0); out[1] = K.template at<float>(1, 1);
-        out[2] = K.template at<float>(0, 2); out[3] = K.template at<float>(1, 2);
-    }
-    static cv::Mat mat_of(const float* v, int rows, int cols) {
-        cv::Mat m(rows, cols, CV_32F);
-        for (int r = 0; r < rows; r++)
-            for (int c = 0; c < cols; c++) m.at<float>(r, c) = v[r * cols + c];
-        return m;
-    }
-
     KeyFrameT* mpKF1;
     KeyFrameT* mpKF2;
     std::vector<float> mT1w, mT2w, mvXw1, mvXw2, mvSigma2_1, mvSigma2_2;

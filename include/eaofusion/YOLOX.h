@@ -35,7 +35,7 @@
 #include <thread>
 #include <vector>
 
-#include "../eao_fusion.h"
+#include "adapter_detail.h"
 #include "../../eao_fusion_amd/csrc/yolox_internal.h"
 
 namespace eaofusion {
@@ -62,7 +62,7 @@ public:
 
     explicit YOLOX(yolox::Infer infer, const eao_yolox_cfg* cfg = nullptr, bool rgb = false) : infer_(std::move(infer)), rgb_(rgb) {
         if (cfg) cfg_ = *cfg; else eao_yolox_cfg_default(&cfg_);
-        if (eao_yolox_create(&cfg_, &h_) != EAO_OK) throw std::runtime_error(std::string("eao_yolox_create: ") + eao_last_error());
+        detail::check(eao_yolox_create(&cfg_, &h_), "eao_yolox_create");
         eao_yolox_buffers(h_, &dBlob_, &dProb_, &stream_);
         raw_.resize((size_t)cfg_.max_proposals);
     }

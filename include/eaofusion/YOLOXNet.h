@@ -16,14 +16,17 @@
 #include <string>
 
 #include "YOLOX.h"
+#include "adapter_detail.h"
 
 namespace eaofusion {
 
 class DetNet {
 public:
     DetNet(const std::string& path, int input_size, int max_batch = 1) {
-        if (eao_detnet_create_from_file(path.c_str(), input_size, max_batch, &h_) != EAO_OK) throw std::runtime_error(std::string("eao_detnet_create_from_file: ") + eao_last_error());
-        if (eao_detnet_info(h_, &desc_) != EAO_OK) { eao_detnet_destroy(h_); throw std::runtime_error(std::string("eao_detnet_info: ") + eao_last_error()); }
+        detail::check(eao_detnet_create_from_file(path.c_str(), input_size, max_batch, &h_), "eao_detnet_create_from_file");
+        const eao_status st = eao_detnet_info(h_, &desc_);
+        if (st != EAO_OK) eao_detnet_destroy(h_);      // (no destructor runs when a constructor throws)
+        detail::check(st, "eao_detnet_info");
     }
     ~DetNet() { eao_detnet_destroy(h_); }
     DetNet(const DetNet&) = delete;
@@ -32,7 +35,7 @@ public:
     // DoInference (:331-367) without its copies: one frame from d_blob to d_prob on `stream`.  A refused call throws: the detector would otherwise decode a stale head.
     yolox::Infer infer() {
         return [this](const float* d_blob, float* d_prob, void* stream) {
-            if (eao_detnet_forward(h_, d_blob, d_prob, 1, stream) != EAO_OK) throw std::runtime_error(std::string("eao_detnet_forward: ") + eao_last_error());
+            detail::check(eao_detnet_forward(h_, d_blob, d_prob, 1, stream), "eao_detnet_forward");
         };
     }
     const eao_detnet_desc& info() const { return desc_; }
