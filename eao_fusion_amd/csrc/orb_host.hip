@@ -174,7 +174,8 @@ eao_status build_geometry(eao_orb* h, int W, int H) {
     g.fastStride = maxSw + 3 <= 48 ? 48 : kTileStrideWide;
     g.fastTileBytes = ((maxSh * g.fastStride) + 15) & ~15;
     g.fastLdsBytes = g.fastTileBytes + ((2 * g.fastMaxTested + 15) & ~15) + ((((maxSw - 4) * (maxSh - 4)) + 15) & ~15) + 64;
-    // k_quadtree dynamic LDS: 2 short4 + 2 cnt + 2 crk + 4 childcnt + 4 childpos + newpos/order/vlist/procRank/scanB per entry + scanA
+    // k_quadtree dynamic LDS: 2 short4 + 2 cnt + 2 crk + 2 mid + 2 x 4 childcnt (this pass's histogram and the next one's, filled while this one's
+    // childpos is read) + 4 childpos + order/vlist/procRank/scanB per entry + scanA
     h->quadLds = (size_t)maxList * (2 * sizeof(short4) + sizeof(int) * kQtNodeInts) + (size_t)scanCap * sizeof(int);
     g.qtNodesGlobal = 0; g.qtNodeFrameBytes = 0;
     if (h->quadLds > 100 * 1024) {   // (thousands of features on one level: upstream takes any N, src/ORBextractor.cc:539)
@@ -726,7 +727,7 @@ eao_status eao_orb_last_timing(eao_orb* h, float ms[6]) {
         EAO_HIP(hipMemcpy(st, h->d_dbg, sizeof(st), hipMemcpyDeviceToHost));
         for (int l = 0; l < h->geom.nlevels; l++) {
             const long long* o = st + 16 * l;
-            fprintf(stderr, "[eao quadtree stamps] level %d: M %lld S %lld passes %lld | setup %lld | multi-scan %lld hist %lld order %lld growth %lld rank %lld newlist %lld rehome %lld tail %lld | final %lld cycles\n",
+            fprintf(stderr, "[eao quadtree stamps] level %d: M %lld S %lld passes %lld | setup %lld | multi-scan %lld hist(initial) %lld order %lld growth %lld rank %lld newlist %lld rehome+hist %lld tail %lld | final %lld cycles\n",
                     l, o[10], o[11], o[9], o[0], o[1], o[2], o[3], o[4], o[5], o[6], o[7], 0LL, o[8]);
         }
     }

@@ -102,7 +102,7 @@ struct PyrArgs {
 // dearer: 1024 threads are faster while the launch is latency-bound (one frame: device step 0.124 -> 0.105 ms, eight frames 0.143 ->
 // 0.129), 256 when many workgroups compete for the CUs (64 frames: 0.323 vs 0.339 ms).
 constexpr int kQTSmall = 1024, kQTLarge = 256;
-constexpr int kQtNodeInts = 2 + 2 + 2 + 4 + 4 + 5;   // per list entry next to its two boxes: cnt, crk, mid (x2 each), childcnt, childpos (x4), five work arrays
+constexpr int kQtNodeInts = 2 + 2 + 2 + 8 + 4 + 4;   // per list entry next to its two boxes: cnt, crk, mid (x2 each), childcnt (x4, twice), childpos (x4), four work arrays
 
 constexpr size_t kProfEvents = 10;
 

@@ -84,10 +84,77 @@ __device__ __forceinline__ int quadrant(unsigned key, short4 bx) {
     return (x < mx ? 0 : 1) + (y < my ? 0 : 2);
 }
 
+// The one sweep of a pass over the M candidates, by the whole workgroup: every candidate moves to the list position that
+// wave 0 has just laid out for its child (childpos, split point of the OLD entry in mid) and, when another pass follows
+// (`count`, uniform), is counted in the NEXT pass's child histogram under the split point of its new entry (nmid; cc zeroed
+// by the caller, complete at the caller's barrier).  The sweep that re-homed in pass i and the one that histogrammed in pass
+// i + 1 walked the same candidates with the same key, and the second looked up the node the first had just stored.
+// The candidates are in spatial order (cells row-major, corners row-major inside a cell), so neighbouring lanes mostly
+// hit the same (node, quadrant) bin: one LDS atomic per RUN of equal bins in the wave instead of one per candidate
+// (while the tree is shallow, thousands of atomics would otherwise queue on a handful of words).
+// (FOUR rows of kQT candidates per trip: every link of the chain node -> split point -> new node -> its split point is fetched for
+//  all four before any of them is used -- as one row per trip a sweep was a chain of dependent LDS reads and an atomic, twelve times over for level 0)
+// With one wave per SIMD a sweep is bound by that wave's own instruction stream (profiles/orb_quadtree_sweep_ab.txt): what counts is the
+// number of instructions per candidate and that the four rows' loads really are in flight together.
+// One trip of the sweep: rows k0, k0 + kQT, .. of kNR <= 4 rows.  Only the last row of a trip that is not kFull may end inside the row.
+template <int kQT, int kNR, bool kFull, class KeyPtr, class NofPtr>
+__device__ __forceinline__ void rehome_and_count_rows(KeyPtr keys, NofPtr nof, int M, int k0, const unsigned* mid, const int* childpos, const unsigned* nmid, int* cc, bool count) {
+    const int t = threadIdx.x, lane = t & 63;
+    // (No load of the chain is conditional: a lane past the last candidate reads the last one's key and node, and entry 0 in the place of
+    //  whatever that gives it -- every address stays inside its array, whatever another wave has stored to nof[M - 1] by then -- and
+    //  neither stores nor counts.  Behind `k < M ? load : x` every load sat in a branch of its own with a full wait in front of it.)
+    int nd[kNR], bin[kNR];
+    unsigned ky[kNR], md[kNR];
+    bool in[kNR];
+#pragma unroll
+    for (int u = 0; u < kNR; u++) {
+        const int k = k0 + u * kQT + t;
+        in[u] = kFull || u < kNR - 1 || k < M;
+        const int kk = in[u] ? k : M - 1;
+        const int n = (int)nof[kk];
+        ky[u] = keys[kk];
+        nd[u] = in[u] ? n : 0;
+    }
+#pragma unroll
+    for (int u = 0; u < kNR; u++) md[u] = mid[nd[u]];
+#pragma unroll
+    for (int u = 0; u < kNR; u++) { const int n = childpos[4 * nd[u] + quadrant_mid(ky[u], md[u])]; nd[u] = in[u] ? n : 0; }
+#pragma unroll
+    for (int u = 0; u < kNR; u++) { const int k = k0 + u * kQT + t; if (in[u]) nof[k] = (unsigned short)nd[u]; }
+    if (!count) return;                            // (uniform: the tree has ended, the best-response step needs the nodes alone)
+#pragma unroll
+    for (int u = 0; u < kNR; u++) md[u] = nmid[nd[u]];
+#pragma unroll
+    for (int u = 0; u < kNR; u++) bin[u] = in[u] && md[u] != kQtLeaf ? 4 * nd[u] + quadrant_mid(ky[u], md[u]) : -1;
+#pragma unroll
+    for (int u = 0; u < kNR; u++) {
+        const int prev = __builtin_amdgcn_update_dpp(-2, bin[u], 0x138, 0xF, 0xF, false);   // wave_shr:1 (lane 0 keeps -2): VALU, not the LDS crossbar
+        const bool head = bin[u] != prev;
+        const unsigned long long hm = __ballot(head);
+        if (head && bin[u] >= 0) {
+            const unsigned long long rest = lane == 63 ? 0ull : (hm >> (lane + 1));
+            const int run = rest ? __ffsll((long long)rest) : 64 - lane;
+            atomicAdd(&cc[bin[u]], run);
+        }
+    }
+}
+
+template <int kQT, class KeyPtr, class NofPtr>
+__device__ __forceinline__ void rehome_and_count(KeyPtr keys, NofPtr nof, int M, const unsigned* mid, const int* childpos, const unsigned* nmid, int* cc, bool count) {
+    int k0 = 0;
+    for (; k0 + 4 * kQT <= M; k0 += 4 * kQT) rehome_and_count_rows<kQT, 4, true>(keys, nof, M, k0, mid, childpos, nmid, cc, count);
+    // the rest, fewer than four rows: as many rows as it has (level 0 of the benchmark frames: 3095 candidates, 23 of them in a fourth trip of 256 x 4)
+    const int rest = M - k0;
+    if (rest > 3 * kQT) rehome_and_count_rows<kQT, 4, false>(keys, nof, M, k0, mid, childpos, nmid, cc, count);
+    else if (rest > 2 * kQT) rehome_and_count_rows<kQT, 3, false>(keys, nof, M, k0, mid, childpos, nmid, cc, count);
+    else if (rest > kQT) rehome_and_count_rows<kQT, 2, false>(keys, nof, M, k0, mid, childpos, nmid, cc, count);
+    else if (rest > 0) rehome_and_count_rows<kQT, 1, false>(keys, nof, M, k0, mid, childpos, nmid, cc, count);
+}
+
 // One workgroup per (level, frame).  List entries are (box, count, creation rank); `nodeof[k]` is the list
-// position of candidate k's node.  Every pass (a) histograms children of all multi-key nodes, (b) picks the set
-// of nodes that upstream would split in this pass and their processing order, (c) lays out the new list exactly
-// as upstream's push_front/erase sequence would leave it.
+// position of candidate k's node.  Every pass (a) picks, from the child histograms of all multi-key nodes, the set
+// of nodes that upstream would split in this pass and their processing order, (b) lays out the new list exactly
+// as upstream's push_front/erase sequence would leave it, (c) moves the candidates and histograms the next pass's children.
 struct QtArgs {
     const Geom* g; const unsigned* cellcand; const int* cellcnt; unsigned* levelkps; int* levelcnt; int f, l, M;
     long long* dbg;
@@ -120,30 +187,53 @@ __device__ __forceinline__ void quadtree_body(const QtArgs& A, unsigned char* sm
     int* crk1 = crk0 + LC;
     unsigned* mid0 = reinterpret_cast<unsigned*>(crk1 + LC);   // split point of a multi-key entry (mx | my << 16), kQtLeaf otherwise
     unsigned* mid1 = mid0 + LC;
-    int* childcnt = reinterpret_cast<int*>(mid1 + LC);          // 4 per entry
-    int* childpos = childcnt + 4 * LC;  // 4 per entry
+    int* childcnt0 = reinterpret_cast<int*>(mid1 + LC);         // 4 per entry, twice: the sweep of a pass fills the next pass's histogram while this pass's childpos is read
+    int* childcnt1 = childcnt0 + 4 * LC;
+    int* childpos = childcnt1 + 4 * LC; // 4 per entry
     unsigned long long* rkey = reinterpret_cast<unsigned long long*>(childpos);   // sort keys of a careful pass (before childpos is filled)
-    int* newpos = childpos + 4 * LC;
-    int* order = newpos + LC;
+    int* order = childpos + 4 * LC;
     int* vlist = order + LC;
     int* procRank = vlist + LC;
     int* scanB = procRank + LC;
     int* scanA = scanB + LC;            // g->scanCap entries (>= LC and >= nCells); holds the exclusive cell prefix on entry
 
-    // ---- gather this level's candidates in upstream order: cells row-major, corners row-major inside a cell.  One
-    // thread per cell, sixteen independent loads in flight (a cell holds a handful of corners).
+    // ---- gather this level's candidates in upstream order: cells row-major, corners row-major inside a cell.  Sixteen
+    // lanes to a cell, each with corners j and j + 16 of eight cells in flight (a cell of the benchmark frames holds ~11 corners,
+    // few more than 32): a load instruction reads 64-byte pieces of four cells' rows, and the loads of 128 cells (256 threads) wait
+    // together.  (As one thread per cell a load instruction touched 64 cache lines for 64 words, sixteen times over, and the 280
+    // cells of level 0 took two rounds of it.)
     const long long cslot = (long long)f * g->totalCells + L.cellBase;
-    for (int c = t; c < L.nCells; c += kQT) {
-        const int o = scanA[c], n = (c + 1 < L.nCells ? scanA[c + 1] : M) - o;
-        const unsigned* srcc = A.cellcand + (cslot + c) * g->cellCap;
-        // (sixteen loads in flight: a cell of the benchmark frames holds ~11 corners, so one memory round trip instead of three)
-        for (int j0 = 0; j0 < n; j0 += 16) {
-            unsigned v[16];
+    {
+        constexpr int kGL = 16, kGC = 8, kGroups = kQT / kGL;
+        const int grp = t / kGL, gl = t % kGL;
+        const int cellCap = g->cellCap;
+        for (int c0 = 0; c0 < L.nCells; c0 += kGroups * kGC) {
+            int o[kGC], n[kGC];
+            unsigned va[kGC], vb[kGC];
 #pragma unroll
-            for (int u = 0; u < 16; u++) v[u] = srcc[min(j0 + u, n - 1)];
+            for (int u = 0; u < kGC; u++) {   // (a group past the last cell takes the last cell's row and stores nothing)
+                const int c = c0 + u * kGroups + grp, cc = min(c, L.nCells - 1);
+                o[u] = scanA[cc];
+                const int e = cc + 1 < L.nCells ? scanA[cc + 1] : M;
+                n[u] = c < L.nCells ? e - o[u] : 0;
+            }
 #pragma unroll
-            for (int u = 0; u < 16; u++)
-                if (j0 + u < n) { keys[o + j0 + u] = v[u]; A.candOut[o + j0 + u] = v[u]; }
+            for (int u = 0; u < kGC; u++) {   // (unconditional: a row holds cellCap words, whatever its count)
+                const unsigned* srcc = A.cellcand + (cslot + min(c0 + u * kGroups + grp, L.nCells - 1)) * cellCap;
+                va[u] = srcc[min(gl, cellCap - 1)];
+                vb[u] = srcc[min(gl + kGL, cellCap - 1)];
+            }
+#pragma unroll
+            for (int u = 0; u < kGC; u++) {
+                if (gl < n[u]) { keys[o[u] + gl] = va[u]; A.candOut[o[u] + gl] = va[u]; }
+                if (gl + kGL < n[u]) { keys[o[u] + gl + kGL] = vb[u]; A.candOut[o[u] + gl + kGL] = vb[u]; }
+            }
+#pragma unroll
+            for (int u = 0; u < kGC; u++) {   // (the rest of a crowded cell)
+                if (n[u] <= 2 * kGL) continue;
+                const unsigned* srcc = A.cellcand + (cslot + c0 + u * kGroups + grp) * cellCap;
+                for (int j = gl + 2 * kGL; j < n[u]; j += kGL) { const unsigned v = srcc[j]; keys[o[u] + j] = v; A.candOut[o[u] + j] = v; }
+            }
         }
     }
     __syncthreads();
@@ -153,8 +243,17 @@ __device__ __forceinline__ void quadtree_body(const QtArgs& A, unsigned char* sm
         box0[t] = make_short4((short)(int)(L.hX * (float)t), 0, (short)(int)(L.hX * (float)(t + 1)), (short)L.boxH);
         cnt0[t] = 0;
         crk0[t] = t;
+        // (the first sweep below moves the candidates like any pass's: from an "old" entry without a split point, whose every key
+        //  maps to quadrant 0, through childpos to the entry's place among the non-empty ones)
+        mid1[t] = kQtLeaf;
+        procRank[t] = -1;
+        childcnt0[4 * t] = 0; childcnt0[4 * t + 1] = 0; childcnt0[4 * t + 2] = 0; childcnt0[4 * t + 3] = 0;
     }
     __syncthreads();
+    if (nIni == 1) {   // (frames up to 3:2, the usual case: min((int)(x / hX), 0) is node 0 for every candidate -- no division, no count)
+        for (int k = t; k < M; k += kQT) nof[k] = 0;
+        if (t == 0) cnt0[0] = M;
+    } else
     for (int k0 = 0; k0 < M; k0 += kQT) {   // (every candidate lands in one of <= 16 nodes: count by ballot, not by 3000 atomics on one word)
         const int k = k0 + t;
         int ini = -1;
@@ -171,40 +270,36 @@ __device__ __forceinline__ void quadtree_body(const QtArgs& A, unsigned char* sm
     if (t == 0) {  // drop empty initial nodes (nIni <= 16)
         int S = 0;
         for (int i = 0; i < nIni; i++) {
-            newpos[i] = S;
+            childpos[4 * i] = S;
             if (cnt0[i] > 0) { box0[S] = box0[i]; cnt0[S] = cnt0[i]; crk0[S] = S; mid0[S] = cnt0[i] > 1 ? box_mid(box0[i]) : kQtLeaf; S++; }
         }
-        sh_S = S; sh_phase = 0; sh_done = 0;
+        sh_S = S; sh_phase = 0; sh_done = 0; sh_rstar = 0x7FFFFFFF; sh_nexp = 0;
     }
     __syncthreads();
-    if (nIni > 1) {
-        for (int k = t; k < M; k += kQT) nof[k] = (unsigned short)newpos[nof[k]];
-        __syncthreads();
-    }
-
     QSTAMP(0);
+    // (wave 0 alone rewrites sh_S / sh_phase / sh_done, behind the NEXT barrier: everyone takes its copies between the two)
+    int S = sh_S, phase = sh_phase, done = 0;
+    // the list is final only now, with the empty nodes dropped: the first pass's child histogram
+    rehome_and_count<kQT>(keys, nof, M, mid1, childpos, mid0, childcnt0, true);
+    __syncthreads();
+    QSTAMP(2);
+
     int diters = 0;
     short4* box = box0; short4* nbox = box1;
     unsigned* mid = mid0; unsigned* nmid = mid1;
     int* cnt = cnt0; int* ncnt = cnt1;
     int* crk = crk0; int* ncrk = crk1;
-    // Every pass: two sweeps over the M candidates by the whole workgroup (child histograms, re-homing) and, between them, the
-    // list logic over the S <= N nodes.  The list logic runs in WAVE 0 ALONE, wave-synchronously (DPP scans, wavefront-scope
-    // fences, no workgroup barrier): as a sequence of block-wide steps it was ~20 barriers per pass with a handful of
-    // instructions between them -- 43 k of level 0's 132 k cycles.  Four barriers per pass remain (six in a careful pass,
-    // whose O(n^2) ranking stays block-wide).
+    int* childcnt = childcnt0; int* nchildcnt = childcnt1;
+    // Every pass: the list logic over the S <= N nodes, then ONE sweep over the M candidates by the whole workgroup, which moves
+    // them to their new nodes and histograms the children of the next pass (rehome_and_count).  The list logic runs in WAVE 0
+    // ALONE, wave-synchronously (DPP scans, wavefront-scope fences, no workgroup barrier): as a sequence of block-wide steps it
+    // was ~20 barriers per pass with a handful of instructions between them -- 43 k of level 0's 132 k cycles.  Meanwhile the
+    // other waves zero the next histogram.  Two barriers per pass remain, one behind the list logic and one behind the sweep
+    // (four in a careful pass, whose O(n^2) ranking stays block-wide).
 #define QT_WAVE_FENCE() eao::wave_sync()
     const int wv = t >> 6;
-    for (int iter = 0; iter < 64 && !sh_done; iter++) {
-        const int S = sh_S, phase = sh_phase;
-        // (1) reset of the per-node scratch (everyone) ...
-        for (int i = t; i < S; i += kQT) {
-            procRank[i] = -1;
-            childcnt[4 * i] = 0; childcnt[4 * i + 1] = 0; childcnt[4 * i + 2] = 0; childcnt[4 * i + 3] = 0;
-        }
-        if (t == 0) { sh_rstar = 0x7FFFFFFF; sh_nexp = 0; }
-        __syncthreads();
-        // ... and the multi-key entries in list order (wave 0, beside the other waves' share of the histogram sweep)
+    for (int iter = 0; iter < 64 && !done; iter++) {
+        // (1) the multi-key entries in list order (childcnt of this pass is complete, procRank[0, S) is -1: the sweep before the barrier saw to both)
         int nCand = 0;
         if (wv == 0) {
             for (int i = lane; i < S; i += 64) scanA[i] = cnt[i] > 1 ? 1 : 0;
@@ -215,36 +310,6 @@ __device__ __forceinline__ void quadtree_body(const QtArgs& A, unsigned char* sm
             QT_WAVE_FENCE();
         }
         QSTAMP(1);
-        // (2) child histograms of every candidate
-        // The candidates are in spatial order (cells row-major, corners row-major inside a cell), so neighbouring lanes mostly
-        // hit the same (node, quadrant) bin: one LDS atomic per RUN of equal bins in the wave instead of one per candidate
-        // (while the tree is shallow, thousands of atomics would otherwise queue on a handful of words).
-        // (FOUR rows of kQT candidates per trip: node, key, split point of all four are fetched before any of them is used -- as one row
-        //  per trip the sweep was a chain of three dependent LDS reads and an atomic, twelve times over for level 0: 7 k cycles per pass)
-        for (int k0 = 0; k0 < M; k0 += 4 * kQT) {
-            int nd[4], bin[4];
-            unsigned ky[4], md[4];
-#pragma unroll
-            for (int u = 0; u < 4; u++) { const int k = k0 + u * kQT + t; nd[u] = k < M ? (int)nof[k] : -1; ky[u] = k < M ? keys[k] : 0u; }
-#pragma unroll
-            for (int u = 0; u < 4; u++) md[u] = nd[u] >= 0 ? mid[nd[u]] : kQtLeaf;
-#pragma unroll
-            for (int u = 0; u < 4; u++) bin[u] = md[u] != kQtLeaf ? 4 * nd[u] + quadrant_mid(ky[u], md[u]) : -1;
-#pragma unroll
-            for (int u = 0; u < 4; u++) {
-                if (k0 + u * kQT >= M) break;          // (uniform)
-                const int prev = __builtin_amdgcn_update_dpp(-2, bin[u], 0x138, 0xF, 0xF, false);   // wave_shr:1 (lane 0 keeps -2): VALU, not the LDS crossbar
-                const bool head = bin[u] != prev;
-                const unsigned long long hm = __ballot(head);
-                if (head && bin[u] >= 0) {
-                    const unsigned long long rest = lane == 63 ? 0ull : (hm >> (lane + 1));
-                    const int run = rest ? __ffsll((long long)rest) : 64 - lane;
-                    atomicAdd(&childcnt[bin[u]], run);
-                }
-            }
-        }
-        __syncthreads();
-        QSTAMP(2);
         // (3) processing order: list order (full pass) or (size, creation rank) descending (careful pass)
         if (phase == 1) {
             // rank by (size, creation rank) descending, block-wide: the two sort fields are packed into one 64-bit key per node
@@ -343,14 +408,18 @@ __device__ __forceinline__ void quadtree_body(const QtArgs& A, unsigned char* sm
                 if (S2 >= N || S2 == S) sh_done = 1;
                 else if (phase == 0 && S2 + 3 * myexp > N) sh_phase = 1;
             }
+        } else {
+            // the other waves, beside the list logic: zero the histogram that this pass's sweep fills (a pass leaves at most 4 S entries;
+            // its last reader was wave 0 of the pass before, two barriers back)
+            const int nz = 4 * min(LC, 4 * S);
+            for (int i = t - 64; i < nz; i += kQT - 64) nchildcnt[i] = 0;
         }
         __syncthreads();
         QSTAMP(6);
-        // (6) re-home the candidates
-        for (int k = t; k < M; k += kQT) {
-            const int nd = nof[k];
-            nof[k] = (unsigned short)childpos[4 * nd + quadrant_mid(keys[k], mid[nd])];
-        }
+        // (6) re-home the candidates and count the next pass's children; procRank of the new list back to "not processed"
+        S = sh_S; phase = sh_phase; done = sh_done;
+        for (int i = t; i < S; i += kQT) procRank[i] = -1;
+        rehome_and_count<kQT>(keys, nof, M, mid, childpos, nmid, nchildcnt, !done);
         __syncthreads();
         QSTAMP(7);
         diters++;
@@ -358,10 +427,10 @@ __device__ __forceinline__ void quadtree_body(const QtArgs& A, unsigned char* sm
         unsigned* tm = mid; mid = nmid; nmid = tm;
         int* ti = cnt; cnt = ncnt; ncnt = ti;
         ti = crk; crk = ncrk; ncrk = ti;
+        ti = childcnt; childcnt = nchildcnt; nchildcnt = ti;
     }
 #undef QT_WAVE_FENCE
     // ---- best response per node, first candidate wins ties (strict '>' at src/ORBextractor.cc:752)
-    const int S = sh_S;
     unsigned* best = reinterpret_cast<unsigned*>(scanB);
     for (int i = t; i < S; i += kQT) best[i] = 0;
     __syncthreads();
