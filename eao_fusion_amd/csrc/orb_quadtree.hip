@@ -69,7 +69,29 @@ __device__ __forceinline__ int wave_excl_scan(int* a, int n, int lane) {
     return total;
 }
 
-constexpr unsigned kQtLeaf = 0xFFFFFFFFu;          // mid of an entry that holds one key (every key then maps to quadrant 0)
+// Inclusive sum over the wave of one value per lane, on the VALU (the DPP steps of the scans above); lane 63 holds the total.
+__device__ __forceinline__ int wave_incl_sum(int v) {
+    v += __builtin_amdgcn_update_dpp(0, v, 0x111, 0xF, 0xF, true);   // row_shr:1
+    v += __builtin_amdgcn_update_dpp(0, v, 0x112, 0xF, 0xF, true);   // row_shr:2
+    v += __builtin_amdgcn_update_dpp(0, v, 0x114, 0xF, 0xF, true);   // row_shr:4
+    v += __builtin_amdgcn_update_dpp(0, v, 0x118, 0xF, 0xF, true);   // row_shr:8
+    v += __builtin_amdgcn_update_dpp(0, v, 0x142, 0xA, 0xF, true);   // row_bcast15 into rows 1 and 3
+    v += __builtin_amdgcn_update_dpp(0, v, 0x143, 0xC, 0xF, true);   // row_bcast31 into rows 2 and 3
+    return v;
+}
+// Minimum over the wave (uniform result) by the same steps; a lane without a source takes the identity.
+__device__ __forceinline__ int wave_min(int v) {
+    constexpr int kTop = 0x7FFFFFFF;
+    v = min(v, __builtin_amdgcn_update_dpp(kTop, v, 0x111, 0xF, 0xF, false));
+    v = min(v, __builtin_amdgcn_update_dpp(kTop, v, 0x112, 0xF, 0xF, false));
+    v = min(v, __builtin_amdgcn_update_dpp(kTop, v, 0x114, 0xF, 0xF, false));
+    v = min(v, __builtin_amdgcn_update_dpp(kTop, v, 0x118, 0xF, 0xF, false));
+    v = min(v, __builtin_amdgcn_update_dpp(kTop, v, 0x142, 0xA, 0xF, false));
+    v = min(v, __builtin_amdgcn_update_dpp(kTop, v, 0x143, 0xC, 0xF, false));
+    return __builtin_amdgcn_readlane(v, 63);
+}
+
+constexpr unsigned kQtLeaf = 0xFFFFFFFFu;         // mid of an entry that holds one key (every key then maps to quadrant 0)
 __device__ __forceinline__ unsigned box_mid(short4 bx) {
     return (unsigned)(bx.x + ((bx.z - bx.x + 1) >> 1)) | ((unsigned)(bx.y + ((bx.w - bx.y + 1) >> 1)) << 16);
 }
@@ -161,11 +183,28 @@ struct QtArgs {
     unsigned* candOut;   // global copy of the gathered candidates (read back by eao_orb_level_candidates)
 };
 
+// The gather's loads of one round: sixteen lanes to a cell, each with corners gl and gl + 16 of eight cells.  No address depends on the
+// cell counts (a row holds cellCap words whatever its count; a group past the last cell takes the last cell's row).
+constexpr int kQtGL = 16, kQtGC = 8;
+constexpr int kQtCU = 4;   // entries per trip of a careful pass's rank loop (register form)
+template <int kQT>
+__device__ __forceinline__ void gather_row_loads(const unsigned* cellcand, long long cslot, int nCells, int cellCap, int c0, unsigned (&va)[kQtGC], unsigned (&vb)[kQtGC]) {
+    const int grp = threadIdx.x / kQtGL, gl = threadIdx.x % kQtGL;
+#pragma unroll
+    for (int u = 0; u < kQtGC; u++) {
+        const unsigned* srcc = cellcand + (cslot + min(c0 + u * (kQT / kQtGL) + grp, nCells - 1)) * cellCap;
+        va[u] = srcc[min(gl, cellCap - 1)];
+        vb[u] = srcc[min(gl + kQtGL, cellCap - 1)];
+    }
+}
+
 // The candidate keys and their node index live in LDS when the level's M candidates fit the launch's LDS budget
 // (g->qtLdsCand; always at the default 1000-feature settings), else in the global scratch arrays: the body is inlined
-// once per placement.
-template <int kQT, class KeyPtr, class NofPtr>
-__device__ __forceinline__ void quadtree_body(const QtArgs& A, unsigned char* smem, int* wtmp, int* shv, KeyPtr keys, NofPtr nof) {
+// once per placement.  kRegs: the node lists are in LDS (every launch but the global fallback, quadtree_global, which stays as it
+// was): the set-up of a level with one initial node, the first round of row loads issued by the caller (pa, pb) and the register
+// form of the list logic.
+template <int kQT, bool kRegs, class KeyPtr, class NofPtr>
+__device__ __forceinline__ void quadtree_body(const QtArgs& A, unsigned char* smem, int* wtmp, int* shv, KeyPtr keys, NofPtr nof, const unsigned (&pa)[kQtGC], const unsigned (&pb)[kQtGC]) {
     const Geom* __restrict__ g = A.g;
     int& sh_S = shv[0]; int& sh_phase = shv[1]; int& sh_done = shv[2]; int& sh_rstar = shv[3]; int& sh_nexp = shv[4];
     long long* dbg = A.dbg;
@@ -202,11 +241,29 @@ __device__ __forceinline__ void quadtree_body(const QtArgs& A, unsigned char* sm
     // few more than 32): a load instruction reads 64-byte pieces of four cells' rows, and the loads of 128 cells (256 threads) wait
     // together.  (As one thread per cell a load instruction touched 64 cache lines for 64 words, sixteen times over, and the 280
     // cells of level 0 took two rounds of it.)
+    // A level with ONE initial node (every frame up to 3:2) needs no initial assignment: node 0 holds all M candidates and its box,
+    // hence its split point, follows from the geometry alone.  The gather then writes nof[k] = 0 beside the key it stores and
+    // counts the key in the first child histogram (per thread: keys right of the split, below it, both; summed per wave with the
+    // DPP scan, one LDS word per wave and bin) -- no nof fill, no initial sweep, and none of the barriers around them.
     const long long cslot = (long long)f * g->totalCells + L.cellBase;
+    const int nIni = L.nIni;
+    const bool direct = kRegs && nIni == 1;
+    const short4 bx0 = make_short4(0, 0, (short)(int)(L.hX * 1.0f), (short)L.boxH);
+    const unsigned m0 = box_mid(bx0);
+    __shared__ int wq[4 * (kQT / 64)];
     {
-        constexpr int kGL = 16, kGC = 8, kGroups = kQT / kGL;
+        constexpr int kGL = kQtGL, kGC = kQtGC, kGroups = kQT / kGL;
         const int grp = t / kGL, gl = t % kGL;
         const int cellCap = g->cellCap;
+        int nx = 0, ny = 0, nxy = 0, nall = 0;   // of this thread's keys: x >= split, y >= split, both, all
+        auto put = [&](int k, unsigned v) {
+            keys[k] = v; A.candOut[k] = v;
+            if (direct) {
+                nof[k] = 0;
+                const bool hx = (v & 0xFFF) >= (m0 & 0xFFFFu), hy = ((v >> 12) & 0xFFF) >= (m0 >> 16);
+                nx += hx; ny += hy; nxy += hx && hy; nall++;
+            }
+        };
         for (int c0 = 0; c0 < L.nCells; c0 += kGroups * kGC) {
             int o[kGC], n[kGC];
             unsigned va[kGC], vb[kGC];
@@ -217,28 +274,52 @@ __device__ __forceinline__ void quadtree_body(const QtArgs& A, unsigned char* sm
                 const int e = cc + 1 < L.nCells ? scanA[cc + 1] : M;
                 n[u] = c < L.nCells ? e - o[u] : 0;
             }
+            // (unconditional: a row holds cellCap words, whatever its count.  The first round's loads were issued by the caller, before the
+            //  scan of the cell counts: their addresses do not depend on it, only the store offsets below do)
+            if (kRegs && c0 == 0) {
 #pragma unroll
-            for (int u = 0; u < kGC; u++) {   // (unconditional: a row holds cellCap words, whatever its count)
-                const unsigned* srcc = A.cellcand + (cslot + min(c0 + u * kGroups + grp, L.nCells - 1)) * cellCap;
-                va[u] = srcc[min(gl, cellCap - 1)];
-                vb[u] = srcc[min(gl + kGL, cellCap - 1)];
-            }
+                for (int u = 0; u < kGC; u++) { va[u] = pa[u]; vb[u] = pb[u]; }
+            } else gather_row_loads<kQT>(A.cellcand, cslot, L.nCells, cellCap, c0, va, vb);
 #pragma unroll
             for (int u = 0; u < kGC; u++) {
-                if (gl < n[u]) { keys[o[u] + gl] = va[u]; A.candOut[o[u] + gl] = va[u]; }
-                if (gl + kGL < n[u]) { keys[o[u] + gl + kGL] = vb[u]; A.candOut[o[u] + gl + kGL] = vb[u]; }
+                if (gl < n[u]) put(o[u] + gl, va[u]);
+                if (gl + kGL < n[u]) put(o[u] + gl + kGL, vb[u]);
             }
 #pragma unroll
             for (int u = 0; u < kGC; u++) {   // (the rest of a crowded cell)
                 if (n[u] <= 2 * kGL) continue;
                 const unsigned* srcc = A.cellcand + (cslot + c0 + u * kGroups + grp) * cellCap;
-                for (int j = gl + 2 * kGL; j < n[u]; j += kGL) { const unsigned v = srcc[j]; keys[o[u] + j] = v; A.candOut[o[u] + j] = v; }
+                if constexpr (kRegs) {   // (unrolled, with the counters, the copy of this loop for keys in global memory spilled 600 registers)
+#pragma unroll 1
+                    for (int j = gl + 2 * kGL; j < n[u]; j += kGL) put(o[u] + j, srcc[j]);
+                } else {
+                    for (int j = gl + 2 * kGL; j < n[u]; j += kGL) put(o[u] + j, srcc[j]);
+                }
             }
+        }
+        if (direct) {   // quadrants 0..3 = (x low, y low), (x high, y low), (x low, y high), (x high, y high), as quadrant_mid
+            const int s0 = wave_incl_sum(nall - nx - ny + nxy), s1 = wave_incl_sum(nx - nxy), s2 = wave_incl_sum(ny - nxy), s3 = wave_incl_sum(nxy);
+            if (lane == 63) { int* w = wq + 4 * (t >> 6); w[0] = s0; w[1] = s1; w[2] = s2; w[3] = s3; }
         }
     }
     __syncthreads();
     // ---- initial nodes
-    const int nIni = L.nIni;
+    int S = 1, phase = 0, done = 0;
+    if (direct) {
+        if (t < 4) {   // (a lone key is a leaf: nothing counted)
+            int s = 0;
+            for (int w = 0; w < kQT / 64; w++) s += wq[4 * w + t];
+            childcnt0[t] = M > 1 ? s : 0;
+        }
+        if (t == 0) {
+            box0[0] = bx0; cnt0[0] = M; crk0[0] = 0; mid0[0] = M > 1 ? m0 : kQtLeaf;
+            procRank[0] = -1;
+            sh_S = 1; sh_phase = 0; sh_done = 0; sh_rstar = 0x7FFFFFFF; sh_nexp = 0;
+        }
+        __syncthreads();
+        QSTAMP(0);
+        QSTAMP(2);
+    } else {
     if (t < nIni) {
         box0[t] = make_short4((short)(int)(L.hX * (float)t), 0, (short)(int)(L.hX * (float)(t + 1)), (short)L.boxH);
         cnt0[t] = 0;
@@ -250,7 +331,7 @@ __device__ __forceinline__ void quadtree_body(const QtArgs& A, unsigned char* sm
         childcnt0[4 * t] = 0; childcnt0[4 * t + 1] = 0; childcnt0[4 * t + 2] = 0; childcnt0[4 * t + 3] = 0;
     }
     __syncthreads();
-    if (nIni == 1) {   // (frames up to 3:2, the usual case: min((int)(x / hX), 0) is node 0 for every candidate -- no division, no count)
+    if (nIni == 1) {   // (the global fallback alone comes here with one node: min((int)(x / hX), 0) is node 0 for every candidate -- no division, no count)
         for (int k = t; k < M; k += kQT) nof[k] = 0;
         if (t == 0) cnt0[0] = M;
     } else
@@ -278,11 +359,12 @@ __device__ __forceinline__ void quadtree_body(const QtArgs& A, unsigned char* sm
     __syncthreads();
     QSTAMP(0);
     // (wave 0 alone rewrites sh_S / sh_phase / sh_done, behind the NEXT barrier: everyone takes its copies between the two)
-    int S = sh_S, phase = sh_phase, done = 0;
+    S = sh_S; phase = sh_phase;
     // the list is final only now, with the empty nodes dropped: the first pass's child histogram
     rehome_and_count<kQT>(keys, nof, M, mid1, childpos, mid0, childcnt0, true);
     __syncthreads();
     QSTAMP(2);
+    }
 
     int diters = 0;
     short4* box = box0; short4* nbox = box1;
@@ -295,10 +377,108 @@ __device__ __forceinline__ void quadtree_body(const QtArgs& A, unsigned char* sm
     // ALONE, wave-synchronously (DPP scans, wavefront-scope fences, no workgroup barrier): as a sequence of block-wide steps it
     // was ~20 barriers per pass with a handful of instructions between them -- 43 k of level 0's 132 k cycles.  Meanwhile the
     // other waves zero the next histogram.  Two barriers per pass remain, one behind the list logic and one behind the sweep
-    // (four in a careful pass, whose O(n^2) ranking stays block-wide).
+    // (four in a careful pass of the general form, whose O(n^2) ranking stays block-wide; the register form has two in every pass).
 #define QT_WAVE_FENCE() eao::wave_sync()
     const int wv = t >> 6;
     for (int iter = 0; iter < 64 && !done; iter++) {
+        if (kRegs && S <= 64) {
+            // The list fits one entry per lane of wave 0 (workgroup-uniform; every pass of a tree of up to four passes from one initial
+            // node): the list logic in registers.  Ranks and prefixes come from ballots, one DPP scan and, in a careful pass, one
+            // uniform loop of readlanes -- no index array in LDS (scanA, vlist, order, procRank, scanB), no fence, and no
+            // block-wide ranking with its two barriers.  The steps and their results are those of the general form below.
+            if (wv == 0) {
+                // (1) the entry of this lane, every load issued before any is used (a lane past the list reads entry 0 and owns nothing)
+                const bool have = lane < S;
+                const int li = have ? lane : 0;
+                const int c = cnt[li];
+                const int2 ca = *reinterpret_cast<const int2*>(childcnt + 4 * li), cb = *reinterpret_cast<const int2*>(childcnt + 4 * li + 2);
+                const short4 b = box[li];
+                const int ck = crk[li];
+                const unsigned md = mid[li];
+                const int cq[4] = {ca.x, ca.y, cb.x, cb.y};
+                const bool multi = have && c > 1;
+                const int ne = multi ? (cq[0] > 0) + (cq[1] > 0) + (cq[2] > 0) + (cq[3] > 0) : 0;
+                const unsigned long long mm = __ballot(multi);
+                const unsigned long long below = (1ull << lane) - 1;
+                const int nCand = __popcll(mm);
+                QSTAMP(1);
+                QSTAMP(3);
+                // (3) + (4) rank r in processing order and growth prefix (the children of the entries processed before this one)
+                int r, pre, nProc = nCand, totalChildren;
+                if (phase == 0) {   // list order
+                    r = __popcll(mm & below);
+                    const int inc = wave_incl_sum(ne);
+                    pre = inc - ne;
+                    totalChildren = __builtin_amdgcn_readlane(inc, 63);
+                } else {
+                    // (size, creation rank) descending.  The pairs are unique, so ne can ride below the creation rank in the low word
+                    // without changing the order: two readlanes per entry hand every lane that entry's key and ne.
+                    // (Over the lanes of the list, kQtCU to a trip, not over the set bits of mm: a bit loop was fourteen dependent
+                    //  instructions per entry, 6.5 k cycles for a list of 64, and longer trips spill.  The key of an entry that is not
+                    //  multi is 0 and above nobody's.  One accumulator: rank in the bits from 9, prefix (<= 4 x 63) below.  The bound
+                    //  through readfirstlane: as a vector value the loop ran on exec masks.)
+                    const unsigned klo = ((unsigned)ck << 3) | (unsigned)ne;
+                    const unsigned long long key = multi ? ((unsigned long long)(unsigned)c << 32) | klo : 0ull;
+                    int acc = 0;
+                    const int Su = __builtin_amdgcn_readfirstlane(S);
+                    for (int j0 = 0; j0 < Su; j0 += kQtCU)
+#pragma unroll
+                    for (int u = 0; u < kQtCU; u++) {
+                        const int j = j0 + u;
+                        const unsigned jlo = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)key, j);
+                        const unsigned long long jkey = ((unsigned long long)(unsigned)__builtin_amdgcn_readlane((int)(key >> 32), j) << 32) | jlo;
+                        acc += jkey > key ? (int)((jlo & 7u) | 0x200u) : 0;
+                    }
+                    r = acc >> 9; pre = acc & 0x1FF;
+                    // the careful pass stops at the first entry whose children bring the list to N
+                    const int rstar = wave_min(multi && S + pre + ne - (r + 1) >= N ? r : 0x7FFFFFFF);
+                    if (rstar != 0x7FFFFFFF) nProc = rstar + 1;
+                    const unsigned long long lastm = __ballot(multi && r == nProc - 1);
+                    totalChildren = lastm ? __builtin_amdgcn_readlane(pre + ne, __ffsll((long long)lastm) - 1) : 0;
+                }
+                QSTAMP(4);
+                const bool proc = multi && r < nProc;
+                const int keep = __popcll(__ballot(have && !proc) & below);   // untouched entries ahead of this one
+                QSTAMP(5);
+                // (5) new list: children of the LAST processed node first (each as n4,n3,n2,n1), untouched entries after
+                int myexp = 0;
+                if (have) {
+                    if (!proc) {
+                        const int p = totalChildren + keep;
+                        nbox[p] = b; ncnt[p] = c; ncrk[p] = ck; nmid[p] = md;
+                        *reinterpret_cast<int2*>(childpos + 4 * lane) = make_int2(p, p);       // (every key of an untouched entry moves with it)
+                        *reinterpret_cast<int2*>(childpos + 4 * lane + 2) = make_int2(p, p);
+                    } else {
+                        const short mx = (short)(b.x + ((b.z - b.x + 1) >> 1)), my = (short)(b.y + ((b.w - b.y + 1) >> 1));
+                        int p = totalChildren - (pre + ne);
+#pragma unroll
+                        for (int q = 3; q >= 0; q--) {
+                            const int cc = cq[q];
+                            if (cc > 0) {
+                                short4 nb;
+                                nb.x = (q & 1) ? mx : b.x; nb.z = (q & 1) ? b.z : mx;
+                                nb.y = (q & 2) ? my : b.y; nb.w = (q & 2) ? b.w : my;
+                                nbox[p] = nb; ncnt[p] = cc; ncrk[p] = 4 * r + q; nmid[p] = cc > 1 ? box_mid(nb) : kQtLeaf;
+                                childpos[4 * lane + q] = p;
+                                p++;
+                                myexp += cc > 1;
+                            }
+                        }
+                    }
+                }
+                myexp = __builtin_amdgcn_readlane(wave_incl_sum(myexp), 63);
+                // (7) upstream's termination tests (src/ORBextractor.cc:660-737)
+                if (lane == 0) {
+                    const int S2 = totalChildren + S - nProc;
+                    sh_S = S2;
+                    if (S2 >= N || S2 == S) sh_done = 1;
+                    else if (phase == 0 && S2 + 3 * myexp > N) sh_phase = 1;
+                }
+            } else {
+                const int nz = 4 * min(LC, 4 * S);
+                for (int i = t - 64; i < nz; i += kQT - 64) nchildcnt[i] = 0;
+            }
+        } else {
         // (1) the multi-key entries in list order (childcnt of this pass is complete, procRank[0, S) is -1: the sweep before the barrier saw to both)
         int nCand = 0;
         if (wv == 0) {
@@ -414,6 +594,7 @@ __device__ __forceinline__ void quadtree_body(const QtArgs& A, unsigned char* sm
             const int nz = 4 * min(LC, 4 * S);
             for (int i = t - 64; i < nz; i += kQT - 64) nchildcnt[i] = 0;
         }
+        }
         __syncthreads();
         QSTAMP(6);
         // (6) re-home the candidates and count the next pass's children; procRank of the new list back to "not processed"
@@ -466,8 +647,9 @@ __device__ __noinline__ void quadtree_global(const Geom* __restrict__ g, const u
         if (t == 0) levelcnt[f * g->nlevels + l] = 0;
         return;
     }
+    const unsigned pa[kQtGC] = {}, pb[kQtGC] = {};   // (no loads ahead of the scan here)
     QtArgs A = {g, cellcand, cellcnt, levelkps, levelcnt, f, l, M, dbg, cand + (long long)f * g->totalCandCap + L.candBase};
-    quadtree_body<kQT>(A, base, wtmp, shv, cand + (long long)f * g->totalCandCap + L.candBase, nodeof + (long long)f * g->totalCandCap + L.candBase);
+    quadtree_body<kQT, false>(A, base, wtmp, shv, cand + (long long)f * g->totalCandCap + L.candBase, nodeof + (long long)f * g->totalCandCap + L.candBase, pa, pb);
 }
 
 template <int kQT>
@@ -492,6 +674,9 @@ __global__ __launch_bounds__(kQT, kQT == 256 ? 4 : 1) void k_quadtree(const Geom
     int* scanA = reinterpret_cast<int*>(smem + (size_t)L.listCap * (2 * sizeof(short4) + sizeof(int) * kQtNodeInts));
     const long long cslot = (long long)f * g->totalCells + L.cellBase;
     for (int i = t; i < L.nCells; i += kQT) scanA[i] = cellcnt[cslot + i];
+    // the gather's first round of row loads, in flight across the scan of the cell counts (consumed in quadtree_body)
+    unsigned pa[kQtGC] = {}, pb[kQtGC] = {};
+    if (L.nCells > 0) gather_row_loads<kQT>(cellcand, cslot, L.nCells, g->cellCap, 0, pa, pb);
     __syncthreads();
     const int M = block_excl_scan<kQT>(scanA, L.nCells, wtmp);
     if (t == 0) candcnt[f * g->nlevels + l] = M;
@@ -502,9 +687,9 @@ __global__ __launch_bounds__(kQT, kQT == 256 ? 4 : 1) void k_quadtree(const Geom
     QtArgs A = {g, cellcand, cellcnt, levelkps, levelcnt, f, l, M, (dbg && f == f0) ? dbg : nullptr, cand + (long long)f * g->totalCandCap + L.candBase};
     if (M <= g->qtLdsCand) {
         unsigned* keysL = reinterpret_cast<unsigned*>(smem + g->qtKeysOff);
-        quadtree_body<kQT>(A, smem, wtmp, shv, keysL, reinterpret_cast<unsigned short*>(keysL + g->qtLdsCand));
+        quadtree_body<kQT, true>(A, smem, wtmp, shv, keysL, reinterpret_cast<unsigned short*>(keysL + g->qtLdsCand), pa, pb);
     } else {
-        quadtree_body<kQT>(A, smem, wtmp, shv, cand + (long long)f * g->totalCandCap + L.candBase, nodeof + (long long)f * g->totalCandCap + L.candBase);
+        quadtree_body<kQT, true>(A, smem, wtmp, shv, cand + (long long)f * g->totalCandCap + L.candBase, nodeof + (long long)f * g->totalCandCap + L.candBase, pa, pb);
     }
 }
 
