@@ -191,6 +191,23 @@ class YoloxCfg(C.Structure):   # eao_yolox_cfg
                 ("max_proposals", C.c_int32), ("max_batch", C.c_int32)]
 
 
+class FrameObjectsDesc(C.Structure):   # eao_frame_objects_desc
+    _fields_ = [("n_kp", C.c_int32), ("kp_x", C.c_void_p), ("kp_y", C.c_void_p), ("mp_id", C.c_void_p), ("mp_xyz", C.c_void_p),
+                ("n_box", C.c_int32), ("boxes", C.c_void_p), ("score", C.c_void_p), ("Tcw", C.c_float * 16),
+                ("fx", C.c_float), ("fy", C.c_float), ("cx", C.c_float), ("cy", C.c_float), ("cols", C.c_int32), ("rows", C.c_int32)]
+
+
+class FrameObjectRecord(C.Structure):   # eao_frame_object_record
+    _fields_ = [("n_assigned", C.c_int32), ("n", C.c_int32), ("sum_pos", C.c_float * 3), ("pos", C.c_float * 3), ("std", C.c_float * 3),
+                ("q1", C.c_float), ("q3", C.c_float), ("max_th", C.c_float), ("boxplot_ran", C.c_int32), ("center_2d", C.c_float * 2),
+                ("has_feature_rect", C.c_int32), ("feature_rect", C.c_int32 * 4), ("num_overlaps", C.c_int32), ("bad", C.c_int32), ("on_edge", C.c_int32)]
+
+
+class FrameObjectsOut(C.Structure):   # eao_frame_objects_out
+    _fields_ = [("records", C.c_void_p), ("assigned_start", C.c_void_p), ("assigned", C.c_void_p), ("assigned_cap", C.c_int64),
+                ("kept_start", C.c_void_p), ("kept", C.c_void_p), ("kept_cap", C.c_int64)]
+
+
 # every symbol include/eao_fusion.h declares: (restype, argtypes)
 _P = C.c_void_p
 _I = C.c_int32
@@ -313,6 +330,10 @@ SYMBOLS = {
     "eao_object_project_rects_batch": (_I, [_I, _P, _P, _P] + [C.c_float] * 4 + [_I, _I, _P, _P, _P]),
     "eao_object_assoc_set_profiling": (_I, [_I]),
     "eao_object_assoc_last_kernel_ms": (_I, [_P]),
+    "eao_frame_objects_batch": (_I, [_I, C.POINTER(FrameObjectsDesc), C.POINTER(FrameObjectsOut)]),
+    "eao_frame_objects": (_I, [C.POINTER(FrameObjectsDesc), C.POINTER(FrameObjectsOut)]),
+    "eao_frame_objects_set_profiling": (_I, [_I]),
+    "eao_frame_objects_last_kernel_ms": (_I, [_P]),
     "eao_yolox_cfg_default": (None, [C.POINTER(YoloxCfg)]),
     "eao_yolox_create": (_I, [C.POINTER(YoloxCfg), C.POINTER(_P)]),
     "eao_yolox_destroy": (None, [_P]),

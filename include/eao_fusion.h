@@ -1432,6 +1432,84 @@ eao_status eao_object_project_rects_batch(int32_t n_map, const int32_t* map_star
 eao_status eao_object_assoc_set_profiling(int32_t on);
 eao_status eao_object_assoc_last_kernel_ms(float* kernel_ms /* 2 */);
 
+/* ---- Object layer: a frame's 2D objects, steps 2, 4, 5 and 6 of the object layer (src/Tracking.cc:1768-1973) -------------------------------------------------
+ * What Tracking::TrackWithMotionModel makes of the detector's boxes before the data association: Tracking::AssociateObjAndPoints (:3031-3065), per box
+ * Object_2D::ComputeMeanAndStandardFrame and RemoveOutliersByBoxPlot (src/Object.cc:61-157), the projection of the centre and the box of the feature points
+ * (:1801-1854), and the removal of bad boxes (:1868-1973).  A pure function of the frame, bit for bit (csrc/frame_objects_internal.h):
+ * one workgroup per (frame, box) compacts the box's keypoints in keypoint order, three lanes add the positions and the squares in that order, Q1 and Q3 come
+ * from counting ranks, and the sequential second loop of step 6 runs on the host behind the download.  The entries are stateless; each host thread has its own
+ * stream and staging.  EAO_ERR_INVALID leaves every output untouched.  Two calls on the same arguments return the same bytes, on one thread or on several.
+ *
+ * A frame: keypoint i has the undistorted coordinates kp_x[i], kp_y[i] (mvKeysUn[i].pt), mp_id[i] = -1 where mvpMapPoints[i] is NULL or isBad() (:3038, :3042)
+ * and otherwise an id >= 0 that is equal for two keypoints exactly when they hold the same MapPoint, and mp_xyz[3 i ..] = GetWorldPos() (read only where
+ * mp_id[i] >= 0).  Box k = {x, y, width, height} of mBoxRect (= mBox, src/Object.cc:53-56) with score[k] = mScore (may be a NaN).  Tcw: mCurrentFrame.mTcw, 4x4
+ * row-major; cols, rows: the image's.
+ *
+ * A record per box, the frames' boxes back to back:
+ *   n_assigned, sum_pos         Obj_c_MapPonits.size() and sum_pos_3d after step 2: the keypoints with a map point whose cvRound'ed position (nearest, ties to
+ *                               even) has x <= px < x + width and y <= py < y + height (:3046), added in keypoint order, one float add per coordinate (:3059)
+ *   boxplot_ran, q1, q3, max_th n_assigned >= 8 (:1782): Q1 = sorted z[n / 4], Q3 = sorted z[n * 3 / 4] over the camera-frame depths, max_th = (float)(Q3 + 1.5 IQR)
+ *                               (src/Object.cc:134-139); zero where the boxplot did not run
+ *   n                           the list's length after the points with z > max_th left it (:150), = mCountMappoint (:1807)
+ *   pos, std                    _Pos = sum_pos / n -- the sum of step 2 over the count after the boxplot: the erase does not touch sum_pos_3d -- as
+ *                               sum * (float)(1.0 / n) + 0.0f, and mStandar_x / y / z about it (:80-99).  n == 0: NaN, as upstream.
+ *   center_2d                   point_center_2d (:1809-1816)
+ *   has_feature_rect, feature_rect   n >= 4 (:1830) and mRectFeaturePoints = {x, y, width, height} (:1836-1853) over pMP->feature of the list: a map point that
+ *                               several keypoints hold carries the coordinates of the LAST of them that lies in any box (:3053); zero otherwise
+ *   num_overlaps                the other boxes l with bboxOverlapratioLatter(this, l) > 0.05 (:1870-1878)
+ *   bad, on_edge                after both loops of :1868-1945; the caller erases the bad objects (:1949-1973).  on_edge is 0 where upstream leaves bOnEdge alone.
+ * assigned / kept: the keypoint indices (within the frame) of Obj_c_MapPonits after step 2 / after the boxplot, in upstream's order; box b of the call owns
+ * entries assigned_start[b] .. assigned_start[b + 1] - 1 (kept_start likewise; total boxes + 1 entries each).  A list buffer that is too short is
+ * EAO_ERR_CAPACITY: assigned_start and kept_start are filled, nothing else is written.
+ * Refused with EAO_ERR_INVALID: a non-finite keypoint, position (where mp_id >= 0), pose or intrinsic; |kp| >= 2^30 (upstream's float -> int conversions are
+ * undefined there); a negative box width or height, a box field or an image size beyond 2^15 (the int areas stay in range); n_kp above
+ * EAO_FRAME_OBJECTS_MAX_KEYPOINTS (the tracker's limit); n_box above EAO_FRAME_OBJECTS_MAX_BOXES; mp_id < -1; more than EAO_FRAME_OBJECTS_MAX_FRAMES frames, or a
+ * batch whose lists could hold more than 2^30 entries (boxes times keypoints with a map point, summed over the frames): split such a call.  Zero-area boxes,
+ * frames without keypoints and n_box == 0 are valid. */
+#define EAO_FRAME_OBJECTS_MAX_KEYPOINTS 4096
+#define EAO_FRAME_OBJECTS_MAX_BOXES 256
+#define EAO_FRAME_OBJECTS_MAX_FRAMES 65535
+typedef struct {
+    int32_t n_kp;
+    const float* kp_x;        /* n_kp */
+    const float* kp_y;        /* n_kp */
+    const int32_t* mp_id;     /* n_kp */
+    const float* mp_xyz;      /* n_kp x 3 */
+    int32_t n_box;
+    const int32_t* boxes;     /* n_box x 4 */
+    const float* score;       /* n_box */
+    float Tcw[16];
+    float fx, fy, cx, cy;
+    int32_t cols, rows;
+} eao_frame_objects_desc;
+typedef struct {
+    int32_t n_assigned, n;
+    float sum_pos[3], pos[3], std[3];
+    float q1, q3, max_th;
+    int32_t boxplot_ran;
+    float center_2d[2];
+    int32_t has_feature_rect;
+    int32_t feature_rect[4];
+    int32_t num_overlaps, bad, on_edge;
+} eao_frame_object_record; /* 100 bytes */
+typedef struct {
+    eao_frame_object_record* records; /* total boxes */
+    int32_t* assigned_start;          /* total boxes + 1 */
+    int32_t* assigned;
+    int64_t assigned_cap;             /* in entries */
+    int32_t* kept_start;              /* total boxes + 1 */
+    int32_t* kept;
+    int64_t kept_cap;
+} eao_frame_objects_out;
+eao_status eao_frame_objects_batch(int32_t n_frames, const eao_frame_objects_desc* frames, const eao_frame_objects_out* out);
+/* a batch of one */
+eao_status eao_frame_objects(const eao_frame_objects_desc* frame, const eao_frame_objects_out* out);
+/* Diagnostic (tools/bench_frame_objects.py): after eao_frame_objects_set_profiling(1) on this thread, the device time in ms of k_frame_features, k_frame_objects
+ * and k_frame_pack of this thread's last call that reached the device, from HIP events on its stream.  An event call that fails costs that measurement
+ * (-1 in its slot) and never fails the product call.  EAO_ERR_INVALID when no slot is measured. */
+eao_status eao_frame_objects_set_profiling(int32_t on);
+eao_status eao_frame_objects_last_kernel_ms(float* kernel_ms /* 3 */);
+
 /* ---------------------------------------------------------------------------------------------------
  * yolox: what YOLOX::Detect (reference src/YOLOX.cc:369-410) does AROUND the network, on the device.  The network itself is the integrator's engine; it reads
  * the blob and writes the head output in HBM, and nothing of either crosses to the host.

@@ -2,7 +2,7 @@
 //
 // In a real EAO-Fusion checkout OpenCV is present and this header only forwards to it.  This build image has no
 // OpenCV, so for compile- and run-testing the adapters a minimal stand-in with the same member names is provided
-// (cv::Mat for CV_8UC1 / CV_32FC1, cv::KeyPoint, cv::Point2f, cv::Point3f, InputArray/OutputArray as Mat references).  It is NOT
+// (cv::Mat for CV_8UC1 / CV_32FC1, cv::KeyPoint, cv::Point2f, cv::Point3f, cv::Rect, InputArray/OutputArray as Mat references).  It is NOT
 // used to build any reference source -- only this repository's own adapters and tests.
 #pragma once
 
@@ -40,6 +40,13 @@ struct Point3f {
     float x = 0, y = 0, z = 0;
     Point3f() {}
     Point3f(float x_, float y_, float z_) : x(x_), y(y_), z(z_) {}
+};
+
+struct Rect {  // cv::Rect_<int>: what include/eaofusion/FrameObjects.h reads of mBoxRect and writes to mRectFeaturePoints
+    int x = 0, y = 0, width = 0, height = 0;
+    Rect() {}
+    Rect(int x_, int y_, int w_, int h_) : x(x_), y(y_), width(w_), height(h_) {}
+    int area() const { return width * height; }
 };
 
 struct KeyPoint {  // same field order and size (28 bytes) as OpenCV's

@@ -202,6 +202,24 @@ TABLES = {
         ("CRITICAL_R2", 943, _R2 % (_NUM, _GRP, _NUM)),
         ("VARIANCE_DIVISOR_R2", 943, _R2 % (_NUM, _NUM, _GRP)),
     ]),
+    # a frame's 2D objects: steps 4, 5 and 6 of the object layer in Tracking::TrackWithMotionModel and Object_2D::RemoveOutliersByBoxPlot
+    "frame_objects": one_group([
+        ("BOXPLOT_MIN_POINTS", "src/Tracking.cc", 1782, r"if \(obj->Obj_c_MapPonits\.size\(\) < (\d+)\)"),
+        ("QUARTILE_DIVISOR", "src/Object.cc", 134, r"float Q1 = z_c\[\(int\)\(z_c\.size\(\) / (\d+)\)\];"),
+        ("IQR_FACTOR", "src/Object.cc", 139, r"float max_th = Q3 \+ ([0-9.]+) \* IQR;"),
+        ("CROWD_RATIO", "src/Tracking.cc", 1876, r"mBoxRect\) > ([0-9.]+)\)"),
+        ("CROWD_MAX", "src/Tracking.cc", 1880, r"if \(num > (\d+)\)"),
+        ("LARGE_AREA_RATIO", "src/Tracking.cc", 1893, r"\(image\.cols \* image\.rows\) > ([0-9.]+)\)"),
+        ("FEW_POINTS", "src/Tracking.cc", 1897, r"Obj_c_MapPonits\.size\(\) < (\d+)\)"),
+        ("FEW_POINTS_ON_EDGE", "src/Tracking.cc", 1901, r"&& \(objs_2d\[f\]->Obj_c_MapPonits\.size\(\) < (\d+)\)\)"),
+        ("FEW_POINTS_EDGE_PIXELS", "src/Tracking.cc", 1903, r"\(objs_2d\[f\]->mBox\.x < (\d+)\)"),
+        ("ON_EDGE_PIXELS", "src/Tracking.cc", 1912, r"\(objs_2d\[f\]->mBox\.x < (\d+)\)"),
+        ("SAME_OBJECT_IOU", "src/Tracking.cc", 1929, r"mBoxRect\) > ([0-9.]+)\)"),
+        ("SURROUND_IOU", "src/Tracking.cc", 1937, r"mBoxRect\) > ([0-9.]+)\)"),
+        ("SURROUND_RATIO", "src/Tracking.cc", 1939, r"mBoxRect\) > ([0-9.]+)\)"),
+        ("SURROUND_RATIO", "src/Tracking.cc", 1941, r"mBoxRect\) > ([0-9.]+)\)"),
+        ("FEATURE_RECT_MIN_POINTS", "src/Tracking.cc", 1830, r"if \(x_pt\.size\(\) < (\d+)\)"),
+    ]),
     # YOLOX::Detect around the network, and what Tracking::GrabImageRGBD keeps of its result
     "yolox": [
         ("NMS_THRESH", "include/YOLOX.h", 33, r"#define NMS_THRESH ([0-9.]+)", 1),
