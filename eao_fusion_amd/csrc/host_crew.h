@@ -15,7 +15,7 @@
 namespace eao {
 namespace lm {
 
-// The host threads of a batch call (window set-up workers, group leaders) are PERSISTENT: a call hands `count` tasks to the crew and
+// The host threads of a batch call (BABatch::worker, the window set-up workers, and BABatch::lead, the group leaders: lm_host.hip) are PERSISTENT: a call hands `count` tasks to the crew and
 // joins them.  Starting eight std::threads per call cost ~0.3 ms of a 2.9 ms batch (clone + first-touch of the thread's HIP state,
 // one after the other) -- which is why more set-up threads used to make a call slower.  The crew is process-wide, grows on
 // demand and is never torn down (its threads sleep on a condition variable between calls and die with the process).

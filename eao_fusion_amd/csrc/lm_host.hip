@@ -1,9 +1,11 @@
 // lm_host.hip -- host side of the Levenberg-Marquardt engine: per-thread contexts, BAJob (arena, pinned mirror, uploads, tile structure, host-stepped trials; its set-up
 // stages that need no device -- validation, the map-scale path's covisibility structure, the active structure, the launch order -- are ba_setup.h, plain C++),
-// eao_local_ba / eao_local_ba_batch / eao_bundle_adjustment(_planes) and the traces.  Kernels: lba.hip, gba.hip (launched through BALaunch).  Shared pieces:
+// eao_local_ba / eao_local_ba_batch (BABatch: one call's windows and groups with its stages as members -- worker, lead, finish_window, join -- over BABatchPool and the
+// plan of ba_batch_plan.h, plain C++) / eao_bundle_adjustment(_planes) and the traces.  Kernels: lba.hip, gba.hip (launched through BALaunch).  Shared pieces:
 // lm_internal.h.  (Round 6: split out of csrc/lm.hip.)
 #include "lm_internal.h"
 #include "ba_setup.h"
+#include "ba_batch_plan.h"
 
 namespace eao {
 namespace lm {
@@ -440,6 +442,16 @@ struct BAJob {
         return EAO_OK;
     }
 
+    // The set-up launches and, for a chained window, its whole run on `on`: the window's own launch, or the batched launch of its group (whose first window speaks for
+    // all of them: they share its iteration counts).
+    eao_status enqueue(BALaunch& on) {
+        eao_status st = on.attributes();
+        if (st) return st;
+        on.setup();
+        if (chained) on.chain(mode, p->its_first, p->its_second);
+        return EAO_OK;
+    }
+
     eao_status wait_status(int want) {
         EAO_HIP(hipStreamSynchronize(L.s));
         if (c->status->seq != want) { eao::set_error("LM status hand-off out of sequence"); return EAO_ERR_INTERNAL; }
@@ -597,11 +609,9 @@ static eao_status ba_run(const eao_ba_problem* p, const volatile uint8_t* stop, 
     if ((st = j.prepare(c.stream))) return st;
     if (j.trivial) return EAO_OK;
     const double tPrep = ms();
-    if ((st = j.L.attributes())) return st;
-    j.L.setup();
+    if ((st = j.enqueue(j.L))) return st;
     double tEnq = 0;
     if (j.chained) {
-        j.L.chain(mode, p->its_first, p->its_second);
         tEnq = ms();
         EAO_HIP(hipStreamSynchronize(c.stream));
     }
@@ -630,6 +640,34 @@ struct BABatchPool {
     std::vector<hipEvent_t> sideDone;
     BADev* hW = nullptr; size_t hWCap = 0;      // pinned mirror of the window array
     eao::DevBuf<BADev> dW;
+    eao_status reserve(int n) {          // the main stream and its events; a context and a trace per window; the window array, pinned and on the device
+        eao_status st;
+        if (!stream) {
+            EAO_HIP(eao::create_stream(&stream, eao::StreamClass::Background));
+            EAO_HIP(hipEventCreate(&ev0));
+            EAO_HIP(hipEventCreate(&ev1));
+        }
+        while ((int)ctx.size() < n) ctx.emplace_back(new LMContext());
+        if ((int)trace.size() < n) trace.resize(n);
+        for (int w = 0; w < n; w++)
+            if ((st = ctx_init(*ctx[w], false, eao::StreamClass::Background))) return st;
+        if (hWCap < (size_t)n * 2) {
+            if (hW) (void)hipHostFree(hW);
+            hW = nullptr; hWCap = 0;
+            EAO_HIP(hipHostMalloc((void**)&hW, (size_t)n * 2 * sizeof(BADev), hipHostMallocDefault));
+            hWCap = (size_t)n * 2;
+        }
+        return dW.reserve((size_t)n * 2);
+    }
+    eao_status reserve_groups(int G) {      // a stream and an event per group beyond the first
+        while ((int)side.size() < G - 1) {
+            hipStream_t q; hipEvent_t e;
+            EAO_HIP(eao::create_stream(&q, eao::StreamClass::Background));
+            EAO_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+            side.push_back(q); sideDone.push_back(e);
+        }
+        return EAO_OK;
+    }
     ~BABatchPool() {
         if (hW) (void)hipHostFree(hW);
         for (hipEvent_t e : sideDone) (void)hipEventDestroy(e);
@@ -640,7 +678,217 @@ struct BABatchPool {
     }
 };
 thread_local BABatchPool g_batch;
-constexpr int kBatchGroups = 4, kBatchGroupMin = 4;     // default number of window groups / fewest windows worth a group
+
+struct Outcome {      // a status and, if it is an error, the text that came with it (eao_last_error() belongs to the thread that failed)
+    eao_status st = EAO_OK; std::string err;
+    void capture(eao_status s) { st = s; if (s) err = eao_last_error(); }
+};
+
+// One eao_local_ba_batch call: its jobs, the plan that deals them to set-up threads and groups (ba_batch_plan.h), a record per window and per group, and the call's
+// stages as members.  worker(t) and lead(g) are the tasks of the host crew (a batch of one runs them on the caller's thread); what they share is in here.
+struct BABatch {
+    struct Window { Outcome out; bool batched = false; };      // (batched: it shares its group's enqueue)
+    struct Group {
+        BALaunch L;                                  // the batched enqueue of its windows
+        Outcome out;
+        int nBatched = 0, first = -1;                // windows in the batched enqueue / the first of them
+        std::atomic<int> prepared{0};                // windows the set-up workers are through with
+        double msPrep = 0, msEnq = 0, msDone = 0;    // since the call's start: windows prepared, launches enqueued, stream drained
+        int state = 0;                               // 0: running, 1: drained, 2: failed (nothing to take out); under doneMu
+    };
+    BABatchPool& B;
+    const int n;
+    std::vector<BAJob> jobs;
+    BatchPlan plan;
+    std::vector<Window> win;
+    std::vector<Group> grp;
+    int dev = 0;
+    // results: when a group's stream has drained, the set-up workers (idle since the first tenth of the call) take its windows' results out in parallel -- the last
+    // group's nine windows were ~0.1 ms of conversions on one thread at the very end of the call
+    bool crewDone = false;
+    std::mutex doneMu;
+    std::condition_variable doneCv;
+    std::chrono::steady_clock::time_point tp0;
+
+    BABatch(BABatchPool& pool, const eao_ba_problem* problems, int n_, const volatile uint8_t* stop, eao_ba_result* results) : B(pool), n(n_), jobs(n_), win(n_) {
+        for (int w = 0; w < n; w++) {
+            BAJob& j = jobs[w];
+            j.p = &problems[w]; j.stop = stop; j.r = &results[w]; j.mode = 0; j.robust = 1; j.c = B.ctx[w].get(); j.tr = &B.trace[w];
+            j.c->status->seq = 0;        // every window of the batch sees the same hand-off sequence numbers
+        }
+        tp0 = std::chrono::steady_clock::now();
+    }
+    double ms() const { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - tp0).count(); }
+    hipStream_t stream_of(int g) const { return g == 0 ? B.stream : B.side[g - 1]; }
+
+    // The switches and the latency marker are read here; the dealing itself is plan_batch.
+    void deal() {
+        static const int envThreads = getenv("EAO_BA_BATCH_THREADS") ? atoi(getenv("EAO_BA_BATCH_THREADS")) : 0;
+        static const int envGroups = getenv("EAO_BA_BATCH_GROUPS") ? atoi(getenv("EAO_BA_BATCH_GROUPS")) : 0;
+        plan_batch(BatchPlanIn{n, envThreads, envGroups, (int)std::thread::hardware_concurrency(), getenv("EAO_BA_BATCH_EVEN") != nullptr, eao::latency_caller_alive()}, plan);
+        grp = std::vector<Group>(plan.G);
+        crewDone = !(plan.nThreads == 1 && plan.G == 1);
+    }
+
+    void finish_window(int w) {
+        BAJob& j = jobs[w];
+        if (j.trivial || win[w].out.st) return;
+        if (win[w].batched) j.L.seq = grp[plan.group_of(w)].L.seq;
+        win[w].out.capture(j.complete());
+    }
+
+    // set-up: nThreads workers take the windows in order (window w's uploads go to its group's stream), so the first
+    // group is complete after one round; each group's leader then enqueues its chain while the workers carry on
+    void worker(int t) {
+        (void)hipSetDevice(dev);
+        for (int w = t; w < n; w += plan.nThreads) {
+            const int g = plan.group_of(w);
+            win[w].out.capture(jobs[w].prepare(stream_of(g), true));
+            grp[g].prepared.fetch_add(1, std::memory_order_release);
+        }
+        if (!crewDone) return;
+        for (int w = t; w < n; w += plan.nThreads) {
+            Group& gr = grp[plan.group_of(w)];
+            int state;
+            { std::unique_lock<std::mutex> lk(doneMu); doneCv.wait(lk, [&] { return gr.state != 0; }); state = gr.state; }
+            if (state == 1) finish_window(w);
+        }
+    }
+
+    // ---- the group leader's steps, in the order lead() takes them; false: the group stops here
+    bool wait_for_windows(int g) {
+        Group& gr = grp[g];
+        const int w0 = plan.gStart[g], w1 = plan.gStart[g + 1];
+        while (gr.prepared.load(std::memory_order_acquire) < w1 - w0) std::this_thread::yield();    // (the workers above)
+        gr.msPrep = ms();
+        for (int w = w0; w < w1; w++)
+            if (win[w].out.st) return false;
+        return true;
+    }
+    void upload_windows(int g) {      // this group's uploads: one launch per eight windows (see BAJob::prepare)
+        BAUploadArgs U;
+        int k = 0;
+        auto flush = [&]() {
+            if (k) hipLaunchKernelGGL(k_ba_upload, dim3(48, k), dim3(256), 0, stream_of(g), U);
+            k = 0;
+        };
+        for (int w = plan.gStart[g]; w < plan.gStart[g + 1]; w++) {
+            if (jobs[w].trivial || !jobs[w].upBytes) continue;
+            U.dst[k] = jobs[w].upDst; U.src[k] = jobs[w].upSrc; U.n16[k] = jobs[w].upBytes / 16;
+            if (++k == 8) flush();
+        }
+        flush();
+    }
+    // the windows that share the batched enqueue (tile-solver path, something to optimise); the others -- windows beyond
+    // 30 free keyframes, empty ones -- follow one by one on the same stream
+    void choose_batched(int g) {
+        Group& gr = grp[g];
+        const int w0 = plan.gStart[g], w1 = plan.gStart[g + 1];
+        BALaunch& L = gr.L;
+        L.s = stream_of(g); L.W = B.dW.p + 2 * w0; L.seq = 0; L.rot = w0 & 7;
+        for (int w = w0; w < w1; w++) {
+            BAJob& j = jobs[w];
+            if (!j.batchable()) continue;
+            if (gr.first >= 0 && (j.p->its_first != jobs[gr.first].p->its_first || j.p->its_second != jobs[gr.first].p->its_second)) continue;
+            if (gr.first < 0) { gr.first = w; L.d = j.L.d; } else L.d.merge(j.L.d);
+            j.write_records(B.hW + 2 * (w0 + gr.nBatched));
+            gr.nBatched++;
+            win[w].batched = true;
+        }
+    }
+    bool enqueue_batched(int g) {
+        Group& gr = grp[g];
+        if (!gr.nBatched) return true;
+        const int w0 = plan.gStart[g];
+        gr.L.nz = gr.nBatched;
+        if (hipMemcpyAsync(B.dW.p + 2 * w0, B.hW + 2 * w0, (size_t)gr.nBatched * 2 * sizeof(BADev), hipMemcpyHostToDevice, stream_of(g)) != hipSuccess) {
+            eao::set_error("hipMemcpyAsync of the window records failed");
+            gr.out.capture(EAO_ERR_NO_DEVICE);
+            return false;
+        }
+        gr.out.capture(jobs[gr.first].enqueue(gr.L));
+        return !gr.out.st;
+    }
+    bool enqueue_singles(int g) {
+        for (int w = plan.gStart[g]; w < plan.gStart[g + 1]; w++) {
+            if (win[w].batched || jobs[w].trivial) continue;
+            grp[g].out.capture(jobs[w].enqueue(jobs[w].L));
+            if (grp[g].out.st) return false;
+        }
+        grp[g].msEnq = ms();
+        return true;
+    }
+    // results (and, for a window whose device-side run handed over to the host, the rest of its run) as soon as THIS
+    // group's stream has drained: only the last group's ~10 us per window are not hidden behind the other groups' kernels
+    bool drain(int g) {
+        Group& gr = grp[g];
+        hipStream_t sg = stream_of(g);
+        if (g > 0 && hipEventRecord(B.sideDone[g - 1], sg) != hipSuccess) { eao::set_error("hipEventRecord failed"); gr.out.capture(EAO_ERR_NO_DEVICE); return false; }
+        if (hipStreamSynchronize(sg) != hipSuccess) {
+            eao::set_error("hipStreamSynchronize: %s", hipGetErrorString(hipGetLastError()));
+            gr.out.capture(EAO_ERR_NO_DEVICE);
+            return false;
+        }
+        gr.msDone = ms();
+        return true;
+    }
+    void lead(int g) {
+        (void)hipSetDevice(dev);
+        struct Announce {      // whatever way this group ends, the workers waiting for it are told
+            std::mutex& mu; std::condition_variable& cv; int& state; int value = 2;
+            ~Announce() { { std::lock_guard<std::mutex> lk(mu); state = value; } cv.notify_all(); }
+        } announce{doneMu, doneCv, grp[g].state};
+        if (!wait_for_windows(g)) return;
+        upload_windows(g);
+        choose_batched(g);
+        if (!enqueue_batched(g) || !enqueue_singles(g) || !drain(g)) return;
+        announce.value = 1;
+        if (!crewDone)
+            for (int w = plan.gStart[g]; w < plan.gStart[g + 1]; w++) finish_window(w);
+    }
+
+    void run() {
+        const int nThreads = plan.nThreads, G = plan.G;
+        if (nThreads == 1 && G == 1) { worker(0); lead(0); }          // (a batch of one: no thread is involved)
+        else host_crew().run(nThreads + G - 1, [&](int i) { if (i < nThreads) worker(i); else lead(i - nThreads + 1); }, [&] { lead(0); });
+    }
+
+    // The groups' streams meet again on the main one (or are drained, if anything failed), the first error is raised, the call's trace and timing are written.
+    eao_status join() {
+        const int G = plan.G;
+        bool failed = false;
+        for (const Window& x : win) failed = failed || x.out.st;
+        for (const Group& x : grp) failed = failed || x.out.st;
+        if (failed)
+            for (int g = 1; g < G; g++) (void)hipStreamSynchronize(B.side[g - 1]);
+        else
+            for (int g = 1; g < G; g++) EAO_HIP(hipStreamWaitEvent(B.stream, B.sideDone[g - 1], 0));   // (device time of the call: ev0 .. ev1)
+        for (int w = 0; w < n; w++)
+            if (win[w].out.st) { eao::set_error("window %d: %s", w, win[w].out.err.c_str()); (void)hipStreamSynchronize(B.stream); return win[w].out.st; }
+        for (const Group& x : grp)
+            if (x.out.st) { eao::set_error("%s", x.out.err.c_str()); (void)hipStreamSynchronize(B.stream); return x.out.st; }
+        for (int w = 0; w < n; w++)
+            if (!jobs[w].trivial) g_trace.linearizations += jobs[w].tr->linearizations;
+        EAO_HIP(hipEventRecord(B.ev1, B.stream));
+        EAO_HIP(hipStreamSynchronize(B.stream));
+        EAO_HIP(hipEventElapsedTime(&g_trace.deviceMs, B.ev0, B.ev1));
+        static const bool envTiming = getenv("EAO_BA_BATCH_TIMING") != nullptr;
+        if (envTiming) print_timing();
+        return EAO_OK;
+    }
+    void print_timing() const {
+        int nBatched = 0;
+        double msPrepare = 0, msEnqueue = 0, msSync = 0;
+        std::string sizes;
+        for (int g = 0; g < plan.G; g++) {
+            nBatched += grp[g].nBatched;
+            msPrepare = std::max(msPrepare, grp[g].msPrep); msEnqueue = std::max(msEnqueue, grp[g].msEnq); msSync = std::max(msSync, grp[g].msDone);
+            sizes += (g ? "+" : "") + std::to_string(plan.gStart[g + 1] - plan.gStart[g]);
+        }
+        fprintf(stderr, "[eao_local_ba_batch] %d windows (%d batched, %d host threads): set-up + uploads enqueued %.3f ms, launches enqueued %.3f, device done %.3f, results out %.3f, groups %s\n",
+                n, nBatched, plan.nThreads, msPrepare, msEnqueue, msSync, ms(), sizes.c_str());
+    }
+};
 
 }  // namespace
 
@@ -654,204 +902,15 @@ eao_status eao_local_ba_batch(const eao_ba_problem* problems, int32_t n, const v
     eao_status st = eao::require_device();
     if (st) return st;
     BABatchPool& B = g_batch;
-    if (!B.stream) {
-        EAO_HIP(eao::create_stream(&B.stream, eao::StreamClass::Background));
-        EAO_HIP(hipEventCreate(&B.ev0));
-        EAO_HIP(hipEventCreate(&B.ev1));
-    }
-    while ((int)B.ctx.size() < n) B.ctx.emplace_back(new LMContext());
-    if ((int)B.trace.size() < n) B.trace.resize(n);
-    for (int w = 0; w < n; w++)
-        if ((st = ctx_init(*B.ctx[w], false, eao::StreamClass::Background))) return st;
-    if (B.hWCap < (size_t)n * 2) {
-        if (B.hW) (void)hipHostFree(B.hW);
-        B.hW = nullptr; B.hWCap = 0;
-        EAO_HIP(hipHostMalloc((void**)&B.hW, (size_t)n * 2 * sizeof(BADev), hipHostMallocDefault));
-        B.hWCap = (size_t)n * 2;
-    }
-    if ((st = B.dW.reserve((size_t)n * 2))) return st;
+    if ((st = B.reserve(n))) return st;
     g_trace.clear();
-    std::vector<BAJob> jobs(n);
-    for (int w = 0; w < n; w++) {
-        BAJob& j = jobs[w];
-        j.p = &problems[w]; j.stop = stop; j.r = &results[w]; j.mode = 0; j.robust = 1; j.c = B.ctx[w].get(); j.tr = &B.trace[w];
-        j.c->status->seq = 0;        // every window of the batch sees the same hand-off sequence numbers
-    }
-    static const bool envTiming = getenv("EAO_BA_BATCH_TIMING") != nullptr;
-    const auto tp0 = std::chrono::steady_clock::now();
-    auto since = [&](std::chrono::steady_clock::time_point a) { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - a).count(); };
+    BABatch batch(B, problems, n, stop, results);
     EAO_HIP(hipEventRecord(B.ev0, B.stream));
-    // ---- The windows are dealt to G groups (contiguous ranges).  A group is a chain of its own on its own stream: its
-    //      host-side set-up (validation, pinned mirror, active structure, two uploads per window: ~0.1 ms of memcpy and
-    //      counting each, on a few host threads), then ONE batched enqueue for its windows.  The first group's kernels start
-    //      while the others are still being set up, and a group's one-workgroup-per-window solver (a tenth of the chip) and
-    //      the tails of its other launches overlap the other groups' wide kernels.  More than four streams share hardware
-    //      queues on this runtime and serialise (measured: 5+ groups are 40 % slower than one).
-    static const int envThreads = getenv("EAO_BA_BATCH_THREADS") ? atoi(getenv("EAO_BA_BATCH_THREADS")) : 0;
-    static const int envGroups = getenv("EAO_BA_BATCH_GROUPS") ? atoi(getenv("EAO_BA_BATCH_GROUPS")) : 0;
-    const int hw = (int)std::thread::hardware_concurrency();
-    // (set-up threads make no HIP call any more -- packing and counting only -- so they scale with the host's cores)
-    const int nThreads = std::max(1, std::min(n, envThreads > 0 ? envThreads : std::min(16, std::max(1, hw / 2))));
-    // Groups hold WHOLE ROWS of eight windows where the batch has them (BA_WIN pins a window to an XCD row by row, and deals an incomplete row over all eight):
-    // 25 windows as 8 + 8 + 9 load every XCD with 3.125 windows, as 6 + 6 + 6 + 7 the fullest one with 3.5 (2.6 against 2.8 ms per call).
-    const int fullRows = n / 8, rest = n - 8 * fullRows;
-    const bool rowGroups = fullRows >= 1 && !getenv("EAO_BA_BATCH_EVEN");      // (A/B switch: the even split of rounds 2-3)
-    const bool restGroup = rowGroups && rest >= kBatchGroupMin;                // an incomplete row large enough to be a group of its own (else it joins the last group)
-    // (two groups while a frame-rate caller is alive in the process: common.h, note_latency_call)
-    const int gWant = std::min(envGroups > 0 ? envGroups : (eao::latency_caller_alive() ? 2 : kBatchGroups), nThreads);
-    const int G = std::max(1, rowGroups ? std::min(gWant, fullRows + (restGroup ? 1 : 0)) : std::min(gWant, n / kBatchGroupMin));
-    std::vector<int> gStart(G + 1, n);
-    for (int g = 0; g < G; g++) {
-        if (!rowGroups) gStart[g] = (int)((long long)n * g / G);
-        else if (restGroup && G > 1) gStart[g] = g == G - 1 ? 8 * fullRows : 8 * (int)((long long)fullRows * g / (G - 1));
-        else gStart[g] = 8 * (int)((long long)fullRows * g / G);
-    }
-    while ((int)B.side.size() < G - 1) {
-        hipStream_t q; hipEvent_t e;
-        EAO_HIP(eao::create_stream(&q, eao::StreamClass::Background));
-        EAO_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-        B.side.push_back(q); B.sideDone.push_back(e);
-    }
-    std::vector<eao_status> stw(n, EAO_OK), stg(G, EAO_OK);
-    std::vector<std::string> errw(n), errg(G);
-    std::vector<BALaunch> LG(G);
-    std::vector<int> groupOf(n, -1), nInGroup(G, 0);
-    std::vector<char> batched(n, 0);
-    std::vector<double> msPrep(G, 0.0), msEnq(G, 0.0), msDone(G, 0.0);
-    int dev = 0;
-    EAO_HIP(hipGetDevice(&dev));
-    // set-up: nThreads workers take the windows in order (window w's uploads go to its group's stream), so the first
-    // group is complete after one round; each group's leader then enqueues its chain while the workers carry on
-    std::vector<std::atomic<int>> prepared(G);
-    for (auto& a : prepared) a.store(0);
-    auto groupOfWindow = [&](int w) { int g = 0; while (gStart[g + 1] <= w) g++; return g; };
-    auto streamOf = [&](int g) { return g == 0 ? B.stream : B.side[g - 1]; };
-    // results: when a group's stream has drained, the set-up workers (idle since the first tenth of the call) take its windows' results out in parallel -- the last
-    // group's nine windows were ~0.1 ms of conversions on one thread at the very end of the call
-    const bool crewDone = !(nThreads == 1 && G == 1);
-    std::mutex doneMu;
-    std::condition_variable doneCv;
-    std::vector<int> gState(G, 0);      // 0: running, 1: drained, 2: failed (nothing to take out)
-    auto finish_window = [&](int w, int g) {
-        BAJob& j = jobs[w];
-        if (j.trivial || stw[w]) return;
-        if (batched[w]) j.L.seq = LG[g].seq;
-        stw[w] = j.complete();
-        if (stw[w]) errw[w] = eao_last_error();
-    };
-    auto worker = [&](int t) {
-        (void)hipSetDevice(dev);
-        for (int w = t; w < n; w += nThreads) {
-            const int g = groupOfWindow(w);
-            stw[w] = jobs[w].prepare(streamOf(g), true);
-            if (stw[w]) errw[w] = eao_last_error();
-            prepared[g].fetch_add(1, std::memory_order_release);
-        }
-        if (!crewDone) return;
-        for (int w = t; w < n; w += nThreads) {
-            const int g = groupOfWindow(w);
-            int state;
-            { std::unique_lock<std::mutex> lk(doneMu); doneCv.wait(lk, [&] { return gState[g] != 0; }); state = gState[g]; }
-            if (state == 1) finish_window(w, g);
-        }
-    };
-    auto groupWork = [&](int g) {
-        (void)hipSetDevice(dev);
-        struct Announce {      // whatever way this group ends, the workers waiting for it are told
-            std::mutex& mu; std::condition_variable& cv; int& state; int value = 2;
-            ~Announce() { { std::lock_guard<std::mutex> lk(mu); state = value; } cv.notify_all(); }
-        } announce{doneMu, doneCv, gState[g]};
-        const int w0 = gStart[g], w1 = gStart[g + 1];
-        hipStream_t sg = streamOf(g);
-        while (prepared[g].load(std::memory_order_acquire) < w1 - w0) std::this_thread::yield();    // (the workers above)
-        msPrep[g] = since(tp0);
-        for (int w = w0; w < w1; w++)
-            if (stw[w]) return;
-        // the windows that share the batched enqueue (tile-solver path, something to optimise); the others -- windows beyond
-        // 30 free keyframes, empty ones -- follow one by one on the same stream
-        {   // this group's uploads: one launch per eight windows (see BAJob::prepare)
-            BAUploadArgs U;
-            int k = 0;
-            auto flush = [&]() {
-                if (k) hipLaunchKernelGGL(k_ba_upload, dim3(48, k), dim3(256), 0, sg, U);
-                k = 0;
-            };
-            for (int w = w0; w < w1; w++) {
-                if (jobs[w].trivial || !jobs[w].upBytes) continue;
-                U.dst[k] = jobs[w].upDst; U.src[k] = jobs[w].upSrc; U.n16[k] = jobs[w].upBytes / 16;
-                if (++k == 8) flush();
-            }
-            flush();
-        }
-        BALaunch& L = LG[g];
-        L.s = sg; L.W = B.dW.p + 2 * w0; L.seq = 0; L.rot = w0 & 7;
-        int first = -1, cnt = 0;
-        for (int w = w0; w < w1; w++) {
-            BAJob& j = jobs[w];
-            if (!j.batchable()) continue;
-            if (first >= 0 && (j.p->its_first != jobs[first].p->its_first || j.p->its_second != jobs[first].p->its_second)) continue;
-            if (first < 0) { first = w; L.d = j.L.d; } else L.d.merge(j.L.d);
-            j.write_records(B.hW + 2 * (w0 + cnt));
-            cnt++;
-            groupOf[w] = g; batched[w] = 1;
-        }
-        nInGroup[g] = cnt;
-        auto fail = [&](eao_status e) { stg[g] = e; errg[g] = eao_last_error(); };
-        if (cnt) {
-            L.nz = cnt;
-            if (hipMemcpyAsync(B.dW.p + 2 * w0, B.hW + 2 * w0, (size_t)cnt * 2 * sizeof(BADev), hipMemcpyHostToDevice, sg) != hipSuccess) {
-                eao::set_error("hipMemcpyAsync of the window records failed");
-                return fail(EAO_ERR_NO_DEVICE);
-            }
-            eao_status e = L.attributes();
-            if (e) return fail(e);
-            L.setup();
-            L.chain(0, jobs[first].p->its_first, jobs[first].p->its_second);
-        }
-        for (int w = w0; w < w1; w++) {
-            BAJob& j = jobs[w];
-            if (batched[w] || j.trivial) continue;
-            eao_status e = j.L.attributes();
-            if (e) return fail(e);
-            j.L.setup();
-            if (j.chained) j.L.chain(0, j.p->its_first, j.p->its_second);
-        }
-        msEnq[g] = since(tp0);
-        // results (and, for a window whose device-side run handed over to the host, the rest of its run) as soon as THIS
-        // group's stream has drained: only the last group's ~10 us per window are not hidden behind the other groups' kernels
-        if (g > 0 && hipEventRecord(B.sideDone[g - 1], sg) != hipSuccess) { eao::set_error("hipEventRecord failed"); return fail(EAO_ERR_NO_DEVICE); }
-        if (hipStreamSynchronize(sg) != hipSuccess) { eao::set_error("hipStreamSynchronize: %s", hipGetErrorString(hipGetLastError())); return fail(EAO_ERR_NO_DEVICE); }
-        msDone[g] = since(tp0);
-        announce.value = 1;
-        if (!crewDone)
-            for (int w = w0; w < w1; w++) finish_window(w, g);
-    };
-    if (nThreads == 1 && G == 1) { worker(0); groupWork(0); }          // (a batch of one: no thread is involved)
-    else host_crew().run(nThreads + G - 1, [&](int i) { if (i < nThreads) worker(i); else groupWork(i - nThreads + 1); }, [&] { groupWork(0); });
-    bool failed = false;
-    for (int w = 0; w < n; w++) failed = failed || stw[w];
-    for (int g = 0; g < G; g++) failed = failed || stg[g];
-    if (failed)
-        for (int g = 1; g < G; g++) (void)hipStreamSynchronize(B.side[g - 1]);
-    else
-        for (int g = 1; g < G; g++) EAO_HIP(hipStreamWaitEvent(B.stream, B.sideDone[g - 1], 0));   // (device time of the call: ev0 .. ev1)
-    for (int w = 0; w < n; w++)
-        if (stw[w]) { eao::set_error("window %d: %s", w, errw[w].c_str()); (void)hipStreamSynchronize(B.stream); return stw[w]; }
-    for (int g = 0; g < G; g++)
-        if (stg[g]) { eao::set_error("%s", errg[g].c_str()); (void)hipStreamSynchronize(B.stream); return stg[g]; }
-    int nBatched = 0;
-    for (int g = 0; g < G; g++) nBatched += nInGroup[g];
-    const double msPrepare = *std::max_element(msPrep.begin(), msPrep.end());
-    const double msEnqueue = *std::max_element(msEnq.begin(), msEnq.end()), msSync = *std::max_element(msDone.begin(), msDone.end());
-    for (int w = 0; w < n; w++)
-        if (!jobs[w].trivial) g_trace.linearizations += jobs[w].tr->linearizations;
-    EAO_HIP(hipEventRecord(B.ev1, B.stream));
-    EAO_HIP(hipStreamSynchronize(B.stream));
-    EAO_HIP(hipEventElapsedTime(&g_trace.deviceMs, B.ev0, B.ev1));
-    if (envTiming)
-        fprintf(stderr, "[eao_local_ba_batch] %d windows (%d batched, %d host threads): set-up + uploads enqueued %.3f ms, launches enqueued %.3f, device done %.3f, results out %.3f\n",
-                n, nBatched, nThreads, msPrepare, msEnqueue, msSync, since(tp0));
-    return EAO_OK;
+    batch.deal();
+    if ((st = B.reserve_groups(batch.plan.G))) return st;
+    EAO_HIP(hipGetDevice(&batch.dev));
+    batch.run();
+    return batch.join();
 }
 
 eao_status eao_bundle_adjustment(const eao_ba_problem* p, int32_t robust, const volatile uint8_t* stop, eao_ba_result* r) {

@@ -432,11 +432,12 @@ def test_local_ba_batch_equals_single_calls(gpu):
     assert _same_result(one[0], single[0])
 
 
-@pytest.mark.parametrize("n", [2, 7, 8, 9, 12, 17, 21])
+@pytest.mark.parametrize("n", [2, 7, 8, 9, 12, 17, 20, 21, 28])
 def test_local_ba_batch_placement_does_not_change_results(gpu, n, monkeypatch):
     """Round 4: a batch's windows are pinned to XCDs row by row, the windows of an incomplete row of eight are dealt over all eight XCDs (BA_WIN), and the
-    window groups hold whole rows (8 + 8 + 9 for 25 windows).  None of it may change a bit: every batch size around the row boundaries against the even
-    split of rounds 2-3 (EAO_BA_BATCH_EVEN=1), one group, and a window's own single call (within the LM bound: a single window runs other kernels)."""
+    window groups hold whole rows (8 + 8 + 9 for 25 windows).  None of it may change a bit: every batch size around the row boundaries (20: the rest group at
+    its threshold of four, 8 + 8 + 4; 28: a fourth group, 8 + 8 + 8 + 4) against the even split of rounds 2-3 (EAO_BA_BATCH_EVEN=1), one group, and a window's
+    own single call (within the LM bound: a single window runs other kernels)."""
     probs = [synth.synth_ba(n_free=4 + (w % 3), n_fixed=2, n_points=150 + 10 * (w % 5), seed=6400 + w) for w in range(n)]
     rows = gpu.Optimizer.LocalBundleAdjustmentBatch(probs)
     monkeypatch.setenv("EAO_BA_BATCH_EVEN", "1")
@@ -482,6 +483,30 @@ def test_local_ba_batch_error_in_one_window_leaves_the_library_usable(gpu):
     for a, b in zip(good, again):
         assert np.array_equal(a["poses"].view(np.uint32), b["poses"].view(np.uint32)) and np.array_equal(a["points"].view(np.uint32), b["points"].view(np.uint32))
         assert list(a["iters"]) == list(b["iters"])
+
+
+@pytest.fixture(scope="module")
+def twenty_windows(gpu):
+    """20 windows of the size above (three groups: 8 + 8 + 4) and their batch, computed once"""
+    probs = [synth.synth_ba(n_free=5, n_fixed=2, n_points=300, seed=6300 + w) for w in range(20)]
+    return probs, gpu.Optimizer.LocalBundleAdjustmentBatch(probs)
+
+
+@pytest.mark.parametrize("bad_at", [3, 18])
+def test_local_ba_batch_error_in_one_group_while_the_others_are_in_flight(gpu, twenty_windows, bad_at):
+    """The same refusal with more than one group: the window with the duplicated edge in the first group (two others to drain) and in the last one.  The call names
+    that window, and the next call on the same thread reproduces the good batch bit for bit."""
+    probs, good = twenty_windows
+    bad = dict(probs[bad_at])
+    k = int(np.flatnonzero(bad["fixed"][bad["edge_cam"]] == 0)[-1])       # an edge of a free camera
+    for key in ("edge_cam", "edge_point", "obs", "inv_sigma2"):
+        bad[key] = np.concatenate([bad[key], bad[key][k:k + 1]])
+    with pytest.raises(gpu.EaoError, match="window %d:" % bad_at):
+        gpu.Optimizer.LocalBundleAdjustmentBatch(probs[:bad_at] + [bad] + probs[bad_at + 1:])
+    again = gpu.Optimizer.LocalBundleAdjustmentBatch(probs)
+    for a, b in zip(good, again):
+        assert a["poses"].tobytes() == b["poses"].tobytes() and a["points"].tobytes() == b["points"].tobytes() and a["chi2"].tobytes() == b["chi2"].tobytes()
+        assert list(a["iters"]) == list(b["iters"]) and np.array_equal(a["edge_outlier"], b["edge_outlier"])
 
 
 def test_map_scale_ba_with_an_abort_flag_that_is_never_raised(gpu):
