@@ -186,6 +186,24 @@ class DetnetDesc(C.Structure):   # eao_detnet_desc
                 ("weight_bytes", C.c_int64), ("activation_bytes", C.c_int64), ("flops", C.c_double)]
 
 
+class ObjectCuboidDesc(C.Structure):   # eao_object_cuboid_desc
+    _fields_ = [("n_points", C.c_int32), ("points", C.c_void_p), ("n_centroids", C.c_int32), ("centroids", C.c_void_p), ("Ryaw", C.c_float * 9),
+                ("prev_cuboid_center", C.c_double * 3)]
+
+
+class ObjectCuboidRec(C.Structure):   # eao_object_cuboid_rec
+    _fields_ = [("status", C.c_int32), ("bounds_written", C.c_int32), ("sum_pos", C.c_float * 3), ("center", C.c_float * 3), ("standar", C.c_float * 3),
+                ("center_standar", C.c_float * 3), ("center_standar_dis", C.c_float), ("bounds", C.c_float * 6),
+                ("lenth", C.c_float), ("width", C.c_float), ("height", C.c_float), ("rmax", C.c_float), ("reserved", C.c_int32),
+                ("Twobj", C.c_float * 16), ("Twobj_without_yaw", C.c_float * 16), ("cuboid_center", C.c_double * 3),
+                ("corners", C.c_double * 3 * 8), ("corners_w", C.c_double * 3 * 8), ("pose_q", C.c_double * 4), ("pose_t", C.c_double * 3),
+                ("pose_without_yaw_q", C.c_double * 4), ("pose_without_yaw_t", C.c_double * 3)]
+
+
+class ObjectOverlapRow(C.Structure):   # eao_object_overlap_row
+    _fields_ = [("cuboid_center", C.c_double * 3), ("lenth", C.c_float), ("width", C.c_float), ("height", C.c_float), ("reserved", C.c_int32)]
+
+
 class YoloxCfg(C.Structure):   # eao_yolox_cfg
     _fields_ = [("input_size", C.c_int32), ("num_classes", C.c_int32), ("conf_thresh", C.c_float), ("nms_thresh", C.c_float),
                 ("max_proposals", C.c_int32), ("max_batch", C.c_int32)]
@@ -334,6 +352,11 @@ SYMBOLS = {
     "eao_frame_objects": (_I, [C.POINTER(FrameObjectsDesc), C.POINTER(FrameObjectsOut)]),
     "eao_frame_objects_set_profiling": (_I, [_I]),
     "eao_frame_objects_last_kernel_ms": (_I, [_P]),
+    "eao_object_cuboids_batch": (_I, [_I, C.POINTER(ObjectCuboidDesc), _P]),
+    "eao_object_cuboids": (_I, [C.POINTER(ObjectCuboidDesc), _P]),
+    "eao_object_overlaps": (_I, [_I, _P, _P, _P, _P]),
+    "eao_object_cuboid_set_profiling": (_I, [_I]),
+    "eao_object_cuboid_last_kernel_ms": (_I, [_P]),
     "eao_yolox_cfg_default": (None, [C.POINTER(YoloxCfg)]),
     "eao_yolox_create": (_I, [C.POINTER(YoloxCfg), C.POINTER(_P)]),
     "eao_yolox_destroy": (None, [_P]),

@@ -1511,6 +1511,86 @@ eao_status eao_frame_objects_set_profiling(int32_t on);
 eao_status eao_frame_objects_last_kernel_ms(float* kernel_ms /* 3 */);
 
 /* ---------------------------------------------------------------------------------------------------
+ * object_cuboid: a map object's centre, deviations, bounds, poses, corners and scale -- Object_Map::ComputeMeanAndStandard (reference src/Object.cc:999-1235)
+ * with both of its calls of Object_Map::UpdateObjPose (:2243-2303) -- on the device, one launch for a batch of objects, bit for bit what upstream's loops compute
+ * (csrc/object_cuboid_internal.h holds the literal form; DESIGN.md section 4q states the order of every sum and every reading that OpenCV, Eigen and g2o leave
+ * open).  Upstream calls it once per associated object per frame (src/Object.cc:718-719, :1593-1596, src/Tracking.cc:3136), after merges and splits (:1691-1699,
+ * :2089, :2200-2201) and for every object of the map on every keyframe (LocalMapping::UpdateObject, src/LocalMapping.cc:771-794).  The entries are stateless;
+ * each host thread has its own stream and staging.  EAO_ERR_INVALID leaves every output untouched.  Two calls on the same arguments return the same bytes, on
+ * one thread or on several.
+ *
+ * An object: points = GetWorldPos() of mvpMapObjectMappoints in list order AFTER the erase of the bad ones (:1003-1024; include/eaofusion/ObjectMap.h erases),
+ * centroids = mObjectFrame[i]->_Pos in list order, Ryaw = the nine floats of upstream's own expression over rotP / rotR / rotY (:2250-2260, row-major; no sin or
+ * cos runs in the library), prev_cuboid_center = mCuboid3D.cuboidCenter before the call (read only when n_centroids >= 5).
+ *
+ * A record per object, stored whole:
+ *   status                      EAO_OBJECT_CUBOID_EMPTY: n_points == 0, the return of :1050; sum_pos, center and standar hold what upstream holds there (0 and
+ *                               NaNs) and every other field is zero: upstream leaves those members untouched.  Otherwise EAO_OBJECT_CUBOID_DONE.
+ *   sum_pos, center, standar    mSumPointsPos (float adds in list order, :1020), mCenter3D = sum * (float)(1.0 / n) + 0.0f (:1027), mStandar_x / y / z (:1030-1048)
+ *   center_standar[3]           mCenterStandar_x / y / z over the centroids (:1054-1068); n_centroids == 0 divides by zero as upstream does (NaN)
+ *   center_standar_dis          mCenterStandar (:1220-1234)
+ *   bounds_written, bounds      n_centroids < 5 (:1071): x_min, x_max, y_min, y_max, z_min, z_max of the world-frame points (:1095-1100).  Otherwise upstream leaves
+ *                               them untouched: zero.  Among equal extrema (a -0.0f beside a +0.0f) the one with the smallest list position is taken.
+ *   lenth, width, height        the object-frame scale (:1182-1184)
+ *   rmax                        mCuboid3D.mfRMax (:1189-1217)
+ *   Twobj, Twobj_without_yaw    the two float matrices of the SECOND UpdateObjPose (:1186), row-major; Converter::toSE3Quat of them is mCuboid3D.pose and
+ *                               pose_without_yaw
+ *   cuboid_center               (corner_2 + corner_8) / 2 (:1185)
+ *   corners, corners_w          corner_1 .. corner_8 through pose (:1160-1167) and corner_1_w .. corner_8_w through pose_without_yaw (:1170-1177), both poses those
+ *                               of the FIRST UpdateObjPose (:1128)
+ *   pose_q, pose_t, pose_without_yaw_q, pose_without_yaw_t      the library's own Quaterniond(R) + normalizeRotation (x, y, z, w) and translation of the final poses
+ * A NaN's sign and payload are nobody's contract.
+ * Refused with EAO_ERR_INVALID before anything is written: a negative count; a null pointer where a count is positive; a non-finite point, centroid, Ryaw entry
+ * or prev_cuboid_center; more than EAO_OBJECT_CUBOID_MAX_OBJECTS objects or more than 2^27 points and centroids in one call (split it).  n_points == 0 and
+ * n_centroids == 0 are valid.  Finite inputs whose squares overflow float are computed, not refused. */
+#define EAO_OBJECT_CUBOID_MAX_OBJECTS 65535
+#define EAO_OBJECT_CUBOID_EMPTY 0
+#define EAO_OBJECT_CUBOID_DONE 1
+typedef struct {
+    int32_t n_points;
+    const float* points;          /* n_points x 3 */
+    int32_t n_centroids;
+    const float* centroids;       /* n_centroids x 3 */
+    float Ryaw[9];
+    double prev_cuboid_center[3];
+} eao_object_cuboid_desc;
+typedef struct {
+    int32_t status, bounds_written;
+    float sum_pos[3], center[3], standar[3];
+    float center_standar[3], center_standar_dis;
+    float bounds[6];
+    float lenth, width, height;
+    float rmax;
+    int32_t reserved;             /* zero */
+    float Twobj[16], Twobj_without_yaw[16];
+    double cuboid_center[3];
+    double corners[8][3], corners_w[8][3];
+    double pose_q[4], pose_t[3];
+    double pose_without_yaw_q[4], pose_without_yaw_t[3];
+} eao_object_cuboid_rec; /* 752 bytes */
+eao_status eao_object_cuboids_batch(int32_t n_obj, const eao_object_cuboid_desc* objs, eao_object_cuboid_rec* recs);
+/* a batch of one */
+eao_status eao_object_cuboids(const eao_object_cuboid_desc* obj, eao_object_cuboid_rec* rec);
+/* Object_Map::WhetherOverlap (src/Object.cc:1954-1970) over every ordered pair of m objects, with the three overlap extents of
+ * LocalMapping::WhetherOverlapObject (src/LocalMapping.cc:858-877): the matrix Tracking's step 10.3 (src/Tracking.cc:2093-2103) and the mapping thread walk with
+ * m^2 scalar calls.  verdict[i * m + j] = 1 when i != j, eligible[i] and eligible[j] are non-zero and |dc| < l / 2 + l' / 2 holds on all three axes (`<` is
+ * strict: touching boxes do not overlap); extents (optional) receives sum_half - dis per axis at 3 * (i * m + j), written only where the verdict is 1.
+ * DealTwoOverlapObjs and the loops' early `break` stay with the caller.  Refused: a negative m or one above EAO_OBJECT_OVERLAP_MAX_ROWS, a null pointer where
+ * m > 0, a non-finite field of a row. */
+#define EAO_OBJECT_OVERLAP_MAX_ROWS 2048
+typedef struct {
+    double cuboid_center[3];      /* mCuboid3D.cuboidCenter */
+    float lenth, width, height;   /* mCuboid3D.lenth / width / height */
+    int32_t reserved;
+} eao_object_overlap_row; /* 40 bytes */
+eao_status eao_object_overlaps(int32_t m, const eao_object_overlap_row* rows, const uint8_t* eligible, uint8_t* verdict /* m * m */, float* extents /* optional, m * m * 3 */);
+/* Diagnostic (tools/bench_object_cuboid.py): after eao_object_cuboid_set_profiling(1) on this thread, the device time in ms of k_object_cuboids and
+ * k_object_overlaps of this thread's last calls that reached the device (-1 for a kernel that has not run since), from HIP events on its stream.  An event call
+ * that fails costs that measurement and never fails the product call.  EAO_ERR_INVALID when no slot is measured. */
+eao_status eao_object_cuboid_set_profiling(int32_t on);
+eao_status eao_object_cuboid_last_kernel_ms(float* kernel_ms /* 2 */);
+
+/* ---------------------------------------------------------------------------------------------------
  * yolox: what YOLOX::Detect (reference src/YOLOX.cc:369-410) does AROUND the network, on the device.  The network itself is the integrator's engine; it reads
  * the blob and writes the head output in HBM, and nothing of either crosses to the host.
  *   in front   StaticResize (:51-62): r = min(S / (cols * 1.0), S / (rows * 1.0)) stored as float, unpad = (int)(r * cols) -- a float product truncated: a

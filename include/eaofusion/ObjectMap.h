@@ -19,6 +19,7 @@
 // value with at<float>(0..2) (cv::Mat 3x1 CV_32F upstream).
 #pragma once
 
+#include <cmath>
 #include <cstddef>
 #include <cstdint>
 #include <mutex>
@@ -105,6 +106,168 @@ int IsolationForestDeleteOutliers(std::vector<ObjT*>& objs, bool biForest) {    
 template <class ObjT>
 int IsolationForestDeleteOutliers(ObjT& obj, bool biForest) {
     return IsolationForestDeleteOutliers(std::vector<ObjT*>(1, &obj), biForest);
+}
+
+// ---- Object_Map::ComputeMeanAndStandard (src/Object.cc:999-1235) with both of its calls of Object_Map::UpdateObjPose (:2243-2303) on top of
+// eao_object_cuboids_batch: the sums, deviations, extrema, corners and poses come from the device, bit for bit what upstream's loops compute; the erase of the bad
+// points (:1003-1024), the evaluation of Ryaw (:2250-2260, so that the caller's own cos(float) / sin(float) decide its bits) and the member writes stay here.
+//
+//   // src/Object.cc in an EAO-Fusion checkout: the bodies become forwards
+//   void Object_Map::ComputeMeanAndStandard() { eaofusion::ComputeMeanAndStandard<Converter>(*this); }
+//   // and, where the loop of :718-719 is restructured: eaofusion::RefineObjects<Converter>(objs, biForest) -- two library calls for all of a frame's objects
+//
+// ConvT is the conversion policy: ConvT::toSE3Quat(cv::Mat 4x4 CV_32F) builds mCuboid3D.pose and pose_without_yaw from the two matrices the library returns.  In a
+// checkout it is upstream's own Converter, so both members are upstream's by construction and this header names no Eigen or g2o type; the vector members are
+// assigned through their own type (deduced), constructed from three doubles as upstream constructs them.
+//
+// Every member is written on the path upstream takes: nothing past mStandar_* when the list is empty (:1050), the bounds only on the few-frames path of :1071 (the
+// record says which).  One difference: upstream reads GetWorldPos() of a point three times (:1012, :1034, :1134) and another thread may move it in between; here
+// it is read once, under mMutexMapPoints.  A refused call (a non-finite position; the return value is -1) leaves every member as it was; the bad points are
+// erased by then, as upstream erases them before it computes anything.
+//
+// ObjT in addition to the above: mCenter3D, mStandar_x / y / z, mCenterStandar_x / y / z, mCenterStandar, mObjectFrame (pointers to objects with _Pos), mMutex,
+// mCuboid3D (rotP, rotR, rotY, cuboidCenter, x_min .. z_max, lenth, width, height, corner_1 .. corner_8, corner_1_w .. corner_8_w, pose, pose_without_yaw,
+// mfRMax).  MapPointT in addition: isBad().
+namespace object_map_detail {
+
+// :1003-1024: the bad points leave the list under the mutex; the positions of the others in list order
+template <class ObjT>
+void gather_good(ObjT& obj, std::vector<float>& xyz) {
+    std::unique_lock<std::mutex> lock(obj.mMutexMapPoints);
+    for (auto pMP = obj.mvpMapObjectMappoints.begin(); pMP != obj.mvpMapObjectMappoints.end();) {
+        const auto pos = (*pMP)->GetWorldPos();
+        if ((*pMP)->isBad()) {
+            pMP = obj.mvpMapObjectMappoints.erase(pMP);
+        } else {
+            detail::push3(pos, xyz);
+            ++pMP;
+        }
+    }
+}
+
+// :2250-2260: upstream's expression, evaluated in float by the caller's own overloads; REigen widens each entry and Converter::toCvMat narrows it back unchanged
+template <class CuboidT>
+void ryaw(const CuboidT& c, float* R) {
+    using std::cos;
+    using std::sin;
+    float cp = cos(c.rotP);
+    float sp = sin(c.rotP);
+    float sr = sin(c.rotR);
+    float cr = cos(c.rotR);
+    float sy = sin(c.rotY);
+    float cy = cos(c.rotY);
+    R[0] = cp * cy; R[1] = (sr * sp * cy) - (cr * sy); R[2] = (cr * sp * cy) + (sr * sy);
+    R[3] = cp * sy; R[4] = (sr * sp * sy) + (cr * cy); R[5] = (cr * sp * sy) - (sr * cy);
+    R[6] = -sp; R[7] = sr * cp; R[8] = cr * cp;
+}
+
+template <class VecT>
+void set3(VecT& dst, const double* v) {
+    dst = VecT(v[0], v[1], v[2]);
+}
+
+template <class ConvT, class ObjT>
+void write_members(ObjT& obj, const eao_object_cuboid_rec& r) {
+    obj.mSumPointsPos = detail::mat_of(r.sum_pos, 3, 1);
+    obj.mCenter3D = detail::mat_of(r.center, 3, 1);
+    obj.mStandar_x = r.standar[0];
+    obj.mStandar_y = r.standar[1];
+    obj.mStandar_z = r.standar[2];
+    if (r.status == EAO_OBJECT_CUBOID_EMPTY) return;      // :1050
+    obj.mCenterStandar_x = r.center_standar[0];
+    obj.mCenterStandar_y = r.center_standar[1];
+    obj.mCenterStandar_z = r.center_standar[2];
+    auto& C = obj.mCuboid3D;
+    if (r.bounds_written) {      // :1095-1100
+        C.x_min = r.bounds[0]; C.x_max = r.bounds[1];
+        C.y_min = r.bounds[2]; C.y_max = r.bounds[3];
+        C.z_min = r.bounds[4]; C.z_max = r.bounds[5];
+    }
+    set3(C.corner_1, r.corners[0]); set3(C.corner_2, r.corners[1]); set3(C.corner_3, r.corners[2]); set3(C.corner_4, r.corners[3]);
+    set3(C.corner_5, r.corners[4]); set3(C.corner_6, r.corners[5]); set3(C.corner_7, r.corners[6]); set3(C.corner_8, r.corners[7]);
+    set3(C.corner_1_w, r.corners_w[0]); set3(C.corner_2_w, r.corners_w[1]); set3(C.corner_3_w, r.corners_w[2]); set3(C.corner_4_w, r.corners_w[3]);
+    set3(C.corner_5_w, r.corners_w[4]); set3(C.corner_6_w, r.corners_w[5]); set3(C.corner_7_w, r.corners_w[6]); set3(C.corner_8_w, r.corners_w[7]);
+    C.lenth = r.lenth;
+    C.width = r.width;
+    C.height = r.height;
+    set3(C.cuboidCenter, r.cuboid_center);
+    {
+        std::unique_lock<std::mutex> lock(obj.mMutex);      // UpdateObjPose's (:2245)
+        C.pose = ConvT::toSE3Quat(detail::mat_of(r.Twobj, 4, 4));
+        C.pose_without_yaw = ConvT::toSE3Quat(detail::mat_of(r.Twobj_without_yaw, 4, 4));
+    }
+    C.mfRMax = r.rmax;
+    obj.mCenterStandar = r.center_standar_dis;
+}
+
+}  // namespace object_map_detail
+
+// Object_Map::ComputeMeanAndStandard for every object of `objs` in ONE library call.  Returns 0, or -1 when the library refused the call.
+template <class ConvT, class ObjT>
+int ComputeMeanAndStandard(const std::vector<ObjT*>& objs) {
+    if (objs.empty()) return 0;
+    std::vector<std::vector<float>> points(objs.size()), centroids(objs.size());
+    std::vector<eao_object_cuboid_desc> descs(objs.size());
+    for (size_t j = 0; j < objs.size(); j++) {
+        ObjT& obj = *objs[j];
+        object_map_detail::gather_good(obj, points[j]);
+        for (size_t i = 0; i < obj.mObjectFrame.size(); i++) detail::push3(obj.mObjectFrame[i]->_Pos, centroids[j]);
+        eao_object_cuboid_desc& d = descs[j];
+        d.n_points = (int32_t)(points[j].size() / 3);
+        d.points = points[j].empty() ? nullptr : points[j].data();
+        d.n_centroids = (int32_t)(centroids[j].size() / 3);
+        d.centroids = centroids[j].empty() ? nullptr : centroids[j].data();
+        object_map_detail::ryaw(obj.mCuboid3D, d.Ryaw);
+        for (int k = 0; k < 3; k++) d.prev_cuboid_center[k] = obj.mCuboid3D.cuboidCenter[k];
+    }
+    std::vector<eao_object_cuboid_rec> recs(objs.size());
+    if (eao_object_cuboids_batch((int32_t)objs.size(), descs.data(), recs.data()) != EAO_OK) return -1;
+    for (size_t j = 0; j < objs.size(); j++) object_map_detail::write_members<ConvT>(*objs[j], recs[j]);
+    return 0;
+}
+
+template <class ConvT, class ObjT>
+int ComputeMeanAndStandard(std::vector<ObjT*>& objs) {      // (a non-const vector must not bind to the single-object form below)
+    return ComputeMeanAndStandard<ConvT>(static_cast<const std::vector<ObjT*>&>(objs));
+}
+
+// Object_Map::ComputeMeanAndStandard.
+template <class ConvT, class ObjT>
+int ComputeMeanAndStandard(ObjT& obj) {
+    return ComputeMeanAndStandard<ConvT>(std::vector<ObjT*>(1, &obj));
+}
+
+// The pair of :718-719 for all of a frame's objects: the forest and its erase, then the cuboids -- two library calls.  Returns the number of points the forest
+// erased, or -1 when either call was refused (the cuboids are asked for even behind a refused forest, as upstream's second line runs whatever the first did).
+template <class ConvT, class ObjT>
+int RefineObjects(const std::vector<ObjT*>& objs, bool biForest) {
+    const int erased = IsolationForestDeleteOutliers(objs, biForest);
+    const int done = ComputeMeanAndStandard<ConvT>(objs);
+    return (erased < 0 || done < 0) ? -1 : erased;
+}
+
+// Object_Map::WhetherOverlap (:1954-1970) over every ordered pair of `objs` in one library call: verdict[i * M + j], and where `extents` is given the three overlap
+// extents of src/LocalMapping.cc:873-875 at 3 * (i * M + j) (zero where the verdict is 0).  eligible[i] == 0 takes object i out of every pair (the callers' own
+// `continue`s: bad_3d, another class, ...).  DealTwoOverlapObjs and the loops' early `break` stay with the caller.  Returns the number of verdicts set, or -1.
+template <class ObjT>
+int OverlapMatrix(const std::vector<ObjT*>& objs, const std::vector<uint8_t>& eligible, std::vector<uint8_t>& verdict, std::vector<float>* extents = nullptr) {
+    const size_t M = objs.size();
+    verdict.assign(M * M, 0);
+    if (extents) extents->assign(3 * M * M, 0.0f);
+    if (M == 0) return 0;
+    if (eligible.size() != M) return -1;
+    std::vector<eao_object_overlap_row> rows(M);
+    for (size_t j = 0; j < M; j++) {
+        rows[j] = eao_object_overlap_row();
+        for (int k = 0; k < 3; k++) rows[j].cuboid_center[k] = objs[j]->mCuboid3D.cuboidCenter[k];
+        rows[j].lenth = objs[j]->mCuboid3D.lenth;
+        rows[j].width = objs[j]->mCuboid3D.width;
+        rows[j].height = objs[j]->mCuboid3D.height;
+    }
+    if (eao_object_overlaps((int32_t)M, rows.data(), eligible.data(), verdict.data(), extents ? extents->data() : nullptr) != EAO_OK) return -1;
+    int set = 0;
+    for (uint8_t v : verdict) set += v;
+    return set;
 }
 
 }  // namespace eaofusion

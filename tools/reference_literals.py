@@ -220,6 +220,25 @@ TABLES = {
         ("SURROUND_RATIO", "src/Tracking.cc", 1941, r"mBoxRect\) > ([0-9.]+)\)"),
         ("FEATURE_RECT_MIN_POINTS", "src/Tracking.cc", 1830, r"if \(x_pt\.size\(\) < (\d+)\)"),
     ]),
+    # a map object's cuboid: Object_Map::ComputeMeanAndStandard, UpdateObjPose and WhetherOverlap.  CORNER_<x><y><z>: the number of the corner that takes the
+    # named extremum on each axis (both the world-frame and the object-frame assignments)
+    "object_cuboid": [
+        ("FEW_FRAMES", "src/Object.cc", 1071, r"if \(this->mObjectFrame\.size\(\) < (\d+)\)", 1),
+        ("CENTER_DIVISOR", "src/Object.cc", 1093, r"\(x_max \+ x_min\) / (\d+), \(y_max \+ y_min\) / (\d+), \(z_max \+ z_min\) / (\d+)\);", 1),
+    ] + [("CORNER_%s" % key, "src/Object.cc", first + k, r"mCuboid3D\.corner_(\d+)%s = %sEigen::Vector3d\(x_%s%s, y_%s%s, z_%s%s\);"
+          % ((tail, mid) + tuple(v for axis in key.split("_") for v in (axis.lower(), suffix))), 1)
+         for first, tail, mid, suffix in ((1106, "", "", ""), (1115, "_w", "", ""), (1160, "", r"this->mCuboid3D\.pose \* ", "_obj"),
+                                          (1170, "_w", r"this->mCuboid3D\.pose_without_yaw \* ", "_obj"))
+         for k, key in enumerate(["MIN_MIN_MIN", "MAX_MIN_MIN", "MAX_MAX_MIN", "MIN_MAX_MIN", "MIN_MIN_MAX", "MAX_MIN_MAX", "MAX_MAX_MAX", "MIN_MAX_MAX"])] + [
+        ("CORNER_FAR_A", "src/Object.cc", 1185, r"cuboidCenter = \(mCuboid3D\.corner_(\d+) \+ mCuboid3D\.corner_(\d+)\) / (\d+);", 1),
+        ("CORNER_FAR_B", "src/Object.cc", 1185, r"cuboidCenter = \(mCuboid3D\.corner_(\d+) \+ mCuboid3D\.corner_(\d+)\) / (\d+);", 2),
+        ("CENTER_DIVISOR", "src/Object.cc", 1185, r"cuboidCenter = \(mCuboid3D\.corner_(\d+) \+ mCuboid3D\.corner_(\d+)\) / (\d+);", 3),
+        ("WITHOUT_YAW_X_FROM_CENTER3D", "src/Object.cc", 2293, r"Twobj_without_yaw\.at<float>\(0, 3\) = mCenter3D\.at<float>\((\d+)\);", 1),
+        ("WITHOUT_YAW_Y_FROM_CUBOID_CENTER", "src/Object.cc", 2294, r"Twobj_without_yaw\.at<float>\(1, 3\) = mCuboid3D\.cuboidCenter\[(\d+)\];", 1),
+        ("WITHOUT_YAW_Z_FROM_CENTER3D", "src/Object.cc", 2295, r"Twobj_without_yaw\.at<float>\(2, 3\) = mCenter3D\.at<float>\((\d+)\);", 1),
+        ("OVERLAP_HALF", "src/Object.cc", 1961, r"float sum_lenth_half = mCuboid3D\.lenth / (\d+) \+ CompareObj->mCuboid3D\.lenth / (\d+);", 1),
+        ("OVERLAP_HALF", "src/LocalMapping.cc", 862, r"float sum_lenth_half = Obj->mCuboid3D\.lenth/(\d+) \+ Obj2->mCuboid3D\.lenth/(\d+);", 1),
+    ],
     # YOLOX::Detect around the network, and what Tracking::GrabImageRGBD keeps of its result
     "yolox": [
         ("NMS_THRESH", "include/YOLOX.h", 33, r"#define NMS_THRESH ([0-9.]+)", 1),
