@@ -204,6 +204,27 @@ class ObjectOverlapRow(C.Structure):   # eao_object_overlap_row
     _fields_ = [("cuboid_center", C.c_double * 3), ("lenth", C.c_float), ("width", C.c_float), ("height", C.c_float), ("reserved", C.c_int32)]
 
 
+class ObjectPointsDesc(C.Structure):   # eao_object_points_desc
+    _fields_ = [("change_gate", C.c_int32), ("gate", C.c_int32), ("erase", C.c_int32), ("box_off_edge", C.c_int32), ("n_map", C.c_int32), ("n_cand", C.c_int32),
+                ("map_points", C.c_void_p), ("map_count", C.c_void_p), ("cand_points", C.c_void_p), ("cand_count", C.c_void_p), ("Tcw", C.c_float * 16),
+                ("fx", C.c_float), ("fy", C.c_float), ("cx", C.c_float), ("cy", C.c_float), ("cols", C.c_int32), ("rows", C.c_int32),
+                ("project_rect1", C.c_int32 * 4), ("box_rect", C.c_int32 * 4), ("center", C.c_float * 3), ("rmax", C.c_float), ("n_frames_after_push", C.c_int32),
+                ("lenth", C.c_float), ("width", C.c_float), ("height", C.c_float), ("pose_q", C.c_double * 4), ("pose_t", C.c_double * 3),
+                ("cuboid_center", C.c_double * 3), ("bounds", C.c_float * 6), ("overlap", C.c_float * 3), ("sum_pos", C.c_float * 3), ("reserved", C.c_int32),
+                ("survivors", C.c_void_p)]
+
+
+class ObjectPointsRec(C.Structure):   # eao_object_points_rec
+    _fields_ = [("status", C.c_int32), ("n_gated", C.c_int32), ("n_appended", C.c_int32), ("n_list", C.c_int32), ("n_erased", C.c_int32), ("n_survivors", C.c_int32),
+                ("rect2", C.c_int32 * 4), ("iou", C.c_float), ("iou2", C.c_float), ("sum_pos_appended", C.c_float * 3), ("sum_pos", C.c_float * 3),
+                ("reserved", C.c_int32 * 2)]
+
+
+class ObjectPointsOut(C.Structure):   # eao_object_points_out
+    _fields_ = [("rec", C.c_void_p), ("gate", C.c_void_p), ("target", C.c_void_p), ("count", C.c_void_p), ("list", C.c_void_p), ("erased", C.c_void_p),
+                ("survivors", C.c_void_p)]
+
+
 class YoloxCfg(C.Structure):   # eao_yolox_cfg
     _fields_ = [("input_size", C.c_int32), ("num_classes", C.c_int32), ("conf_thresh", C.c_float), ("nms_thresh", C.c_float),
                 ("max_proposals", C.c_int32), ("max_batch", C.c_int32)]
@@ -357,6 +378,10 @@ SYMBOLS = {
     "eao_object_overlaps": (_I, [_I, _P, _P, _P, _P]),
     "eao_object_cuboid_set_profiling": (_I, [_I]),
     "eao_object_cuboid_last_kernel_ms": (_I, [_P]),
+    "eao_object_points_update_batch": (_I, [_I, C.POINTER(ObjectPointsDesc), C.POINTER(ObjectPointsOut)]),
+    "eao_object_points_update": (_I, [C.POINTER(ObjectPointsDesc), C.POINTER(ObjectPointsOut)]),
+    "eao_object_points_set_profiling": (_I, [_I]),
+    "eao_object_points_last_kernel_ms": (_I, [_P]),
     "eao_yolox_cfg_default": (None, [C.POINTER(YoloxCfg)]),
     "eao_yolox_create": (_I, [C.POINTER(YoloxCfg), C.POINTER(_P)]),
     "eao_yolox_destroy": (None, [_P]),

@@ -16,6 +16,13 @@
 
 #include "../../include/eao_fusion.h"
 
+// the scalar steps csrc/object_points.hip runs on the device too compile for both sides; csrc/frame_objects.hip calls them on the host only
+#if defined(__HIPCC__)
+#define EAO_FO_HD __host__ __device__ inline
+#else
+#define EAO_FO_HD inline
+#endif
+
 namespace eao {
 namespace frame_objects {
 
@@ -40,8 +47,8 @@ constexpr int32_t kMaxBoxField = 1 << 15;         // box fields and the image's 
 constexpr float kMaxKeypoint = 1073741824.0f;     // 2^30: below it cvRound and the float -> int conversions of cv::Rect are defined
 
 // cv::Rect_<int>::contains(Point2f) (:3046): the point converts through saturate_cast<int> = cvRound (nearest, ties to even), then x <= px < x + width.
-inline int32_t cv_round(float v) { return (int32_t)std::nearbyintf(v); }      // (the default rounding mode; |v| < 2^30)
-inline bool contains(const int32_t* box, float px, float py) {
+EAO_FO_HD int32_t cv_round(float v) { return (int32_t)std::nearbyintf(v); }      // (the default rounding mode; |v| < 2^30)
+EAO_FO_HD bool contains(const int32_t* box, float px, float py) {
     const int32_t x = cv_round(px), y = cv_round(py);
     return box[0] <= x && x < box[0] + box[2] && box[1] <= y && y < box[1] + box[3];
 }
@@ -59,15 +66,15 @@ inline float mat_div(float sum, int32_t n) {
 }
 
 // (rect1 & rect2).area() (src/Converter.cc:196)
-inline int32_t area(const int32_t* b) { return b[2] * b[3]; }
-inline int32_t overlap_area(const int32_t* a, const int32_t* b) {
+EAO_FO_HD int32_t area(const int32_t* b) { return b[2] * b[3]; }
+EAO_FO_HD int32_t overlap_area(const int32_t* a, const int32_t* b) {
     const int32_t x1 = std::max(a[0], b[0]), y1 = std::max(a[1], b[1]);
     const int32_t w = std::min(a[0] + a[2], b[0] + b[2]) - x1, h = std::min(a[1] + a[3], b[1] + b[3]) - y1;
     return (w <= 0 || h <= 0) ? 0 : w * h;
 }
-inline float overlap_ratio(const int32_t* a, const int32_t* b) { const int32_t o = overlap_area(a, b); return (float)o / ((float)(area(a) + area(b) - o)); }
-inline float overlap_ratio_former(const int32_t* a, const int32_t* b) { return (float)overlap_area(a, b) / ((float)area(a)); }
-inline float overlap_ratio_latter(const int32_t* a, const int32_t* b) { return (float)overlap_area(a, b) / ((float)area(b)); }
+EAO_FO_HD float overlap_ratio(const int32_t* a, const int32_t* b) { const int32_t o = overlap_area(a, b); return (float)o / ((float)(area(a) + area(b) - o)); }
+EAO_FO_HD float overlap_ratio_former(const int32_t* a, const int32_t* b) { return (float)overlap_area(a, b) / ((float)area(a)); }
+EAO_FO_HD float overlap_ratio_latter(const int32_t* a, const int32_t* b) { return (float)overlap_area(a, b) / ((float)area(b)); }
 
 // the first loop of step 6 for one box (:1870-1878): the other boxes it overlaps by more than 0.05 of THEIR area.  0 / 0 is NaN and compares false.
 inline int32_t num_overlaps(int32_t n_box, const int32_t* boxes, int32_t f) {

@@ -15,6 +15,13 @@
 #include <cstdint>
 #include <cstring>
 
+// the projection and the rectangle compile for both sides: csrc/object_points.hip runs them inside its kernel
+#if defined(__HIPCC__)
+#define EAO_OA_HD __host__ __device__ inline
+#else
+#define EAO_OA_HD inline
+#endif
+
 namespace eao {
 namespace object_assoc {
 
@@ -100,7 +107,7 @@ inline bool any_nan(const float* xyz, size_t nPoints) {
 // ---- Object_Map::ComputeProjectRectFrame
 // :1617-1624 for one point.  Rcw * X + tcw is a cv::Mat product: accumulated in double, rounded to float once; 1.0 / z is a double
 // division rounded to float; u and v are float expressions rounded operation by operation.  The kernel runs the same statements.
-inline void project_point(const float* Tcw, float fx, float fy, float cx, float cy, const float* X, float* u, float* v) {
+EAO_OA_HD void project_point(const float* Tcw, float fx, float fy, float cx, float cy, const float* X, float* u, float* v) {
     float Pc[3];
     for (int r = 0; r < 3; r++) {
         const double acc = (double)Tcw[4 * r] * (double)X[0] + (double)Tcw[4 * r + 1] * (double)X[1] + (double)Tcw[4 * r + 2] * (double)X[2];
@@ -118,8 +125,8 @@ struct Extent {
     float uMin, uMax, vMin, vMax;
     uint32_t anyNan;
 };
-inline void extent_init(Extent& e) { e.uMin = e.vMin = INFINITY; e.uMax = e.vMax = -INFINITY; e.anyNan = 0; }
-inline void extent_add(Extent& e, float u, float v) {
+EAO_OA_HD void extent_init(Extent& e) { e.uMin = e.vMin = INFINITY; e.uMax = e.vMax = -INFINITY; e.anyNan = 0; }
+EAO_OA_HD void extent_add(Extent& e, float u, float v) {
     if (std::isnan(u) || std::isnan(v)) e.anyNan = 1;
     e.uMin = u < e.uMin ? u : e.uMin;
     e.uMax = u > e.uMax ? u : e.uMax;
@@ -128,10 +135,10 @@ inline void extent_add(Extent& e, float u, float v) {
 }
 
 // float -> int as cv::Rect_<int>'s constructor converts: defined when the truncated value is an int
-inline bool fits_int(float v) { return v >= -2147483648.0f && v < 2147483648.0f; }
+EAO_OA_HD bool fits_int(float v) { return v >= -2147483648.0f && v < 2147483648.0f; }
 
 // :1641-1650.  rect = {x, y, width, height}; written only with kRectOk.
-inline uint8_t finish_rect(const Extent& e, int32_t cols, int32_t rows, int32_t* rect) {
+EAO_OA_HD uint8_t finish_rect(const Extent& e, int32_t cols, int32_t rows, int32_t* rect) {
     if (e.anyNan) return kRectUndefined;      // std::sort over a NaN (:1634)
     float x_min = e.uMin, x_max = e.uMax, y_min = e.vMin, y_max = e.vMax;
     if (x_min < 0) x_min = 0;

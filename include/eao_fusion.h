@@ -1575,7 +1575,8 @@ eao_status eao_object_cuboids(const eao_object_cuboid_desc* obj, eao_object_cubo
  * LocalMapping::WhetherOverlapObject (src/LocalMapping.cc:858-877): the matrix Tracking's step 10.3 (src/Tracking.cc:2093-2103) and the mapping thread walk with
  * m^2 scalar calls.  verdict[i * m + j] = 1 when i != j, eligible[i] and eligible[j] are non-zero and |dc| < l / 2 + l' / 2 holds on all three axes (`<` is
  * strict: touching boxes do not overlap); extents (optional) receives sum_half - dis per axis at 3 * (i * m + j), written only where the verdict is 1.
- * DealTwoOverlapObjs and the loops' early `break` stay with the caller.  Refused: a negative m or one above EAO_OBJECT_OVERLAP_MAX_ROWS, a null pointer where
+ * DealTwoOverlapObjs' decisions and the loops' early `break` stay with the caller; its erases (BigToSmall, DivideEquallyTwoObjs) are the BOX and SHRUNK rules
+ * of eao_object_points_update_batch below.  Refused: a negative m or one above EAO_OBJECT_OVERLAP_MAX_ROWS, a null pointer where
  * m > 0, a non-finite field of a row. */
 #define EAO_OBJECT_OVERLAP_MAX_ROWS 2048
 typedef struct {
@@ -1589,6 +1590,103 @@ eao_status eao_object_overlaps(int32_t m, const eao_object_overlap_row* rows, co
  * that fails costs that measurement and never fails the product call.  EAO_ERR_INVALID when no slot is measured. */
 eao_status eao_object_cuboid_set_profiling(int32_t on);
 eao_status eao_object_cuboid_last_kernel_ms(float* kernel_ms /* 2 */);
+
+/* ---------------------------------------------------------------------------------------------------
+ * object_points: the update of a map object's point list (mvpMapObjectMappoints) on the device -- step 1, 3 and 4 of Object_Map::DataAssociateUpdate (reference
+ * src/Object.cc:1364-1436, :1460-1535, :1538-1589), step 1 of Object_Map::MergeTwoMapObjs (:1766-1821) and the erase loops of BigToSmall (:2070-2087) and
+ * DivideEquallyTwoObjs (:2096-2120) -- bit for bit what upstream's loops compute (csrc/object_points_internal.h holds the literal form; DESIGN.md section 4r
+ * states why the growing list can be compared all pairs at once).  A desc is one (map object, source) pair; its stages run in upstream's order and each is
+ * optional.  The entries are stateless; each host thread has its own stream and staging.  EAO_ERR_INVALID leaves every output untouched.  Two calls on the same
+ * arguments return the same bytes, on one thread or on several.
+ *
+ *   1. change_gate != 0 (:1364-1436, upstream's Flags 2 and 3): the candidates and then the list are projected under Tcw and the intrinsics, the extrema of u and
+ *      v are clamped (:1419-1426) and truncated as cv::Rect(float ...) does: rect2.  iou = bboxOverlapratio(project_rect1, rect2), iou2 =
+ *      bboxOverlapratioFormer(rect2, box_rect).  (iou < 0.5) && (iou2 < 0.8), compared in double, a NaN ratio comparing false, is status REJECTED: upstream's
+ *      `return false`, nothing else is computed.  A NaN projection, a conversion to int that is undefined, or no point at all (x_pt[0] of an empty vector) is
+ *      status UNDEFINED: only the status is set.
+ *   2. gate != NONE, per candidate j in order (:1460-1535, :1766-1821):
+ *        RADIUS   fDis > th * rmax skips it (gate[j] = 0); fDis = sqrt of the float squares of center - p (:1465-1466), th = 0.9f when n_frames_after_push > 5 and
+ *                 1.0f otherwise (:1468-1472)
+ *        CUBOID   |pose.inverse() * p| in double against 1.1 * lenth / 2, 1.1 * width / 2, 1.1 * height / 2 (:1771-1774)
+ *      count[j] = cand_count[j] + 1 where gate[j], cand_count[j] otherwise (what object_id_vector holds afterwards, :1492-1502).  A gated-in candidate is
+ *      compared in list order with the list as it stands: the n_map entries, then those appended before it.  Equality is countNonZero(a - b) == 0: componentwise
+ *      ==, so -0.0f equals +0.0f.  target[j] = the position in the final list of the first equal entry, or -1 for a candidate that is appended (and for one that
+ *      is gated out).  list = the final list as (source, index) pairs, source 0 = the map list, 1 = the candidates.  sum_pos_appended = sum_pos plus the appended
+ *      positions, float adds in append order (:1532).
+ *   3. erase != NONE, over the list after stage 2 in list order:
+ *        PROJECTION  (:1543-1588) only when box_off_edge != 0 (the caller's :1538-1541).  An entry whose count (map_count, or count[j] of an appended candidate)
+ *                    exceeds 8 stays.  Otherwise it is erased when 0 < u < cols, 0 < v < rows and !box_rect.contains(Point2f(u, v)) (cvRound, half-open).
+ *        BOX         (:2078-2081) erased when strictly inside bounds = x_min x_max y_min y_max z_min z_max
+ *        SHRUNK      (:2105-2110) erased when strictly inside cuboid_center -+ (lenth / 2 - overlap / 2) on all three axes (the half-extents in float, the
+ *                    bounds in double)
+ *      erased[k] per list position, survivors = the (source, index) pairs that stay, in order; sum_pos = sum_pos_appended minus the erased positions, float
+ *      subtractions in list order (:1577, PROJECTION only).  desc.survivors, where not NULL, receives the surviving positions, n_survivors x 3 floats: the
+ *      `points` of an eao_object_cuboid_desc.
+ * With a status other than DONE only the record is written.  A list entry that is the very MapPoint of a gated-in candidate shares its object_id_vector with it:
+ * the caller that needs the incremented count in stage 3 passes it in map_count.
+ * Refused with EAO_ERR_INVALID before anything is written: a negative count; a null pointer where a count is positive (map_count only with PROJECTION); a
+ * non-finite coordinate, pose, intrinsic, bound, extent, centre, sum or rmax; an unknown gate or erase; cols, rows or a rect field outside -2^15 .. 2^15 (a
+ * negative size); more than EAO_OBJECT_POINTS_MAX_DESCS descs or more than 2^27 points in one call (split it).  n_map == 0 and n_cand == 0 are valid. */
+#define EAO_OBJECT_POINTS_MAX_DESCS 65535
+#define EAO_OBJECT_POINTS_DONE 1
+#define EAO_OBJECT_POINTS_REJECTED 2
+#define EAO_OBJECT_POINTS_UNDEFINED 3
+#define EAO_OBJECT_POINTS_GATE_NONE 0
+#define EAO_OBJECT_POINTS_GATE_RADIUS 1
+#define EAO_OBJECT_POINTS_GATE_CUBOID 2
+#define EAO_OBJECT_POINTS_ERASE_NONE 0
+#define EAO_OBJECT_POINTS_ERASE_PROJECTION 1
+#define EAO_OBJECT_POINTS_ERASE_BOX 2
+#define EAO_OBJECT_POINTS_ERASE_SHRUNK 3
+#define EAO_OBJECT_POINTS_KEEP_COUNT 8           /* src/Object.cc:1555: a count above it keeps the point */
+#define EAO_OBJECT_POINTS_EDGE_PIXELS 25         /* :1538-1541: the caller's box_off_edge */
+typedef struct {
+    int32_t change_gate, gate, erase, box_off_edge;
+    int32_t n_map, n_cand;
+    const float* map_points;      /* n_map x 3: GetWorldPos() of mvpMapObjectMappoints in list order */
+    const int32_t* map_count;     /* n_map: object_id_vector[mnId], 0 where absent (PROJECTION only) */
+    const float* cand_points;     /* n_cand x 3 */
+    const int32_t* cand_count;    /* n_cand: object_id_vector[mnId] before the call, 0 where absent */
+    float Tcw[16];                /* row-major */
+    float fx, fy, cx, cy;
+    int32_t cols, rows;
+    int32_t project_rect1[4], box_rect[4];      /* x y width height */
+    float center[3], rmax;        /* mCenter3D, mCuboid3D.mfRMax (RADIUS) */
+    int32_t n_frames_after_push;  /* mObjectFrame.size() after :1451 (RADIUS) */
+    float lenth, width, height;   /* of the cuboid the stage reads: this object's (CUBOID), the other one's (SHRUNK) */
+    double pose_q[4], pose_t[3];  /* mCuboid3D.pose, x y z w (CUBOID) */
+    double cuboid_center[3];      /* the other object's (SHRUNK) */
+    float bounds[6];              /* the other object's (BOX) */
+    float overlap[3];             /* (SHRUNK) */
+    float sum_pos[3];             /* mSumPointsPos before the call */
+    int32_t reserved;             /* zero */
+    float* survivors;             /* optional, (n_map + n_cand) x 3 */
+} eao_object_points_desc;
+typedef struct {
+    int32_t status;
+    int32_t n_gated, n_appended, n_list, n_erased, n_survivors;
+    int32_t rect2[4];
+    float iou, iou2;
+    float sum_pos_appended[3], sum_pos[3];
+    int32_t reserved[2];          /* zero */
+} eao_object_points_rec; /* 80 bytes */
+typedef struct {
+    eao_object_points_rec* rec;
+    uint8_t* gate;                /* n_cand */
+    int32_t* target;              /* n_cand */
+    int32_t* count;               /* n_cand */
+    int32_t* list;                /* (n_map + n_cand) x 2, n_list pairs written */
+    uint8_t* erased;              /* n_map + n_cand, n_list written */
+    int32_t* survivors;           /* (n_map + n_cand) x 2, n_survivors pairs written */
+} eao_object_points_out;
+eao_status eao_object_points_update_batch(int32_t n, const eao_object_points_desc* descs, const eao_object_points_out* outs);
+/* a batch of one */
+eao_status eao_object_points_update(const eao_object_points_desc* desc, const eao_object_points_out* out);
+/* Diagnostic (tools/bench_object_points.py): after eao_object_points_set_profiling(1) on this thread, the device time in ms of k_object_points_match (-1 where
+ * the call ran fused) and k_object_points (or k_object_points_finish) of this thread's last call that reached the device, from HIP events on its stream.  An
+ * event call that fails costs that measurement and never fails the product call.  EAO_ERR_INVALID when no slot is measured. */
+eao_status eao_object_points_set_profiling(int32_t on);
+eao_status eao_object_points_last_kernel_ms(float* kernel_ms /* 2 */);
 
 /* ---------------------------------------------------------------------------------------------------
  * yolox: what YOLOX::Detect (reference src/YOLOX.cc:369-410) does AROUND the network, on the device.  The network itself is the integrator's engine; it reads

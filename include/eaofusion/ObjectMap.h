@@ -23,6 +23,7 @@
 #include <cstddef>
 #include <cstdint>
 #include <mutex>
+#include <unordered_map>
 #include <vector>
 
 #include "adapter_detail.h"
@@ -248,7 +249,8 @@ int RefineObjects(const std::vector<ObjT*>& objs, bool biForest) {
 
 // Object_Map::WhetherOverlap (:1954-1970) over every ordered pair of `objs` in one library call: verdict[i * M + j], and where `extents` is given the three overlap
 // extents of src/LocalMapping.cc:873-875 at 3 * (i * M + j) (zero where the verdict is 0).  eligible[i] == 0 takes object i out of every pair (the callers' own
-// `continue`s: bad_3d, another class, ...).  DealTwoOverlapObjs and the loops' early `break` stay with the caller.  Returns the number of verdicts set, or -1.
+// `continue`s: bad_3d, another class, ...).  DealTwoOverlapObjs' decisions and the loops' early `break` stay with the caller; the point erases behind them (BigToSmall,
+// DivideEquallyTwoObjs) are BigToSmall and DivideEquallyTwoObjs below.  Returns the number of verdicts set, or -1.
 template <class ObjT>
 int OverlapMatrix(const std::vector<ObjT*>& objs, const std::vector<uint8_t>& eligible, std::vector<uint8_t>& verdict, std::vector<float>* extents = nullptr) {
     const size_t M = objs.size();
@@ -268,6 +270,214 @@ int OverlapMatrix(const std::vector<ObjT*>& objs, const std::vector<uint8_t>& el
     int set = 0;
     for (uint8_t v : verdict) set += v;
     return set;
+}
+
+// ---- The update of mvpMapObjectMappoints on top of eao_object_points_update: Object_Map::DataAssociateUpdate (src/Object.cc:1352-1601), step 1 of
+// MergeTwoMapObjs (:1766-1821), BigToSmall (:2043-2090) and DivideEquallyTwoObjs (:2094-2121).  The change gate, the gates of the candidates, the comparison of
+// every candidate with the growing list, the erase rules and the float sums come from the device, bit for bit what upstream's loops compute (DESIGN.md section
+// 4r); the writes into the map points and the object stay here, in upstream's order.
+//
+//   // src/Object.cc in an EAO-Fusion checkout
+//   bool Object_Map::DataAssociateUpdate(Object_2D* ObjectFrame, Frame& mCurrentFrame, cv::Mat& image, int Flag) {
+//       if ((Flag != 1) && (Flag != 4)) this->ComputeProjectRectFrame(image, mCurrentFrame);      // :1371, as before
+//       return eaofusion::DataAssociateUpdate<Converter>(*this, ObjectFrame, mCurrentFrame, image, Flag, biForest, [&] { /* step 2, :1439-1457; false = :1454 */ }) > 0;
+//   }
+//
+// What stays the caller's: step 2 of DataAssociateUpdate (mnLastAddID, mLastRect, mnConfidence, mObjectFrame; handed in as `step2`, which runs where upstream runs
+// it: behind the change gate, before the first write), the cv::circle debug draw, mAssMapObjCenter and mvObjectFrame (:1598-1599), steps 2 to 5 of MergeTwoMapObjs,
+// the corner members BigToSmall reads for nothing.  One difference: GetWorldPos() of a point is read once per call, not once per comparison.
+//
+// ObjT in addition to the above: mnId, mvpMapCurrentNewMappoints, mRectProject, mCuboid3D.pose with rotation().x() .. w() and translation()[k].  MapPointT in
+// addition: object_id, object_class, object_id_vector (std::map<int, int>), have_feature, feature.  Obj2DT: _class_id, Obj_c_MapPonits, mBox, mBoxRect.  FrameT:
+// mTcw, fx, fy, cx, cy.  ImageT: cols, rows.  Every function returns -1 when the library refused the call; nothing is written then.
+namespace object_map_detail {
+
+template <class MapPointT>
+int32_t id_count(const MapPointT& mp, int id) {
+    const auto sit = mp.object_id_vector.find(id);
+    return sit == mp.object_id_vector.end() ? 0 : (int32_t)sit->second;
+}
+
+// one call of the entry for one object: the lists as gathered, the outputs sized for them
+struct PointsCall {
+    eao_object_points_desc d = eao_object_points_desc();
+    eao_object_points_rec rec = eao_object_points_rec();
+    std::vector<float> map_points, cand_points, survivors_xyz;
+    std::vector<int32_t> map_count, cand_count, target, count, list, survivors;
+    std::vector<uint8_t> gate, erased;
+
+    template <class ObjT>
+    void gather_list(const ObjT& obj) {
+        for (size_t i = 0; i < obj.mvpMapObjectMappoints.size(); i++) {
+            detail::push3(obj.mvpMapObjectMappoints[i]->GetWorldPos(), map_points);
+            map_count.push_back(id_count(*obj.mvpMapObjectMappoints[i], obj.mnId));
+        }
+        for (int k = 0; k < 3; k++) d.sum_pos[k] = obj.mSumPointsPos.template at<float>(k);
+    }
+    template <class ObjT, class MapPointT>
+    void gather_candidates(const ObjT& obj, const std::vector<MapPointT*>& cand) {
+        for (size_t j = 0; j < cand.size(); j++) {
+            detail::push3(cand[j]->GetWorldPos(), cand_points);
+            cand_count.push_back(id_count(*cand[j], obj.mnId));
+        }
+    }
+    bool run() {
+        const size_t M = map_count.size(), C = cand_count.size();
+        d.n_map = (int32_t)M;
+        d.n_cand = (int32_t)C;
+        d.map_points = M ? map_points.data() : nullptr;
+        d.map_count = M ? map_count.data() : nullptr;
+        d.cand_points = C ? cand_points.data() : nullptr;
+        d.cand_count = C ? cand_count.data() : nullptr;
+        gate.assign(C + 1, 0); target.assign(C + 1, -1); count.assign(C + 1, 0);
+        list.assign(2 * (M + C) + 2, 0); erased.assign(M + C + 1, 0); survivors.assign(2 * (M + C) + 2, 0); survivors_xyz.assign(3 * (M + C) + 3, 0.0f);
+        d.survivors = survivors_xyz.data();
+        eao_object_points_out o = eao_object_points_out();
+        o.rec = &rec; o.gate = gate.data(); o.target = target.data(); o.count = count.data();
+        o.list = list.data(); o.erased = erased.data(); o.survivors = survivors.data();
+        return eao_object_points_update(&d, &o) == EAO_OK;
+    }
+};
+
+// :1484-1535 / :1779-1820 with the device's answers: the writes of the candidate loop in candidate order, then the appended points in append order
+template <class ObjT, class MapPointT>
+void apply_append(ObjT& obj, const std::vector<MapPointT*>& cand, const PointsCall& c, bool current_new) {
+    const size_t M = c.map_count.size();
+    auto source = [&](int32_t at) -> MapPointT* { return c.list[2 * at] == 0 ? obj.mvpMapObjectMappoints[(size_t)c.list[2 * at + 1]] : cand[(size_t)c.list[2 * at + 1]]; };
+    std::vector<MapPointT*> final_list((size_t)c.rec.n_list);
+    for (int32_t k = 0; k < c.rec.n_list; k++) final_list[(size_t)k] = source(k);
+    std::unique_lock<std::mutex> lock(obj.mMutexMapPoints);
+    for (size_t j = 0; j < cand.size(); j++) {
+        if (!c.gate[j]) continue;
+        MapPointT* pMP = cand[j];
+        pMP->object_id = obj.mnId;
+        pMP->object_class = obj.mnClass;
+        pMP->object_id_vector[pMP->object_id] = c.count[j];      // erase + insert of sit_sec + 1, or insert of 1
+        if (c.target[j] >= 0) {
+            MapPointT* old = final_list[(size_t)c.target[j]];
+            old->have_feature = pMP->have_feature;
+            old->feature = pMP->feature;
+        }
+    }
+    for (size_t k = M; k < final_list.size(); k++) {
+        obj.mvpMapObjectMappoints.push_back(final_list[k]);
+        if (current_new) obj.mvpMapCurrentNewMappoints.push_back(final_list[k]);
+    }
+}
+
+// the erases of :1543-1588, :2070-2087, :2096-2120 with the device's flags over the list as apply_append left it, and mSumPointsPos
+template <class ObjT>
+void apply_erase(ObjT& obj, const PointsCall& c) {
+    std::unique_lock<std::mutex> lock(obj.mMutexMapPoints);
+    size_t at = 0;
+    for (auto pMP = obj.mvpMapObjectMappoints.begin(); pMP != obj.mvpMapObjectMappoints.end(); at++) {
+        if (at < (size_t)c.rec.n_list && c.erased[at]) pMP = obj.mvpMapObjectMappoints.erase(pMP);
+        else ++pMP;
+    }
+    for (int k = 0; k < 3; k++) obj.mSumPointsPos.template at<float>(k) = c.rec.sum_pos[k];
+}
+
+// A list entry that is itself a gated-in candidate shares its object_id_vector with it: step 3 has raised the count that step 4 reads (:1550-1559).  The library
+// knows positions, not identities, and was given the count of before; an entry it erased whose raised count exceeds the bound stays.  (mSumPointsPos then holds one
+// subtraction too many until ComputeMeanAndStandard, which follows at once, sums it anew.)
+template <class ObjT, class MapPointT>
+void keep_recounted(const ObjT& obj, const std::vector<MapPointT*>& cand, PointsCall& c) {
+    std::unordered_map<const MapPointT*, int32_t> raised;
+    for (size_t j = 0; j < cand.size(); j++)
+        if (c.gate[j]) raised[cand[j]]++;
+    for (size_t k = 0; k < c.map_count.size(); k++) {
+        if (!c.erased[k]) continue;
+        const auto it = raised.find(obj.mvpMapObjectMappoints[k]);
+        if (it != raised.end() && c.map_count[k] + it->second > EAO_OBJECT_POINTS_KEEP_COUNT) {
+            c.erased[k] = 0;
+            c.rec.n_erased--;
+            c.rec.n_survivors++;
+        }
+    }
+}
+
+template <class CuboidT>
+void read_cuboid_pose(const CuboidT& C, eao_object_points_desc& d) {
+    d.pose_q[0] = C.pose.rotation().x(); d.pose_q[1] = C.pose.rotation().y(); d.pose_q[2] = C.pose.rotation().z(); d.pose_q[3] = C.pose.rotation().w();
+    for (int k = 0; k < 3; k++) d.pose_t[k] = C.pose.translation()[k];
+    d.lenth = C.lenth; d.width = C.width; d.height = C.height;
+}
+
+}  // namespace object_map_detail
+
+// Object_Map::DataAssociateUpdate.  1: associated (upstream's true); 0: upstream's `return false` (another class, the change gate, or step2() said so); -1: refused.
+template <class ConvT, class ObjT, class Obj2DT, class FrameT, class ImageT, class Step2T>
+int DataAssociateUpdate(ObjT& obj, Obj2DT* ObjectFrame, FrameT& mCurrentFrame, const ImageT& image, int Flag, bool biForest, Step2T step2) {
+    if (ObjectFrame->_class_id != obj.mnClass) return 0;      // :1357
+    object_map_detail::PointsCall c;
+    eao_object_points_desc& d = c.d;
+    d.change_gate = ((Flag != 1) && (Flag != 4)) ? 1 : 0;      // :1364
+    d.gate = EAO_OBJECT_POINTS_GATE_RADIUS;
+    d.erase = EAO_OBJECT_POINTS_ERASE_PROJECTION;
+    d.box_off_edge = ((ObjectFrame->mBox.x > EAO_OBJECT_POINTS_EDGE_PIXELS) && (ObjectFrame->mBox.y > EAO_OBJECT_POINTS_EDGE_PIXELS) && (ObjectFrame->mBox.x + ObjectFrame->mBox.width < image.cols - EAO_OBJECT_POINTS_EDGE_PIXELS) &&
+                      (ObjectFrame->mBox.y + ObjectFrame->mBox.height < image.rows - EAO_OBJECT_POINTS_EDGE_PIXELS)) ? 1 : 0;      // :1538-1541
+    detail::read44(mCurrentFrame.mTcw, d.Tcw);
+    d.fx = mCurrentFrame.fx; d.fy = mCurrentFrame.fy; d.cx = mCurrentFrame.cx; d.cy = mCurrentFrame.cy;
+    d.cols = image.cols; d.rows = image.rows;
+    d.project_rect1[0] = obj.mRectProject.x; d.project_rect1[1] = obj.mRectProject.y; d.project_rect1[2] = obj.mRectProject.width; d.project_rect1[3] = obj.mRectProject.height;
+    d.box_rect[0] = ObjectFrame->mBoxRect.x; d.box_rect[1] = ObjectFrame->mBoxRect.y; d.box_rect[2] = ObjectFrame->mBoxRect.width; d.box_rect[3] = ObjectFrame->mBoxRect.height;
+    for (int k = 0; k < 3; k++) d.center[k] = obj.mCenter3D.template at<float>(k);
+    d.rmax = obj.mCuboid3D.mfRMax;
+    d.n_frames_after_push = (int32_t)obj.mObjectFrame.size() + 1;      // step 2 pushes before step 3 reads the size (:1451, :1469)
+    c.gather_list(obj);
+    c.gather_candidates(obj, ObjectFrame->Obj_c_MapPonits);
+    if (!c.run()) return -1;
+    if (c.rec.status != EAO_OBJECT_POINTS_DONE) return 0;      // :1435 (an undefined projection associates nothing either)
+    if (!step2()) return 0;                                    // :1454
+    object_map_detail::keep_recounted(obj, ObjectFrame->Obj_c_MapPonits, c);
+    object_map_detail::apply_append(obj, ObjectFrame->Obj_c_MapPonits, c, true);
+    object_map_detail::apply_erase(obj, c);
+    if (ComputeMeanAndStandard<ConvT>(obj) < 0) return -1;              // :1593 (it sums mSumPointsPos anew, :1001)
+    if (IsolationForestDeleteOutliers(obj, biForest) < 0) return -1;    // :1596
+    return 1;
+}
+
+// Step 1 of Object_Map::MergeTwoMapObjs (:1766-1821): RepeatObj's points into obj.  Returns the number of points appended, or -1.
+template <class ObjT>
+int MergeTwoMapObjsPoints(ObjT& obj, ObjT& RepeatObj) {
+    object_map_detail::PointsCall c;
+    c.d.gate = EAO_OBJECT_POINTS_GATE_CUBOID;
+    object_map_detail::read_cuboid_pose(obj.mCuboid3D, c.d);
+    c.gather_list(obj);
+    c.gather_candidates(obj, RepeatObj.mvpMapObjectMappoints);
+    if (!c.run()) return -1;
+    object_map_detail::apply_append(obj, RepeatObj.mvpMapObjectMappoints, c, false);
+    for (int k = 0; k < 3; k++) obj.mSumPointsPos.template at<float>(k) = c.rec.sum_pos[k];
+    return c.rec.n_appended;
+}
+
+// Object_Map::BigToSmall (:2043-2090): the points of obj strictly inside SmallObj's bounds leave it, then ComputeMeanAndStandard.  Returns the number erased, or -1.
+template <class ConvT, class ObjT>
+int BigToSmall(ObjT& obj, const ObjT& SmallObj) {
+    object_map_detail::PointsCall c;
+    c.d.erase = EAO_OBJECT_POINTS_ERASE_BOX;
+    const auto& S = SmallObj.mCuboid3D;
+    c.d.bounds[0] = S.x_min; c.d.bounds[1] = S.x_max; c.d.bounds[2] = S.y_min; c.d.bounds[3] = S.y_max; c.d.bounds[4] = S.z_min; c.d.bounds[5] = S.z_max;
+    c.gather_list(obj);
+    if (!c.run()) return -1;
+    object_map_detail::apply_erase(obj, c);
+    if (ComputeMeanAndStandard<ConvT>(obj) < 0) return -1;      // :2089
+    return c.rec.n_erased;
+}
+
+// Object_Map::DivideEquallyTwoObjs (:2094-2121).  Returns the number erased, or -1.
+template <class ObjT>
+int DivideEquallyTwoObjs(ObjT& obj, const ObjT& AnotherObj, float overlap_x, float overlap_y, float overlap_z) {
+    object_map_detail::PointsCall c;
+    c.d.erase = EAO_OBJECT_POINTS_ERASE_SHRUNK;
+    const auto& A = AnotherObj.mCuboid3D;
+    for (int k = 0; k < 3; k++) c.d.cuboid_center[k] = A.cuboidCenter[k];
+    c.d.lenth = A.lenth; c.d.width = A.width; c.d.height = A.height;
+    c.d.overlap[0] = overlap_x; c.d.overlap[1] = overlap_y; c.d.overlap[2] = overlap_z;
+    c.gather_list(obj);
+    if (!c.run()) return -1;
+    object_map_detail::apply_erase(obj, c);
+    return c.rec.n_erased;
 }
 
 }  // namespace eaofusion

@@ -239,6 +239,21 @@ TABLES = {
         ("OVERLAP_HALF", "src/Object.cc", 1961, r"float sum_lenth_half = mCuboid3D\.lenth / (\d+) \+ CompareObj->mCuboid3D\.lenth / (\d+);", 1),
         ("OVERLAP_HALF", "src/LocalMapping.cc", 862, r"float sum_lenth_half = Obj->mCuboid3D\.lenth/(\d+) \+ Obj2->mCuboid3D\.lenth/(\d+);", 1),
     ],
+    # the update of a map object's point list: Object_Map::DataAssociateUpdate, MergeTwoMapObjs
+    "object_points": [
+        ("MIN_IOU", "src/Object.cc", 1434, r"if \(\(fIou < ([0-9.]+)\) && \(fIou2 < ([0-9.]+)\)\)", 1),
+        ("MIN_IOU_FORMER", "src/Object.cc", 1434, r"if \(\(fIou < ([0-9.]+)\) && \(fIou2 < ([0-9.]+)\)\)", 2),
+        ("MANY_FRAMES", "src/Object.cc", 1469, r"if \(mObjectFrame\.size\(\) > (\d+)\)", 1),
+        ("TH_MANY_FRAMES", "src/Object.cc", 1470, r"th = ([0-9.]+);", 1),
+        ("EDGE_PIXELS", "src/Object.cc", 1538, r"if \(\(ObjectFrame->mBox\.x > (\d+)\) && \(ObjectFrame->mBox\.y > (\d+)\) &&", 1),
+        ("EDGE_PIXELS", "src/Object.cc", 1538, r"if \(\(ObjectFrame->mBox\.x > (\d+)\) && \(ObjectFrame->mBox\.y > (\d+)\) &&", 2),
+        ("EDGE_PIXELS", "src/Object.cc", 1539, r"mBox\.width < image\.cols - (\d+)\) &&", 1),
+        ("EDGE_PIXELS", "src/Object.cc", 1540, r"mBox\.height < image\.rows - (\d+)\)\)", 1),
+        ("KEEP_COUNT", "src/Object.cc", 1555, r"if \(sit_sec > (\d+)\)", 1),
+        ("CUBOID_SLACK", "src/Object.cc", 1772, r"abs\(scale\[0\]\) > ([0-9.]+) \* this->mCuboid3D\.lenth / 2\)", 1),
+        ("CUBOID_SLACK", "src/Object.cc", 1773, r"abs\(scale\[1\]\) > ([0-9.]+) \* this->mCuboid3D\.width / 2\)", 1),
+        ("CUBOID_SLACK", "src/Object.cc", 1774, r"abs\(scale\[2\]\) > ([0-9.]+) \* this->mCuboid3D\.height / 2\)\)", 1),
+    ],
     # YOLOX::Detect around the network, and what Tracking::GrabImageRGBD keeps of its result
     "yolox": [
         ("NMS_THRESH", "include/YOLOX.h", 33, r"#define NMS_THRESH ([0-9.]+)", 1),
