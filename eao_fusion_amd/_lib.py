@@ -225,6 +225,19 @@ class ObjectPointsOut(C.Structure):   # eao_object_points_out
                 ("survivors", C.c_void_p)]
 
 
+class ObjectChainDesc(C.Structure):   # eao_object_chain_desc
+    _fields_ = [("points", ObjectPointsDesc), ("map_bad", C.c_void_p), ("cand_bad", C.c_void_p), ("cand_alias", C.c_void_p), ("n_centroids", C.c_int32),
+                ("class_id", C.c_int32), ("centroids", C.c_void_p), ("Ryaw", C.c_float * 9), ("bi_forest", C.c_int32), ("prev_cuboid_center", C.c_double * 3)]
+
+
+class ObjectChainRec(C.Structure):   # eao_object_chain_rec
+    _fields_ = [("n_final", C.c_int32), ("forest_status", C.c_int32), ("removed", C.c_int32), ("reserved", C.c_int32)]
+
+
+class ObjectChainOut(C.Structure):   # eao_object_chain_out
+    _fields_ = [("points", ObjectPointsOut), ("rec", C.c_void_p), ("final", C.c_void_p), ("cuboid", C.c_void_p), ("forest_flags", C.c_void_p), ("scores", C.c_void_p)]
+
+
 class YoloxCfg(C.Structure):   # eao_yolox_cfg
     _fields_ = [("input_size", C.c_int32), ("num_classes", C.c_int32), ("conf_thresh", C.c_float), ("nms_thresh", C.c_float),
                 ("max_proposals", C.c_int32), ("max_batch", C.c_int32)]
@@ -382,6 +395,10 @@ SYMBOLS = {
     "eao_object_points_update": (_I, [C.POINTER(ObjectPointsDesc), C.POINTER(ObjectPointsOut)]),
     "eao_object_points_set_profiling": (_I, [_I]),
     "eao_object_points_last_kernel_ms": (_I, [_P]),
+    "eao_object_update_chain_batch": (_I, [_I, C.POINTER(ObjectChainDesc), C.POINTER(ObjectChainOut)]),
+    "eao_object_update_chain": (_I, [C.POINTER(ObjectChainDesc), C.POINTER(ObjectChainOut)]),
+    "eao_object_chain_set_profiling": (_I, [_I]),
+    "eao_object_chain_last_kernel_ms": (_I, [_P]),
     "eao_yolox_cfg_default": (None, [C.POINTER(YoloxCfg)]),
     "eao_yolox_create": (_I, [C.POINTER(YoloxCfg), C.POINTER(_P)]),
     "eao_yolox_destroy": (None, [_P]),

@@ -21,16 +21,6 @@ namespace {
 
 using namespace eao::iforest;
 
-struct ObjDev {
-    uint32_t ptStart, n, sampleSize, maxDepth;
-    uint32_t treeBase, treeCount, inLds, idsBytes;
-    uint64_t nodeBase;      // in NodeDev
-    uint64_t wsBase;        // in uint16
-    uint32_t cBase, stride; // C table offset in doubles; NodeDev per tree
-    uint32_t pad[2];
-};
-static_assert(sizeof(ObjDev) == 64, "ObjDev layout");
-
 static_assert(kTreeCount == EAO_OBJECT_IFOREST_TREES && kSeed == EAO_OBJECT_IFOREST_SEED && kMinPoints == EAO_OBJECT_IFOREST_MIN_POINTS &&
                   kMaxPoints == EAO_IFOREST_MAX_POINTS && kExemptClasses[0] == EAO_OBJECT_IFOREST_EXEMPT_CLASS_A &&
                   kExemptClasses[1] == EAO_OBJECT_IFOREST_EXEMPT_CLASS_B && kExemptClasses[2] == EAO_OBJECT_IFOREST_EXEMPT_CLASS_C,
@@ -145,6 +135,7 @@ __global__ __launch_bounds__(64) void k_iforest_build(const ObjDev* __restrict__
     const unsigned obj = treeObj[g];
     const ObjDev o = objs[obj];
     const unsigned tree = g - o.treeBase;
+    if (tree >= o.treeCount) return;      // (uniform) an object of a chain that the rules skip: its trees are launched before its size is known
     const unsigned N = o.n, S = o.sampleSize, maxDepth = o.maxDepth;
     const float* pin = xyz + (size_t)o.ptStart * 3;
     NodeDev* out = nodes + o.nodeBase + (size_t)tree * o.stride;
@@ -383,6 +374,28 @@ __global__ __launch_bounds__(64 * kScoreWaves) void k_iforest_score(const ObjDev
     if (lane == 0) totals[(size_t)o.ptStart + i] = total;
 }
 
+}  // namespace
+
+namespace eao {
+namespace iforest {
+
+hipError_t enqueue_build(hipStream_t stream, const ObjDev* objs, const unsigned* treeObj, const unsigned* seeds, const float* xyz, NodeDev* nodes, unsigned* nodeCount,
+                         unsigned* failed, unsigned short* ws, unsigned long long* stamps, unsigned n_trees, size_t dyn_lds) {
+    hipLaunchKernelGGL(k_iforest_build, dim3(n_trees), dim3(64), dyn_lds, stream, objs, treeObj, seeds, xyz, nodes, nodeCount, failed, ws, stamps);
+    return hipGetLastError();
+}
+
+hipError_t enqueue_score(hipStream_t stream, const ObjDev* objs, const float* xyz, const NodeDev* nodes, const double* cTable, const unsigned* failed, double* totals,
+                         unsigned max_n, unsigned n_obj) {
+    hipLaunchKernelGGL(k_iforest_score, dim3(eao::cdiv((int)max_n, kScoreWaves), n_obj), dim3(64 * kScoreWaves), 0, stream, objs, xyz, nodes, cTable, failed, totals);
+    return hipGetLastError();
+}
+
+}  // namespace iforest
+}  // namespace eao
+
+namespace {
+
 struct Job {
     const float* xyz;      // n * 3, host
     uint32_t n, treeCount, seed, sampleSize;
@@ -460,14 +473,12 @@ eao_status run_forests(const std::vector<Job>& jobs, bool wantNodes, Built& B) {
     eao::Drain drain(ctx.stream);
     EAO_HIP(hipMemcpyAsync(d, h, inEnd, hipMemcpyHostToDevice, ctx.stream));
     ctx.clock.mark(0, ctx.stream);
-    hipLaunchKernelGGL(k_iforest_build, dim3((unsigned)nTrees), dim3(64), dynLds, ctx.stream, (const ObjDev*)(d + oObj), (const unsigned*)(d + oTo),
-                       (const unsigned*)(d + oSeed), (const float*)(d + oXyz), ctx.nodes.p, (unsigned*)(d + oCnt), (unsigned*)(d + oFail), ctx.ws.p,
-                       profiling ? ctx.stamps.p : nullptr);
-    EAO_HIP(hipGetLastError());      // (the scores are not launched over trees that were not built)
+    // (the scores are not launched over trees that were not built)
+    EAO_HIP(enqueue_build(ctx.stream, (const ObjDev*)(d + oObj), (const unsigned*)(d + oTo), (const unsigned*)(d + oSeed), (const float*)(d + oXyz), ctx.nodes.p,
+                          (unsigned*)(d + oCnt), (unsigned*)(d + oFail), ctx.ws.p, profiling ? ctx.stamps.p : nullptr, (unsigned)nTrees, dynLds));
     ctx.clock.mark(1, ctx.stream);
-    hipLaunchKernelGGL(k_iforest_score, dim3(eao::cdiv((int)maxN, kScoreWaves), (unsigned)nJobs), dim3(64 * kScoreWaves), 0, ctx.stream, (const ObjDev*)(d + oObj),
-                       (const float*)(d + oXyz), (const NodeDev*)ctx.nodes.p, (const double*)(d + oC), (const unsigned*)(d + oFail), (double*)(d + oTot));
-    EAO_HIP(hipGetLastError());
+    EAO_HIP(enqueue_score(ctx.stream, (const ObjDev*)(d + oObj), (const float*)(d + oXyz), (const NodeDev*)ctx.nodes.p, (const double*)(d + oC), (const unsigned*)(d + oFail),
+                          (double*)(d + oTot), maxN, (unsigned)nJobs));
     ctx.clock.mark(2, ctx.stream);
     EAO_HIP(hipMemcpyAsync(h + oFail, d + oFail, end - oFail, hipMemcpyDeviceToHost, ctx.stream));
     EAO_HIP(drain.wait(eao::Drain::Latency));

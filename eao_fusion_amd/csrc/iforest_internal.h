@@ -17,6 +17,12 @@
 #include <cstring>
 #include <vector>
 
+#if defined(__HIPCC__)
+#define EAO_IF_HD __host__ __device__ inline
+#else
+#define EAO_IF_HD inline
+#endif
+
 namespace eao {
 namespace iforest {
 
@@ -119,6 +125,14 @@ inline void tree_seeds(uint32_t seed, uint32_t treeCount, uint32_t* out) {
 
 // IsolationTree::Build (:340)
 inline uint32_t max_depth(uint32_t sampleSize) { return (uint32_t)std::ceil(std::log2((double)sampleSize)); }
+// The same number without libm, for a sample size that only the device knows (csrc/object_chain.hip): the bits of sampleSize - 1.  log2 of a power of two is
+// exact and log2 is monotonic, so ceil(log2(S)) is the smallest d with 2^d >= S wherever log2(S) does not round up to an integer from below; a double has 53
+// bits and S < 2^32, so it does not.  tests/test_object_chain_reference_cpu.py holds the two forms equal for every S in 1 .. 32767.
+EAO_IF_HD uint32_t max_depth_int(uint32_t sampleSize) {
+    uint32_t d = 0;
+    for (uint32_t v = sampleSize - 1; v != 0 && sampleSize != 0; v >>= 1) d++;
+    return d;
+}
 
 // CalculateC (:103-118), with libm's log: the scorer reads a table of these, so its sums are upstream's
 inline double c_of(uint32_t n) {
@@ -153,7 +167,7 @@ struct NodeDev {
 };
 constexpr size_t kForestHeaderBytes = 16, kTreeHeaderBytes = 12;
 inline size_t stream_bytes(uint32_t treeCount, size_t totalNodes) { return kForestHeaderBytes + kTreeHeaderBytes * treeCount + sizeof(NodeRec) * totalNodes; }
-inline uint32_t max_nodes(uint32_t sampleSize) { return 2 * sampleSize - 1; }
+EAO_IF_HD uint32_t max_nodes(uint32_t sampleSize) { return 2 * sampleSize - 1; }
 
 // IsolationForest::Serialize (:532-560) over the kernel's node arrays: tree t owns nodes[t * stride .. + count[t])
 inline void write_stream(uint8_t* out, uint32_t treeCount, uint32_t sampleSize, const NodeDev* nodes, size_t stride, const uint32_t* count) {
@@ -194,14 +208,35 @@ struct LdsPlan {
     size_t bytes;             // ids + coordinates
     bool inLds;
 };
-inline LdsPlan lds_plan(uint32_t n, uint32_t sampleSize) {
+EAO_IF_HD LdsPlan lds_plan(uint32_t n, uint32_t sampleSize) {
     LdsPlan p;
-    p.idsEntries = std::max(n, 2 * sampleSize);
+    p.idsEntries = n > 2 * sampleSize ? n : 2 * sampleSize;
     p.idsBytes = ((size_t)p.idsEntries * 2 + 15) & ~(size_t)15;
     p.bytes = p.idsBytes + (size_t)sampleSize * 12;
     p.inLds = p.bytes <= kLdsBudget;
     return p;
 }
+
+// ---- what the kernels of csrc/iforest.hip read per object from device memory, for the callers that enqueue them: the file's own entries write it on the host,
+// the plan kernel of csrc/object_chain.hip on the device.  Tree g of the launch belongs to object treeObj[g]; a tree at or above treeCount leaves at once.
+struct ObjDev {
+    uint32_t ptStart, n, sampleSize, maxDepth;
+    uint32_t treeBase, treeCount, inLds, idsBytes;
+    uint64_t nodeBase;      // in NodeDev
+    uint64_t wsBase;        // in uint16
+    uint32_t cBase, stride; // C table offset in doubles; NodeDev per tree
+    uint32_t pad[2];
+};
+static_assert(sizeof(ObjDev) == 64, "ObjDev layout");
+
+#if defined(__HIPCC__)
+// dyn_lds: the largest LdsPlan::bytes among the objects whose plan is inLds; ws: the ids of those whose plan is not
+hipError_t enqueue_build(hipStream_t stream, const ObjDev* objs, const unsigned* treeObj, const unsigned* seeds, const float* xyz, NodeDev* nodes, unsigned* nodeCount,
+                         unsigned* failed, unsigned short* ws, unsigned long long* stamps, unsigned n_trees, size_t dyn_lds);
+// max_n: the largest n among the objects (at least 1)
+hipError_t enqueue_score(hipStream_t stream, const ObjDev* objs, const float* xyz, const NodeDev* nodes, const double* cTable, const unsigned* failed, double* totals,
+                         unsigned max_n, unsigned n_obj);
+#endif
 
 // ---- the forest on the host, in the sort-free form the kernel uses (tools/isolation_forest_walk.cpp; the timing tool's host baseline).
 // Returns false where Node::Build does (:167: a split above the maximum leaves the right child an empty range).

@@ -33,14 +33,6 @@ constexpr int kWaves = kBlock / 64;
 constexpr int kChunk = 1024;                 // list entries whose terms wait in LDS for the ordered adds
 constexpr int kNone = 0x7fffffff;            // the list position of a lane that has seen no point
 
-struct ObjDev {
-    int64_t pointStart, centroidStart;       // in entries of the packed lists
-    int32_t n, m;
-    float Ryaw[9];
-    int32_t pad;
-    double prev[3];
-};
-static_assert(sizeof(ObjDev) == 88, "ObjDev layout");
 static_assert(sizeof(eao_object_cuboid_rec) == 752, "record layout");
 static_assert(sizeof(eao_object_overlap_row) == 40, "row layout");
 constexpr int kRecWords = sizeof(eao_object_cuboid_rec) / 4;
@@ -108,6 +100,7 @@ __global__ __launch_bounds__(kBlock) void k_object_cuboids(const ObjDev* __restr
     __shared__ eao_object_cuboid_rec sRec;
     __shared__ Pose sPose[2];
     const ObjDev& O = objs[blockIdx.x];
+    if (O.skip) return;      // (uniform) an object of a chain whose point update did not finish
     const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
     const int n = O.n, m = O.m;
     const float* P = points + 3 * (size_t)O.pointStart;
@@ -244,6 +237,17 @@ thread_local ObjectCuboidCtx g_oc;
 
 }  // namespace
 
+namespace eao {
+namespace object_cuboid {
+
+hipError_t enqueue_cuboids(hipStream_t stream, const ObjDev* objs, const float* points, const float* centroids, eao_object_cuboid_rec* records, unsigned n_obj) {
+    hipLaunchKernelGGL(k_object_cuboids, dim3(n_obj), dim3(kBlock), 0, stream, objs, points, centroids, records);
+    return hipGetLastError();
+}
+
+}  // namespace object_cuboid
+}  // namespace eao
+
 extern "C" {
 
 eao_status eao_object_cuboids_batch(int32_t n_obj, const eao_object_cuboid_desc* objs, eao_object_cuboid_rec* recs) {
@@ -290,9 +294,7 @@ eao_status eao_object_cuboids_batch(int32_t n_obj, const eao_object_cuboid_desc*
     eao::Drain drain(ctx.stream);
     EAO_HIP(hipMemcpyAsync(d, h, inEnd, hipMemcpyHostToDevice, ctx.stream));
     ctx.clock.mark(0, ctx.stream);
-    hipLaunchKernelGGL(k_object_cuboids, dim3((unsigned)nO), dim3(kBlock), 0, ctx.stream, (const ObjDev*)(d + oObj), (const float*)(d + oPts), (const float*)(d + oCen),
-                       (eao_object_cuboid_rec*)(d + oRec));
-    EAO_HIP(hipGetLastError());
+    EAO_HIP(enqueue_cuboids(ctx.stream, (const ObjDev*)(d + oObj), (const float*)(d + oPts), (const float*)(d + oCen), (eao_object_cuboid_rec*)(d + oRec), (unsigned)nO));
     ctx.clock.mark(1, ctx.stream);
     EAO_HIP(hipMemcpyAsync(h + oRec, d + oRec, nO * sizeof(eao_object_cuboid_rec), hipMemcpyDeviceToHost, ctx.stream));
     EAO_HIP(drain.wait(eao::Drain::Latency));

@@ -203,6 +203,21 @@ EAO_OC_HD bool overlap(const eao_object_overlap_row& a, const eao_object_overlap
     return (dis_x < sum_lenth_half) && (dis_y < sum_width_half) && (dis_z < sum_height_half);
 }
 
+// ---- what k_object_cuboids reads per object from device memory, for the callers that enqueue it: the file's own entry writes it on the host, the plan kernel
+// of csrc/object_chain.hip on the device.  An object with skip != 0 costs nothing: its workgroup leaves at once and stores no record.
+struct ObjDev {
+    int64_t pointStart, centroidStart;       // in entries of the packed lists
+    int32_t n, m;
+    float Ryaw[9];
+    int32_t skip;
+    double prev[3];
+};
+static_assert(sizeof(ObjDev) == 88, "ObjDev layout");
+
+#if defined(__HIPCC__)
+hipError_t enqueue_cuboids(hipStream_t stream, const ObjDev* objs, const float* points, const float* centroids, eao_object_cuboid_rec* records, unsigned n_obj);
+#endif
+
 // ---- what the entry points refuse (include/eao_fusion.h); nullptr = accepted
 inline const char* object_refusal(const eao_object_cuboid_desc& D) {
     if (D.n_points < 0 || D.n_centroids < 0) return "a negative count";

@@ -46,27 +46,6 @@ static_assert(sizeof(eao_object_points_rec) == 80, "record layout");
 static_assert(kBlock <= kChunk && kCandBlock <= kBlock, "a step of the erase waits in the chunk's LDS; one thread per candidate of a block");
 constexpr int kRecWords = sizeof(eao_object_points_rec) / 4;
 
-struct PtsDev {
-    eao_object_points_desc d;                // the scalars; its pointers are the host's and are not read
-    int64_t mapStart, candStart, listStart;  // in entries of the packed arrays
-};
-
-struct Bufs {
-    const PtsDev* descs;
-    const float* mapPts;
-    const int32_t* mapCount;
-    const float* candPts;
-    const int32_t* candCount;
-    int32_t *first, *rank, *app;             // per candidate (device only)
-    uint8_t* gate;
-    int32_t *target, *count;                 // per candidate
-    int32_t* list;
-    uint8_t* erased;
-    int32_t* surv;
-    float* survPts;                          // per list position
-    eao_object_points_rec* recs;
-};
-
 struct Shared {
     float tile[3][kTile];
     float sum[3][kChunk];
@@ -349,6 +328,26 @@ thread_local ObjectPointsCtx g_op;
 
 }  // namespace
 
+namespace eao {
+namespace object_points {
+
+bool launch_is_split(int64_t n_map, int64_t n_cand) { return n_cand * (n_map + n_cand) > kSplitPairs; }
+
+hipError_t enqueue_match(hipStream_t stream, const Bufs& B, unsigned n_desc, int64_t max_cand) {
+    const unsigned blocks = (unsigned)((max_cand + kCandBlock - 1) / kCandBlock);
+    hipLaunchKernelGGL(k_object_points_match, dim3(blocks, n_desc), dim3(kBlock), 0, stream, B);
+    return hipGetLastError();
+}
+
+hipError_t enqueue_finish(hipStream_t stream, const Bufs& B, unsigned n_desc, bool fused) {
+    if (fused) hipLaunchKernelGGL(k_object_points, dim3(n_desc), dim3(kBlock), 0, stream, B);
+    else hipLaunchKernelGGL(k_object_points_finish, dim3(n_desc), dim3(kBlock), 0, stream, B);
+    return hipGetLastError();
+}
+
+}  // namespace object_points
+}  // namespace eao
+
 extern "C" {
 
 eao_status eao_object_points_update_batch(int32_t n, const eao_object_points_desc* descs, const eao_object_points_out* outs) {
@@ -362,7 +361,7 @@ eao_status eao_object_points_update_batch(int32_t n, const eao_object_points_des
         nCand += descs[k].n_cand;
         EAO_REQUIRE(nMap + nCand <= kMaxBatchPoints, "more than 2^27 points in one call: split it");
         maxCand = descs[k].n_cand > maxCand ? descs[k].n_cand : maxCand;
-        split = split || (int64_t)descs[k].n_cand * ((int64_t)descs[k].n_map + descs[k].n_cand) > kSplitPairs;
+        split = split || launch_is_split(descs[k].n_map, descs[k].n_cand);
     }
     for (int32_t k = 0; k < n; k++) {
         const char* why = desc_refusal(descs[k]);
@@ -420,17 +419,14 @@ eao_status eao_object_points_update_batch(int32_t n, const eao_object_points_des
     eao::Drain drain(ctx.stream);
     EAO_HIP(hipMemcpyAsync(d, h, inEnd, hipMemcpyHostToDevice, ctx.stream));
     if (split) {
-        const unsigned blocks = (unsigned)((maxCand + kCandBlock - 1) / kCandBlock);
         ctx.clock.mark(0, ctx.stream);
-        hipLaunchKernelGGL(k_object_points_match, dim3(blocks, (unsigned)N), dim3(kBlock), 0, ctx.stream, B);
-        EAO_HIP(hipGetLastError());
+        EAO_HIP(enqueue_match(ctx.stream, B, (unsigned)N, maxCand));
         ctx.clock.mark(1, ctx.stream);
-        hipLaunchKernelGGL(k_object_points_finish, dim3((unsigned)N), dim3(kBlock), 0, ctx.stream, B);
+        EAO_HIP(enqueue_finish(ctx.stream, B, (unsigned)N, false));
     } else {
         ctx.clock.mark(1, ctx.stream);
-        hipLaunchKernelGGL(k_object_points, dim3((unsigned)N), dim3(kBlock), 0, ctx.stream, B);
+        EAO_HIP(enqueue_finish(ctx.stream, B, (unsigned)N, true));
     }
-    EAO_HIP(hipGetLastError());
     ctx.clock.mark(2, ctx.stream);
     EAO_HIP(hipMemcpyAsync(h + oGate, d + oGate, end - oGate, hipMemcpyDeviceToHost, ctx.stream));
     EAO_HIP(drain.wait(eao::Drain::Latency));

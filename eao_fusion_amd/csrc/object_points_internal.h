@@ -174,6 +174,37 @@ inline const char* out_refusal(const eao_object_points_desc& D, const eao_object
     return nullptr;
 }
 
+// ---- what the kernels of csrc/object_points.hip read and write, for the callers that enqueue them (its own entry and csrc/object_chain.hip)
+struct PtsDev {
+    eao_object_points_desc d;                // the scalars; its pointers are the host's and are not read
+    int64_t mapStart, candStart, listStart;  // in entries of the packed arrays
+};
+
+struct Bufs {
+    const PtsDev* descs;
+    const float* mapPts;
+    const int32_t* mapCount;
+    const float* candPts;
+    const int32_t* candCount;
+    int32_t *first, *rank, *app;             // per candidate (device only)
+    uint8_t* gate;
+    int32_t *target, *count;                 // per candidate
+    int32_t* list;
+    uint8_t* erased;
+    int32_t* surv;
+    float* survPts;                          // per list position
+    eao_object_points_rec* recs;
+};
+
+#if defined(__HIPCC__)
+// whether a desc of these sizes takes the call to the two-launch form
+bool launch_is_split(int64_t n_map, int64_t n_cand);
+// k_object_points_match over the descs of B (the two-launch form only), max_cand = the largest n_cand among them
+hipError_t enqueue_match(hipStream_t stream, const Bufs& B, unsigned n_desc, int64_t max_cand);
+// k_object_points (fused) or k_object_points_finish (behind enqueue_match)
+hipError_t enqueue_finish(hipStream_t stream, const Bufs& B, unsigned n_desc, bool fused);
+#endif
+
 // ---- upstream's form, literally: the fallback no entry point takes, the sanitizer target and the -O3 baseline of tools/bench_object_points.py
 struct Walk {
     eao_object_points_rec rec;

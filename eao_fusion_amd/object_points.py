@@ -41,32 +41,37 @@ def lists_of(d):
     return mp, mc, cp, cc
 
 
+def fill_desc(c, o, d, fill, want_points):
+    """one eao_object_points_desc `c` and eao_object_points_out `o` from the dict d; returns the numpy buffers behind them.  An `n_map` / `n_cand` / `null` key
+    overrides what the lists say (a test provokes a refusal)"""
+    mp, mc, cp, cc = lists_of(d)
+    M, Cn = len(mp), len(cp)
+    for f in INTS:
+        setattr(c, f, int(d.get(f, 0)))
+    for f in FLOATS:
+        setattr(c, f, float(np.float32(d.get(f, 0.0))))
+    for f, (ct, n, dt) in VECTORS.items():
+        setattr(c, f, (ct * n)(*np.asarray(d.get(f, DEFAULTS.get(f, np.zeros(n))), dt).reshape(n).tolist()))
+    c.n_map, c.n_cand = d.get("n_map", M), d.get("n_cand", Cn)
+    null = d.get("null", ())
+    c.map_points = _lib.ptr(mp) if M and "map_points" not in null else None
+    c.map_count = _lib.ptr(mc) if M and "map_count" not in null else None
+    c.cand_points = _lib.ptr(cp) if Cn and "cand_points" not in null else None
+    c.cand_count = _lib.ptr(cc) if Cn and "cand_count" not in null else None
+    out = dict(rec=_filled(1, RECORD_DTYPE, fill), gate=_filled(max(Cn, 1), np.uint8, fill), target=_filled(max(Cn, 1), np.int32, fill),
+               count=_filled(max(Cn, 1), np.int32, fill), list=_filled(2 * max(M + Cn, 1), np.int32, fill), erased=_filled(max(M + Cn, 1), np.uint8, fill),
+               survivors=_filled(2 * max(M + Cn, 1), np.int32, fill), points=_filled(3 * max(M + Cn, 1), np.float32, fill) if want_points else None)
+    c.survivors = _lib.ptr(out["points"])
+    for f in ("rec", "gate", "target", "count", "list", "erased", "survivors"):
+        setattr(o, f, None if f in null else _lib.ptr(out[f]))
+    return mp, mc, cp, cc, out
+
+
 def _descs(descs, fill, want_points):
-    """the C arrays of a batch and the numpy buffers behind them; an `n_map` / `n_cand` / `null` key overrides what the lists say (a test provokes a refusal)"""
+    """the C arrays of a batch and the numpy buffers behind them"""
     keep, cd, co = [], (_lib.ObjectPointsDesc * max(len(descs), 1))(), (_lib.ObjectPointsOut * max(len(descs), 1))()
     for k, d in enumerate(descs):
-        mp, mc, cp, cc = lists_of(d)
-        M, Cn = len(mp), len(cp)
-        c = cd[k]
-        for f in INTS:
-            setattr(c, f, int(d.get(f, 0)))
-        for f in FLOATS:
-            setattr(c, f, float(np.float32(d.get(f, 0.0))))
-        for f, (ct, n, dt) in VECTORS.items():
-            setattr(c, f, (ct * n)(*np.asarray(d.get(f, DEFAULTS.get(f, np.zeros(n))), dt).reshape(n).tolist()))
-        c.n_map, c.n_cand = d.get("n_map", M), d.get("n_cand", Cn)
-        null = d.get("null", ())
-        c.map_points = _lib.ptr(mp) if M and "map_points" not in null else None
-        c.map_count = _lib.ptr(mc) if M and "map_count" not in null else None
-        c.cand_points = _lib.ptr(cp) if Cn and "cand_points" not in null else None
-        c.cand_count = _lib.ptr(cc) if Cn and "cand_count" not in null else None
-        out = dict(rec=_filled(1, RECORD_DTYPE, fill), gate=_filled(max(Cn, 1), np.uint8, fill), target=_filled(max(Cn, 1), np.int32, fill),
-                   count=_filled(max(Cn, 1), np.int32, fill), list=_filled(2 * max(M + Cn, 1), np.int32, fill), erased=_filled(max(M + Cn, 1), np.uint8, fill),
-                   survivors=_filled(2 * max(M + Cn, 1), np.int32, fill), points=_filled(3 * max(M + Cn, 1), np.float32, fill) if want_points else None)
-        c.survivors = _lib.ptr(out["points"])
-        for f in ("rec", "gate", "target", "count", "list", "erased", "survivors"):
-            setattr(co[k], f, None if f in null else _lib.ptr(out[f]))
-        keep.append((mp, mc, cp, cc, out))
+        keep.append(fill_desc(cd[k], co[k], d, fill, want_points))
     return keep, cd, co
 
 

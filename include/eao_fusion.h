@@ -1689,6 +1689,81 @@ eao_status eao_object_points_set_profiling(int32_t on);
 eao_status eao_object_points_last_kernel_ms(float* kernel_ms /* 2 */);
 
 /* ---------------------------------------------------------------------------------------------------
+ * object_chain: the three numeric steps of Object_Map::DataAssociateUpdate (reference src/Object.cc:1352-1601) in ONE device call -- the point update above
+ * (stages 1-3 of eao_object_points_update_batch), the erase of the bad points (:1003-1024), ComputeMeanAndStandard with both UpdateObjPose calls
+ * (eao_object_cuboids_batch) and the isolation forest (:1239-1348, eao_object_iforest_outliers_batch) over the list the cuboid saw.  One upload, one download and
+ * one wait on the stream per call; the list a stage leaves is read by the next one from device memory, and no count travels to the host in between.  Every
+ * output is, bit for bit, what the three entries return when the caller chains them by hand (csrc/object_chain_internal.h).  The entries
+ * are stateless; each host thread has its own stream and staging.  EAO_ERR_INVALID leaves every output untouched.  Two calls on the same arguments return the
+ * same bytes, on one thread or on several.
+ *
+ * A desc:
+ *   points                an eao_object_points_desc; its `survivors` is ignored here
+ *   map_bad, cand_bad     n_map and n_cand bytes: isBad() of every point (a non-zero byte is a bad point)
+ *   cand_alias            optional, n_cand entries: the list position < n_map of the entry that is the very MapPoint of candidate j, or -1.  Upstream's step 3
+ *                         raises object_id_vector of a gated-in candidate before step 4 reads it (:1550-1559): with cand_alias the PROJECTION erase reads, for list
+ *                         entry k, map_count[k] plus the number of gated-in candidates whose alias is k (the entry's host half forms the sum from the same gate
+ *                         rule the device runs; integers only).  NULL gives exactly stage 3 of eao_object_points_update_batch.
+ *   n_centroids, centroids, Ryaw, prev_cuboid_center        the cuboid's inputs as in eao_object_cuboid_desc (centroids = mObjectFrame[i]->_Pos AFTER step 2's push)
+ *   class_id, bi_forest   mnClass and the file-level flag biForest (:1241)
+ * Per desc, in upstream's order:
+ *   1-3.  the point update: out.points receives what eao_object_points_update_batch writes (rec.sum_pos stays what stage 3 computed; upstream sums anew at :1001
+ *         and so does the cuboid record).  A status other than DONE writes the points record and nothing else, and the stages behind cost no device work worth
+ *         naming: their workgroups leave at once.
+ *   4.    the survivors whose bad flag is set leave, in order: `final` receives the list of the cuboid and of the forest as (source, index) pairs, rec.n_final
+ *         their number.
+ *   5.    cuboid: the eao_object_cuboid_rec of that list (EMPTY when n_final == 0).
+ *   6.    forest: the object runs when bi_forest is set, its class is none of 75 / 64 / 65 and n_final >= 30; the device decides this from n_final.  Then
+ *         Build(50, 12345, data, n_final / 2); the device returns the total path length per final position and the entry's host half finishes as
+ *         eao_object_iforest_outliers_batch does (libm's pow, then the threshold).  forest_flags per final position (1 = erase), rec.removed their number, scores
+ *         (optional) the anomaly scores, -1.0 where the forest was skipped.  rec.forest_status: SKIPPED, DONE, or FAILED where upstream's Build returns false
+ *         (flags all zero, scores -1.0).
+ * Refused with EAO_ERR_INVALID before anything is written: everything the three entries refuse; map_bad or cand_bad NULL where its count is positive; an alias
+ * outside -1 .. n_map - 1; an output pointer that is NULL where its list can be non-empty; and a desc whose forest may run (bi_forest set, class not exempt) with
+ * n_map + n_cand > EAO_IFOREST_MAX_POINTS: the true count is only known on the device, and the bound is the honest check.
+ * Out of scope: the order of :718-719 (forest, erase, then cuboid; RefineObjects of include/eaofusion/ObjectMap.h stays as it is): its erase needs the flag on
+ * the device, and the flag is pow(2, x) > th with libm's pow, which the device does not have bit for bit.  A handle that keeps lists resident across frames:
+ * local bundle adjustment moves the points between frames.  MergeTwoMapObjsPoints, BigToSmall and DivideEquallyTwoObjs: no chain follows them upstream. */
+#define EAO_OBJECT_CHAIN_FOREST_SKIPPED 0
+#define EAO_OBJECT_CHAIN_FOREST_DONE 1
+#define EAO_OBJECT_CHAIN_FOREST_FAILED 2
+typedef struct {
+    eao_object_points_desc points;
+    const uint8_t* map_bad;       /* n_map */
+    const uint8_t* cand_bad;      /* n_cand */
+    const int32_t* cand_alias;    /* optional, n_cand */
+    int32_t n_centroids;
+    int32_t class_id;
+    const float* centroids;       /* n_centroids x 3 */
+    float Ryaw[9];
+    int32_t bi_forest;
+    double prev_cuboid_center[3];
+} eao_object_chain_desc;
+typedef struct {
+    int32_t n_final;
+    int32_t forest_status;
+    int32_t removed;
+    int32_t reserved;             /* zero */
+} eao_object_chain_rec; /* 16 bytes */
+typedef struct {
+    eao_object_points_out points;
+    eao_object_chain_rec* rec;
+    int32_t* final;               /* (n_map + n_cand) x 2, n_final pairs written */
+    eao_object_cuboid_rec* cuboid;
+    uint8_t* forest_flags;        /* n_map + n_cand, n_final written */
+    double* scores;               /* optional, n_map + n_cand, n_final written */
+} eao_object_chain_out;
+eao_status eao_object_update_chain_batch(int32_t n, const eao_object_chain_desc* descs, const eao_object_chain_out* outs);
+/* a batch of one */
+eao_status eao_object_update_chain(const eao_object_chain_desc* desc, const eao_object_chain_out* out);
+/* Diagnostic (tools/bench_object_chain.py): after eao_object_chain_set_profiling(1) on this thread, the device time in ms of the chain's kernels in this thread's
+ * last call that reached the device, from HIP events on its stream: k_object_points_match (-1 where the call ran fused), k_object_points (or
+ * k_object_points_finish), k_object_chain_plan, k_object_cuboids, k_iforest_build and k_iforest_score (-1 where no desc's forest could run).  An event call that
+ * fails costs that measurement and never fails the product call.  EAO_ERR_INVALID when no slot is measured. */
+eao_status eao_object_chain_set_profiling(int32_t on);
+eao_status eao_object_chain_last_kernel_ms(float* kernel_ms /* 6 */);
+
+/* ---------------------------------------------------------------------------------------------------
  * yolox: what YOLOX::Detect (reference src/YOLOX.cc:369-410) does AROUND the network, on the device.  The network itself is the integrator's engine; it reads
  * the blob and writes the head output in HBM, and nothing of either crosses to the host.
  *   in front   StaticResize (:51-62): r = min(S / (cols * 1.0), S / (rows * 1.0)) stored as float, unpad = (int)(r * cols) -- a float product truncated: a

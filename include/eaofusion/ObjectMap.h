@@ -437,6 +437,118 @@ int DataAssociateUpdate(ObjT& obj, Obj2DT* ObjectFrame, FrameT& mCurrentFrame, c
     return 1;
 }
 
+namespace object_map_detail {
+
+// one call of eao_object_update_chain for one object: the points call's lists, gathered once, and what the stages behind it need
+struct ChainCall {
+    PointsCall p;
+    std::vector<uint8_t> map_bad, cand_bad, forest_flags;
+    std::vector<int32_t> cand_alias, final_list;
+    std::vector<float> centroids;
+    eao_object_chain_desc d = eao_object_chain_desc();
+    eao_object_chain_rec rec = eao_object_chain_rec();
+    eao_object_cuboid_rec cuboid = eao_object_cuboid_rec();
+
+    // isBad() of every point, and per candidate the list position of the entry that is the very same MapPoint (-1: none)
+    template <class ObjT, class MapPointT>
+    void gather_flags(const ObjT& obj, const std::vector<MapPointT*>& cand) {
+        std::unordered_map<const MapPointT*, int32_t> at;
+        for (size_t k = obj.mvpMapObjectMappoints.size(); k-- > 0;) at[obj.mvpMapObjectMappoints[k]] = (int32_t)k;      // (the first of equal pointers)
+        for (size_t k = 0; k < obj.mvpMapObjectMappoints.size(); k++) map_bad.push_back(obj.mvpMapObjectMappoints[k]->isBad() ? 1 : 0);
+        for (size_t j = 0; j < cand.size(); j++) {
+            cand_bad.push_back(cand[j]->isBad() ? 1 : 0);
+            const auto it = at.find(cand[j]);
+            cand_alias.push_back(it == at.end() ? -1 : it->second);
+        }
+    }
+    bool run() {
+        const size_t M = p.map_count.size(), C = p.cand_count.size();
+        eao_object_points_desc& q = p.d;
+        q.n_map = (int32_t)M;
+        q.n_cand = (int32_t)C;
+        q.map_points = M ? p.map_points.data() : nullptr;
+        q.map_count = M ? p.map_count.data() : nullptr;
+        q.cand_points = C ? p.cand_points.data() : nullptr;
+        q.cand_count = C ? p.cand_count.data() : nullptr;
+        p.gate.assign(C + 1, 0); p.target.assign(C + 1, -1); p.count.assign(C + 1, 0);
+        p.list.assign(2 * (M + C) + 2, 0); p.erased.assign(M + C + 1, 0); p.survivors.assign(2 * (M + C) + 2, 0);
+        final_list.assign(2 * (M + C) + 2, 0);
+        forest_flags.assign(M + C + 1, 0);
+        d.points = q;
+        d.map_bad = M ? map_bad.data() : nullptr;
+        d.cand_bad = C ? cand_bad.data() : nullptr;
+        d.cand_alias = C ? cand_alias.data() : nullptr;
+        d.n_centroids = (int32_t)(centroids.size() / 3);
+        d.centroids = centroids.empty() ? nullptr : centroids.data();
+        eao_object_chain_out o = eao_object_chain_out();
+        o.points.rec = &p.rec; o.points.gate = p.gate.data(); o.points.target = p.target.data(); o.points.count = p.count.data();
+        o.points.list = p.list.data(); o.points.erased = p.erased.data(); o.points.survivors = p.survivors.data();
+        o.rec = &rec; o.final = final_list.data(); o.cuboid = &cuboid; o.forest_flags = forest_flags.data();
+        return eao_object_update_chain(&d, &o) == EAO_OK;
+    }
+};
+
+// :1003-1024 with the flags the chain was given: over the list as apply_erase left it (the survivors, in order), the bad points leave under the mutex
+template <class ObjT>
+void apply_bad(ObjT& obj, const ChainCall& c) {
+    std::unique_lock<std::mutex> lock(obj.mMutexMapPoints);
+    size_t at = 0;
+    for (auto pMP = obj.mvpMapObjectMappoints.begin(); pMP != obj.mvpMapObjectMappoints.end(); at++) {
+        bool bad = false;
+        if (at < (size_t)c.p.rec.n_survivors) {
+            const int32_t src = c.p.survivors[2 * at], idx = c.p.survivors[2 * at + 1];
+            bad = (src ? c.cand_bad[(size_t)idx] : c.map_bad[(size_t)idx]) != 0;
+        }
+        if (bad) pMP = obj.mvpMapObjectMappoints.erase(pMP);
+        else ++pMP;
+    }
+}
+
+}  // namespace object_map_detail
+
+// Object_Map::DataAssociateUpdate over ONE library call (eao_object_update_chain): the positions are gathered once, and the point update, the erase of the bad
+// points, the cuboid and the isolation forest run chained on the device.  The same three return values and the same members afterwards as DataAssociateUpdate
+// above.  The chain is pure, so a false step2() discards it, as the order above discards the points call.  Two differences: isBad() of a point is read when the
+// lists are gathered, not when ComputeMeanAndStandard would reach it; and a list that holds the same MapPoint twice hands the raised count of :1550-1559 to the
+// first of the two entries only.
+template <class ConvT, class ObjT, class Obj2DT, class FrameT, class ImageT, class Step2T>
+int DataAssociateUpdateChained(ObjT& obj, Obj2DT* ObjectFrame, FrameT& mCurrentFrame, const ImageT& image, int Flag, bool biForest, Step2T step2) {
+    if (ObjectFrame->_class_id != obj.mnClass) return 0;      // :1357
+    object_map_detail::ChainCall c;
+    eao_object_points_desc& d = c.p.d;
+    d.change_gate = ((Flag != 1) && (Flag != 4)) ? 1 : 0;      // :1364
+    d.gate = EAO_OBJECT_POINTS_GATE_RADIUS;
+    d.erase = EAO_OBJECT_POINTS_ERASE_PROJECTION;
+    d.box_off_edge = ((ObjectFrame->mBox.x > EAO_OBJECT_POINTS_EDGE_PIXELS) && (ObjectFrame->mBox.y > EAO_OBJECT_POINTS_EDGE_PIXELS) && (ObjectFrame->mBox.x + ObjectFrame->mBox.width < image.cols - EAO_OBJECT_POINTS_EDGE_PIXELS) &&
+                      (ObjectFrame->mBox.y + ObjectFrame->mBox.height < image.rows - EAO_OBJECT_POINTS_EDGE_PIXELS)) ? 1 : 0;      // :1538-1541
+    detail::read44(mCurrentFrame.mTcw, d.Tcw);
+    d.fx = mCurrentFrame.fx; d.fy = mCurrentFrame.fy; d.cx = mCurrentFrame.cx; d.cy = mCurrentFrame.cy;
+    d.cols = image.cols; d.rows = image.rows;
+    d.project_rect1[0] = obj.mRectProject.x; d.project_rect1[1] = obj.mRectProject.y; d.project_rect1[2] = obj.mRectProject.width; d.project_rect1[3] = obj.mRectProject.height;
+    d.box_rect[0] = ObjectFrame->mBoxRect.x; d.box_rect[1] = ObjectFrame->mBoxRect.y; d.box_rect[2] = ObjectFrame->mBoxRect.width; d.box_rect[3] = ObjectFrame->mBoxRect.height;
+    for (int k = 0; k < 3; k++) d.center[k] = obj.mCenter3D.template at<float>(k);
+    d.rmax = obj.mCuboid3D.mfRMax;
+    d.n_frames_after_push = (int32_t)obj.mObjectFrame.size() + 1;      // step 2 pushes before step 3 reads the size (:1451, :1469)
+    c.p.gather_list(obj);
+    c.p.gather_candidates(obj, ObjectFrame->Obj_c_MapPonits);
+    c.gather_flags(obj, ObjectFrame->Obj_c_MapPonits);
+    for (size_t i = 0; i < obj.mObjectFrame.size(); i++) detail::push3(obj.mObjectFrame[i]->_Pos, c.centroids);
+    detail::push3(ObjectFrame->_Pos, c.centroids);      // step 2 pushes the detection before the cuboid reads the centroids (:1451, :1054)
+    object_map_detail::ryaw(obj.mCuboid3D, c.d.Ryaw);
+    for (int k = 0; k < 3; k++) c.d.prev_cuboid_center[k] = obj.mCuboid3D.cuboidCenter[k];
+    c.d.class_id = (int32_t)obj.mnClass;
+    c.d.bi_forest = biForest ? 1 : 0;
+    if (!c.run()) return -1;
+    if (c.p.rec.status != EAO_OBJECT_POINTS_DONE) return 0;      // :1435 (an undefined projection associates nothing either)
+    if (!step2()) return 0;                                      // :1454
+    object_map_detail::apply_append(obj, ObjectFrame->Obj_c_MapPonits, c.p, true);
+    object_map_detail::apply_erase(obj, c.p);
+    object_map_detail::apply_bad(obj, c);
+    object_map_detail::write_members<ConvT>(obj, c.cuboid);      // :1593 (it sums mSumPointsPos anew, :1001)
+    object_map_detail::erase(obj, c.forest_flags.data(), (size_t)c.rec.n_final);      // :1596
+    return 1;
+}
+
 // Step 1 of Object_Map::MergeTwoMapObjs (:1766-1821): RepeatObj's points into obj.  Returns the number of points appended, or -1.
 template <class ObjT>
 int MergeTwoMapObjsPoints(ObjT& obj, ObjT& RepeatObj) {
